@@ -19,6 +19,12 @@ reach across the band edge); frontiers are merged across bands on the device
 receive, RCCL all-gather of the export records over the same communicator,
 dm_merge_bands; dm/sharded.py).
 
+A plain run sets up, warms up, times --steps steps and prints the line.
+--full adds the secondary measurements, each a run of its own after the timed
+steps (integrate-only / frontier-only times, per-kernel times and rooflines,
+host inputs, the explored-map pass, the CPU baselines); --dump-outputs DIR
+writes the last timed step's results as .npy files (dump_outputs).
+
 Prints ONE JSON line on rank 0.  See DESIGN.md §5 for every field.
 """
 from __future__ import annotations
@@ -86,6 +92,15 @@ def parse():
                     help="skip the PCIe-inclusive measurement (value_host_inputs)")
     ap.add_argument("--step-trace", default=None,
                     help="C3 / C4: write every timed step's host start-to-start time (us) to this JSON file")
+    ap.add_argument("--full", action="store_true",
+                    help="C3 / C4: after the timed steps also run the secondary measurements (integrate-only "
+                         "and frontier-only times, per-kernel times and rooflines, the PCIe-inclusive rate, "
+                         "the atomic peak, the explored-map frontier pass, the CPU baselines); without it "
+                         "the run sets up, warms up, times --steps steps and prints the line.  The "
+                         "--config C1 / C2 / C5 measurements always run whole")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy "
+                         "(dump_outputs): the cluster list and windows of the map around the robots")
     args = ap.parse_args()
     if args.depth is None:
         args.depth = 1 if args.config == "C1" else 2
@@ -352,6 +367,134 @@ def main():
                       "step_wall_us_p50": [float(x) for x in per[:, 3]],
                       "step_wall_us_max": [float(x) for x in per[:, 4]]}
 
+    if args.dump_outputs:
+        # before anything else touches the map: the last timed step's results
+        dump_outputs(args.dump_outputs, np, fr, band, pool[0][0], res, rank, world_size)
+    U_mean = float(np.mean([c[0] for c in counts]))
+    T_mean = float(np.mean([c[1] for c in counts]))
+    extras = None
+    if args.full:
+        extras = full_measurements(args, np, torch, dist, dm, synth, mapper, band, integrate, step, run_steps,
+                                   barrier, pool, params, world, stats, fr, ranks_info, U_all,
+                                   dict(rank=rank, world_size=world_size, local_rank=local_rank, cdev=cdev,
+                                        G=G, H_total=H_total, res=res, half_w=half_w, oy_global=oy_global,
+                                        c4=c4, N=N, amin=amin, inc=inc, U_mean=U_mean, T_mean=T_mean))
+
+    result = None
+    if rank == 0:
+        result = {
+            "metric": ("beam-cell updates/sec + frontier-extract ms (C4: 32768² shared map)" if c4
+                       else "beam-cell updates/sec + frontier-extract ms on 16384² grid"),
+            "value": U_all / elapsed,
+            "unit": "beam-cell updates/s",
+            "n_gpus": world_size,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong" if c4 else "weak",
+            "vs_baseline": None,
+            "dtype": "int32/u32 ray math + fp32 log-odds (fp64 endpoints)",
+            "data": "synthetic: seeded rectangle world, random-walk robots, LD06-format scans",
+            "config": {
+                "workload": ("C4: one 32768² grid @5cm shared by 32 robots (32 x 4096-beam scans "
+                             "per step), row bands over the ranks, integrate + full frontier "
+                             "extraction per step" if c4 else
+                             "C3: 16384² grid @5cm per GPU, 64-scan x 4096-beam batch "
+                             "integrate + full frontier extraction per step"),
+                "grid": [G, H_total],
+                "resolution_m": res,
+                "scans_per_batch": S,
+                "beams_per_scan": N,
+                "batch_pool": len(pool),
+                "parallelism": f"row-bands x{world_size}" if world_size > 1 else "single GPU",
+            },
+            # False: only the timed steps ran and the --full fields are absent
+            "full": bool(args.full),
+            "updates_per_batch": U_mean,
+            "touched_cells_per_batch": T_mean,
+            # the last pass collected: of the timed steps, or with --full of
+            # the frontier-only timing after them
+            "clusters": int(len(fr)) if fr is not None else None,
+            "stage_stats": {k: float(np.mean([st[k] for st in stats])) for k in stats[0]},
+            "scans_per_rank_batch": float(np.mean([p.shape[0] for p, _ in pool])),
+            "exchange": (f"device: halo rows sent to / received from the two neighbour bands (batched "
+                         f"{'RCCL' if args.backend == 'nccl' else args.backend} send / receive), export "
+                         f"records all-gathered ({args.records_comm} communicator), dm_merge_bands on "
+                         f"every rank" if world_size > 1 else None),
+            "exchange_fallbacks": (sum(ranks_info["exchange_fallbacks"]) if ranks_info
+                                   else getattr(mapper, "fallbacks", 0)),
+            # N > 1: the world size the process group reports, the launcher,
+            # and every rank's own timed region (value uses the slowest)
+            "ranks": ranks_info,
+            "pipelined": (f"step k+1's integrate front-end overlaps step k's frontier pass "
+                          f"(dm_set_overlap + dm_frontiers_begin/_end), {args.depth} passes in flight")
+            if pipelined else None,
+            "host_cpus": host_cpus,
+            "gen_seconds": t_gen,
+            # host-side start-to-start time of each timed step (rank 0): a
+            # host stall shows here as a long tail, kernel time in `roofline`
+            "step_wall_us": _cadence(marks),
+        }
+        if extras:
+            result.update(extras)
+        print(json.dumps(result), flush=True)
+    mapper.close()
+    if world_size > 1:
+        dist.destroy_process_group()
+    return result
+
+
+def dump_outputs(out_dir, np, fr, band, poses, res, rank=0, world_size=1, max_cells=1 << 30):
+    """--dump-outputs: what the timed path's last step left with its caller,
+    as float64 / float32 .npy files (~34 MB for C3), so that two builds can be
+    compared output for output (the inputs are seeded: the same arguments give
+    the same arrays).
+      clusters.npy         float64 [K, 6]: the last collected frontier pass's
+                           cluster records (label, size, sum_x, sum_y, cx_m,
+                           cy_m), sorted by label; rank 0 writes it (after the
+                           merge every rank holds the same list)
+      logodds_windows.npy  float32 [R, w, w]: the map's log-odds in a w x w
+      state_windows.npy    window (w = 256) around each of the first batch's
+                           (at most 64) robots, clipped to the band: a fixed
+                           sample of the map the steps integrated into (the
+                           robots random-walk inside these windows' reach)
+    N > 1: every rank writes its band's windows as *_rank<r>.npy.  A map of
+    more than `max_cells` cells (C5's 65536²) is not read back: clusters only."""
+    os.makedirs(out_dir, exist_ok=True)
+    if rank == 0:
+        c = fr.clusters if fr is not None else np.empty(0, dtype=[("label", "<i8")])
+        cols = [np.asarray(c[name], np.float64) for name in c.dtype.names]
+        np.save(os.path.join(out_dir, "clusters.npy"), np.stack(cols, axis=1))
+    rows, width = band.rows, band.width
+    if rows * width > max_cells:
+        return
+    prm = band.params
+    w = min(256, rows, width)
+    poses = np.asarray(poses, np.float64).reshape(-1, 3)[:64]
+    cx = np.floor((poses[:, 0] - prm.origin_x) / res).astype(np.int64)
+    cy = np.floor((poses[:, 1] - prm.origin_y) / res).astype(np.int64) - band.row0
+    x0 = np.clip(cx - w // 2, 0, width - w)
+    y0 = np.clip(cy - w // 2, 0, rows - w)
+    suffix = f"_rank{rank}" if world_size > 1 else ""
+    for name, grid in (("logodds", band.logodds()), ("state", band.state())):
+        win = np.stack([grid[y:y + w, x:x + w] for x, y in zip(x0, y0)]) if len(x0) else \
+            np.empty((0, w, w), grid.dtype)
+        np.save(os.path.join(out_dir, f"{name}_windows{suffix}.npy"), win.astype(np.float32))
+        del grid
+
+
+def full_measurements(args, np, torch, dist, dm, synth, mapper, band, integrate, step, run_steps, barrier,
+                      pool, params, world, stats, fr, ranks_info, U_all, ctx):
+    """--full: everything the C3 / C4 line reports beyond the timed steps, run
+    after them on the same mapper.  Returns the fields to add to the line
+    (rank 0; other ranks take part in the collectives and return None)."""
+    import gc
+
+    rank, world_size, local_rank, cdev = ctx["rank"], ctx["world_size"], ctx["local_rank"], ctx["cdev"]
+    G, H_total, res, half_w, oy_global = ctx["G"], ctx["H_total"], ctx["res"], ctx["half_w"], ctx["oy_global"]
+    c4, N, amin, inc, U_mean, T_mean = ctx["c4"], ctx["N"], ctx["amin"], ctx["inc"], ctx["U_mean"], ctx["T_mean"]
+
     # integrate-only and frontier-only timings (untimed w.r.t. `value`)
     reps = max(3, min(args.steps, 20))
     ti = []
@@ -370,8 +513,6 @@ def main():
     fstats = band.last_stats()  # the last pass's visited tiles / slots / clusters
     t_int = float(np.median(ti))
     t_fr = float(np.median(tf))
-    U_mean = float(np.mean([c[0] for c in counts]))
-    T_mean = float(np.mean([c[1] for c in counts]))
 
     # live per-kernel timing with HIP events on the library's stream
     band.profile(True)
@@ -479,100 +620,47 @@ def main():
         explored = explored_frontier(band, mapper, synth, world, G, H_total, res, -half_w, oy_global,
                                      args.seed, reps, np)
 
-    result = None
-    if rank == 0:
-        cpu = None
-        if world_size == 1 and args.cpu_seconds > 0:
-            cpu = cpu_baseline(params, pool, amin, inc, args.cpu_seconds)
-        fr_clusters = int(len(fr))
-        result = {
-            "metric": ("beam-cell updates/sec + frontier-extract ms (C4: 32768² shared map)" if c4
-                       else "beam-cell updates/sec + frontier-extract ms on 16384² grid"),
-            "value": U_all / elapsed,
-            "unit": "beam-cell updates/s",
-            "n_gpus": world_size,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong" if c4 else "weak",
-            "vs_baseline": None,
-            "dtype": "int32/u32 ray math + fp32 log-odds (fp64 endpoints)",
-            "data": "synthetic: seeded rectangle world, random-walk robots, LD06-format scans",
-            "config": {
-                "workload": ("C4: one 32768² grid @5cm shared by 32 robots (32 x 4096-beam scans "
-                             "per step), row bands over the ranks, integrate + full frontier "
-                             "extraction per step" if c4 else
-                             "C3: 16384² grid @5cm per GPU, 64-scan x 4096-beam batch "
-                             "integrate + full frontier extraction per step"),
-                "grid": [G, H_total],
-                "resolution_m": res,
-                "scans_per_batch": S,
-                "beams_per_scan": N,
-                "batch_pool": len(pool),
-                "parallelism": f"row-bands x{world_size}" if world_size > 1 else "single GPU",
-            },
-            "frontier_ms": t_fr * 1e3,
-            "integrate_ms": t_int * 1e3,
-            "integrate_updates_per_s": U_mean / t_int,
-            "updates_per_batch": U_mean,
-            "touched_cells_per_batch": T_mean,
-            "clusters": fr_clusters,
-            "kernel_avg_ms": avg,
-            "roofline": {
-                # bytes the DRAM actually moved (PMC) lead: the model's 8 B per
-                # update stay in LDS, so `frac` (the contract's algorithmic
-                # fraction) credits bytes that never reach HBM
-                "frac_traffic": (traffic / (t_accum_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS
-                                 if traffic and t_accum_ms > 0 else None),
-                "traffic": traffic,
-                "kernel": "tile_accum",
-                "dominant_kernel": dominant,
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s",
-                "frac": (achieved / HBM_PEAK_GBPS) if achieved else None,
-                "traffic_source": traffic_src,
-                "avg_launch_ms": t_accum_ms,
-                "algorithmic_bytes_per_launch": bytes_accum,
-                "bytes_model": "8*U + 25*T per call (SURVEY.md §8(d) per-unit figures)",
-                **hbm_model({k: float(np.mean([st[k] for st in stats]))
-                             for k in ("active_tiles", "pieces", "sparse_items")},
-                            t_accum_ms, T_mean),
-                "atomics": atom,
-                "frontier": fr_roof,
-            },
-            "value_host_inputs": host_inputs["value"] if host_inputs else None,
-            "host_inputs": host_inputs,
-            "frontier_ms_explored": explored["frontier_ms"] if explored else None,
-            "frontier_explored": explored,
-            "stage_stats": {k: float(np.mean([st[k] for st in stats])) for k in stats[0]},
-            "scans_per_rank_batch": float(np.mean([p.shape[0] for p, _ in pool])),
-            "exchange": (f"device: halo rows sent to / received from the two neighbour bands (batched "
-                         f"{'RCCL' if args.backend == 'nccl' else args.backend} send / receive), export "
-                         f"records all-gathered ({args.records_comm} communicator), dm_merge_bands on "
-                         f"every rank" if world_size > 1 else None),
-            "exchange_fallbacks": (sum(ranks_info["exchange_fallbacks"]) if ranks_info
-                                   else getattr(mapper, "fallbacks", 0)),
-            # N > 1: the world size the process group reports, the launcher,
-            # and every rank's own timed region (value uses the slowest)
-            "ranks": ranks_info,
-            "pipelined": (f"step k+1's integrate front-end overlaps step k's frontier pass "
-                          f"(dm_set_overlap + dm_frontiers_begin/_end), {args.depth} passes in flight")
-            if pipelined else None,
-            "cpu_baseline": cpu,
-            "host_cpus": host_cpus,
-            "gen_seconds": t_gen,
-            # host-side start-to-start time of each timed step (rank 0): a
-            # host stall shows here as a long tail, kernel time in `roofline`
-            "step_wall_us": _cadence(marks),
-        }
-        print(json.dumps(result), flush=True)
-    mapper.close()
-    if world_size > 1:
-        dist.destroy_process_group()
-    return result
+    if rank != 0:
+        return None
+    cpu = None
+    if world_size == 1 and args.cpu_seconds > 0:
+        cpu = cpu_baseline(params, pool, amin, inc, args.cpu_seconds)
+    return {
+        "frontier_ms": t_fr * 1e3,
+        "integrate_ms": t_int * 1e3,
+        "integrate_updates_per_s": U_mean / t_int,
+        "clusters": int(len(fr)),
+        "kernel_avg_ms": avg,
+        "roofline": {
+            # bytes the DRAM actually moved (PMC) lead: the model's 8 B per
+            # update stay in LDS, so `frac` (the contract's algorithmic
+            # fraction) credits bytes that never reach HBM
+            "frac_traffic": (traffic / (t_accum_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS
+                             if traffic and t_accum_ms > 0 else None),
+            "traffic": traffic,
+            "kernel": "tile_accum",
+            "dominant_kernel": dominant,
+            "bound": "hbm",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBPS,
+            "unit": "GB/s",
+            "frac": (achieved / HBM_PEAK_GBPS) if achieved else None,
+            "traffic_source": traffic_src,
+            "avg_launch_ms": t_accum_ms,
+            "algorithmic_bytes_per_launch": bytes_accum,
+            "bytes_model": "8*U + 25*T per call (SURVEY.md §8(d) per-unit figures)",
+            **hbm_model({k: float(np.mean([st[k] for st in stats]))
+                         for k in ("active_tiles", "pieces", "sparse_items")},
+                        t_accum_ms, T_mean),
+            "atomics": atom,
+            "frontier": fr_roof,
+        },
+        "value_host_inputs": host_inputs["value"] if host_inputs else None,
+        "host_inputs": host_inputs,
+        "frontier_ms_explored": explored["frontier_ms"] if explored else None,
+        "frontier_explored": explored,
+        "cpu_baseline": cpu,
+    }
 
 
 def pmc_summary(workload):
@@ -975,6 +1063,8 @@ def _run_replay(args, np, torch, synth, m, params, amin, dev):
     m.synchronize()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, np, fr, m, poses[-1:], 0.05)
     reps = min(200, n)
     ti, tf = [], []
     for k in range(reps):
@@ -1069,6 +1159,8 @@ def _run_c5(args, np, torch, synth, m, params, amin, dev, world):
         m.synchronize()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and N == sweep[-1]:
+            dump_outputs(args.dump_outputs, np, fr, m, pool[0][0], 0.01)  # the last sweep point's clusters
         U = sum(stats[k % len(stats)]["updates"] for k in range(args.warmup, args.warmup + args.steps))
         ti, tf = [], []
         for k in range(max(3, min(args.steps, 10))):

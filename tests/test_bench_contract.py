@@ -98,6 +98,52 @@ def test_bench_parser_knows_every_config():
         assert cfg in out.stdout
 
 
+def test_bench_parser_has_full_and_dump_outputs():
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"],
+                         capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    assert "--full" in out.stdout and "--dump-outputs DIR" in out.stdout
+
+
+def test_dump_outputs_writes_float_clusters_and_windows_on_the_robots(tmp_path):
+    """bench.dump_outputs on a stand-in band (no GPU): the cluster records as
+    float64 columns, and a 256² window of the map centred on each robot,
+    clipped at the map's edge."""
+    import types
+
+    import numpy as np
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    class Band:
+        rows, width, row0 = 400, 400, 0
+        params = types.SimpleNamespace(origin_x=-10.0, origin_y=-10.0)
+
+        def logodds(self):
+            return np.arange(160000, dtype=np.float32).reshape(400, 400)
+
+        def state(self):
+            return np.full((400, 400), -1, np.int8)
+
+    dt = [("label", "<i8"), ("size", "<i8"), ("sum_x", "<i8"), ("sum_y", "<i8"), ("cx_m", "<f8"), ("cy_m", "<f8")]
+    cl = np.zeros(3, dt)
+    cl["label"], cl["cy_m"] = [5, 7, 9], [0.25, 0.5, 0.75]
+    poses = np.array([[0.0, 0.0, 0.0], [9.9, -9.9, 1.0]])  # cells (200, 200) and (398, 2)
+    bench.dump_outputs(str(tmp_path), np, types.SimpleNamespace(clusters=cl), Band(), poses, 0.05)
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["clusters.npy", "logodds_windows.npy",
+                                                          "state_windows.npy"]
+    c = np.load(tmp_path / "clusters.npy")
+    assert c.dtype == np.float64 and c.shape == (3, 6)
+    assert c[:, 0].tolist() == [5.0, 7.0, 9.0] and c[:, 5].tolist() == [0.25, 0.5, 0.75]
+    L = np.load(tmp_path / "logodds_windows.npy")
+    assert L.dtype == np.float32 and L.shape == (2, 256, 256)
+    assert L[0, 0, 0] == 72 * 400 + 72 and L[0, -1, -1] == 327 * 400 + 327  # rows / columns 72..327
+    assert L[1, 0, 0] == 0 * 400 + 144 and L[1, -1, -1] == 255 * 400 + 399  # clipped: rows 0.., columns ..399
+    st = np.load(tmp_path / "state_windows.npy")
+    assert st.dtype == np.float32 and (st == -1.0).all()
+
+
 def test_r06_headline_fields():
     """Round 6's final C3 line: the measured traffic and the design's own byte
     model beside the SURVEY model's `frac`, and the two agree."""

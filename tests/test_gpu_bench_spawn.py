@@ -14,8 +14,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "3", "--warmup", "1", "--pool", "2", "--cpu-seconds", "0", "--no-explored",
-         "--no-host-inputs", "--profile-steps", "2", "--grid", "4096", "--robots", "8", "--beams", "1024"]
+SIZE = ["--steps", "3", "--warmup", "1", "--pool", "2", "--grid", "4096", "--robots", "8", "--beams", "1024"]
+# --full: the per-kernel times, the roofline and the exchange phases are measured after the timed steps
+SMALL = SIZE + ["--full", "--cpu-seconds", "0", "--no-explored", "--no-host-inputs", "--profile-steps", "2"]
 
 
 def _run(args, timeout=240):
@@ -57,3 +58,34 @@ def test_bench_one_gpu_runs_in_process():
     assert d["n_gpus"] == 1 and d["ranks"] is None
     assert d["config"]["grid"] == [4096, 4096] and d["config"]["parallelism"] == "single GPU"
     assert d["value"] > 0 and d["roofline"]["frac"] > 0
+    assert d["full"] is True
+
+
+def test_plain_run_times_the_steps_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full the line holds the timed steps' figures and none of the
+    secondary measurements; --dump-outputs writes the last timed step's
+    clusters and map windows as float .npy files, identical from run to run
+    (seeded inputs, deterministic kernels)."""
+    import numpy as np
+
+    runs = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        d = _run(["--gpus", "1"] + SIZE + ["--dump-outputs", str(out)])
+        assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "beam-cell updates/s"
+        for k in ("roofline", "kernel_avg_ms", "cpu_baseline", "host_inputs", "frontier_explored",
+                  "integrate_ms", "frontier_ms"):
+            assert k not in d, k
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["clusters.npy", "logodds_windows.npy", "state_windows.npy"]
+        arrays = {f: np.load(out / f) for f in files}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["clusters.npy"].dtype == np.float64 and arrays["clusters.npy"].shape == (d["clusters"], 6)
+        for f in ("logodds_windows.npy", "state_windows.npy"):
+            assert arrays[f].dtype == np.float32 and arrays[f].shape == (8, 256, 256)
+        # the windows sit on the robots: the steps wrote into every one of them
+        assert d["clusters"] > 0 and (arrays["state_windows.npy"] != -1).reshape(8, -1).any(axis=1).all()
+        runs.append(arrays)
+    for f in runs[0]:
+        np.testing.assert_array_equal(runs[0][f], runs[1][f], err_msg=f)

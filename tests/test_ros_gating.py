@@ -8,12 +8,11 @@ import ast
 import math
 import os
 
-import pytest
-
 from dm.ros_node import ScanGate, SlamParams, quaternion_from_yaw, stamp_seconds, yaw_from_quaternion
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_YAML = "/root/reference/server/thymio_project/config/slam_config.yaml"
+# the reference's server/thymio_project/config/slam_config.yaml, stored as a fixture
+REF_YAML = os.path.join(REPO, "tests", "golden", "slam_config.yaml")
 
 
 def test_defaults_are_the_reference_config():
@@ -25,7 +24,6 @@ def test_defaults_are_the_reference_config():
     assert gp.resolution == 0.05 and gp.range_max == 12.0 and gp.width == 4096
 
 
-@pytest.mark.skipif(not os.path.exists(REF_YAML), reason="reference checkout not present")
 def test_reads_the_reference_parameter_file():
     p = SlamParams.from_yaml(REF_YAML)
     assert p == SlamParams()  # every value the stage uses equals the defaults above

@@ -14,7 +14,7 @@ for r in $(seq $R); do
     head=${spec%%@*}; args=""; [ "$head" != "$spec" ] && args=${spec#*@}
     lt=${head%%:*}; envs=""; [ "$lt" != "$head" ] && envs=${head#*:}
     lib=$D/libdm_$lt.so; [ $lt = base ] && lib=$D/libdm.so
-    env ${envs//,/ } DM_LIB=$PWD/$lib timeout -k 10 150 python -u bench.py --steps $ST --warmup 40 --cpu-seconds 0 \
+    env ${envs//,/ } DM_LIB=$PWD/$lib timeout -k 10 150 python -u bench.py --full --steps $ST --warmup 40 --cpu-seconds 0 \
       --profile-steps 10 --no-explored --no-host-inputs ${args//,/ } > gpurun_out/ab_args_tmp.log 2>&1 \
       || { echo "$spec failed"; tail -8 gpurun_out/ab_args_tmp.log; exit 1; }
     python -c "

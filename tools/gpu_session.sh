@@ -4,7 +4,7 @@
 # Usage: bash tools/gpu_session.sh STEP...   (from the repo root)
 #   tests         pytest -m gpu
 #   tests:EXPR    pytest -m gpu -k EXPR
-#   bench         python bench.py (the driver's command, with CPU baseline)
+#   bench         python bench.py --full (every measurement, with CPU baseline)
 #   shard         2-rank sharded bench rehearsal (gloo, both ranks on GPU 0)
 #   prof          rocprofv3 --kernel-trace --stats over a bench run
 #   probe         rocprofv3 --kernel-trace --stats over tools/frontier_probe.py (explored map)
@@ -29,23 +29,23 @@ for s in "$@"; do
       rc=$?; echo "tests rc=$rc"; grep -E "FAILED|ERROR|passed|failed" $OUT/pytest_gpu.log | tail -8
       ok $rc || exit $rc ;;
     bench)
-      timeout -k 10 400 python -u bench.py > $OUT/bench.log 2>&1
+      timeout -k 10 400 python -u bench.py --full > $OUT/bench.log 2>&1
       rc=$?; echo "bench rc=$rc"; tail -1 $OUT/bench.log | cut -c1-600; ok $rc || exit $rc ;;
     rehearse:*)
       # N ranks of the multi-GPU bench on this one GPU (gloo, host-staged
       # exchange): the N > 1 line's fields, not xGMI timings
       n=${s#rehearse:}
-      timeout -k 10 500 python -u bench.py --gpus $n --backend gloo --device-override 0 --steps 20 --warmup 5 \
+      timeout -k 10 500 python -u bench.py --full --gpus $n --backend gloo --device-override 0 --steps 20 --warmup 5 \
         --cpu-seconds 0 --pool 3 --no-host-inputs > $OUT/rehearse_$n.log 2>&1
       rc=$?; echo "rehearse $n rc=$rc"; tail -1 $OUT/rehearse_$n.log | cut -c1-300; ok $rc || exit $rc ;;
     shard)
       timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --backend gloo --device-override 0 \
+        --master-port 29533 bench.py --full --gpus 2 --steps 5 --warmup 2 --backend gloo --device-override 0 \
         --cpu-seconds 0 --pool 3 > $OUT/shard.log 2>&1
       rc=$?; echo "shard rc=$rc"; tail -1 $OUT/shard.log | cut -c1-300; ok $rc || exit $rc ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run \
-        --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --cpu-seconds 0 > $OUT/prof.log 2>&1)
+        --output-format csv -- python3 $R/bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 > $OUT/prof.log 2>&1)
       rc=$?; echo "prof rc=$rc"; ok $rc || exit $rc ;;
     probe)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/probe -o run \
@@ -88,15 +88,15 @@ for s in "$@"; do
       # the driver's exact command three times (step traces), a 200-step run,
       # and a kernel trace of the driver's command (per-step kernels after reset)
       for i in 1 2 3; do
-        timeout -k 10 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 --step-trace $OUT/drv_trace_$i.json \
+        timeout -k 10 400 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 --step-trace $OUT/drv_trace_$i.json \
           > $OUT/drv_$i.log 2>&1
         rc=$?; echo "driver run $i rc=$rc"; ok $rc || exit $rc
       done
-      timeout -k 10 400 python -u bench.py --gpus 1 --steps 200 --warmup 5 --cpu-seconds 0 \
+      timeout -k 10 400 python -u bench.py --full --gpus 1 --steps 200 --warmup 5 --cpu-seconds 0 \
         --step-trace $OUT/drv_trace_200.json > $OUT/drv_200.log 2>&1
       rc=$?; echo "200-step rc=$rc"; ok $rc || exit $rc
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace -d $OUT/drvprof -o run \
-        --output-format csv -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 \
+        --output-format csv -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 \
         --no-explored --no-host-inputs > $OUT/drvprof.log 2>&1)
       rc=$?; echo "drvprof rc=$rc"; ok $rc || exit $rc ;;
     cfg:*)

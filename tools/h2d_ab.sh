@@ -12,7 +12,7 @@ for r in $(seq $R); do
   for spec in "$@"; do
     tag=$spec; lt=${spec%%:*}; envs=""; [ "$lt" != "$spec" ] && envs=${spec#*:}
     lib=$D/libdm_$lt.so; [ $lt = base ] && lib=$D/libdm.so
-    env ${envs//,/ } DM_LIB=$PWD/$lib timeout -k 10 150 python -u bench.py --steps 400 --warmup 40 --cpu-seconds 0 --profile-steps 0 \
+    env ${envs//,/ } DM_LIB=$PWD/$lib timeout -k 10 150 python -u bench.py --full --steps 400 --warmup 40 --cpu-seconds 0 --profile-steps 0 \
       --no-explored > gpurun_out/h2d_ab_tmp.log 2>&1 || { echo "$tag failed"; tail -5 gpurun_out/h2d_ab_tmp.log; exit 1; }
     python -c "
 import json; d=json.loads(open('gpurun_out/h2d_ab_tmp.log').read().strip().splitlines()[-1])

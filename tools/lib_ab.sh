@@ -20,7 +20,7 @@ import json; d=json.loads(open('gpurun_out/lib_ab_tmp.log').read().strip().split
 for p in d.get('sweep', []): print('$tag', 'beams', p.get('beams_per_scan'), 'ms/step', round(p.get('ms_per_step', 0), 3), 'int', round(p.get('integrate_ms', 0), 3), 'fr', round(p.get('frontier_ms', 0), 3), {k: round(v*1e3, 1) for k, v in (p.get('kernel_avg_ms') or {}).items()})
 " | tee -a $OUT
     else
-      env ${envs//,/ } DM_LIB=$PWD/$lib timeout -k 10 120 python -u bench.py --steps 400 --warmup 40 --cpu-seconds 0 --profile-steps 10 \
+      env ${envs//,/ } DM_LIB=$PWD/$lib timeout -k 10 120 python -u bench.py --full --steps 400 --warmup 40 --cpu-seconds 0 --profile-steps 10 \
         --no-explored --no-host-inputs > gpurun_out/lib_ab_tmp.log 2>&1 || { echo "$tag failed"; tail -5 gpurun_out/lib_ab_tmp.log; exit 1; }
       python -c "
 import json; d=json.loads(open('gpurun_out/lib_ab_tmp.log').read().strip().splitlines()[-1])

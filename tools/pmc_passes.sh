@@ -13,7 +13,7 @@ R=$PWD
 OUT=${1:-gpurun_out/pmc}
 shift
 CMD=("$@")
-[ ${#CMD[@]} -eq 0 ] && CMD=(python3 $R/bench.py --steps 5 --warmup 2 --cpu-seconds 0 --profile-steps 0 --pool 3 \
+[ ${#CMD[@]} -eq 0 ] && CMD=(python3 $R/bench.py --full --steps 5 --warmup 2 --cpu-seconds 0 --profile-steps 0 --pool 3 \
                              --no-explored --no-host-inputs --no-overlap)
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
