@@ -19,9 +19,9 @@
 
 #include <stdlib.h>
 
-// Wait for all three streams; nothing of this handle is in flight afterwards.
+// Wait for all four streams; nothing of this handle is in flight afterwards.
 hipError_t dm_sync_all(dm_grid* g) {
-  for (hipStream_t s : {g->stream, g->fe_streams[0], g->fe_streams[1], g->pass_stream, g->big_stream}) {
+  for (hipStream_t s : {g->stream, g->fe_stream, g->pass_stream, g->big_stream}) {
     if (!s) continue;
     const hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
@@ -543,8 +543,8 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   DM_HIP(hipMemset(g->fl_n, 0, sizeof(unsigned long long) * 48));
   if ((rc = dev_alloc(&g->bits_flag, 16, "bit-row hand-off word"))) return fail(rc);
   DM_HIP(hipMemset(g->bits_flag, 0, sizeof(unsigned long long) * 16));
-  if ((rc = dev_alloc(&g->fe_flag, 32, "front-end completion words"))) return fail(rc);
-  DM_HIP(hipMemset(g->fe_flag, 0, sizeof(unsigned long long) * 32));
+  if ((rc = dev_alloc(&g->fe_flag, 16, "front-end completion words"))) return fail(rc);
+  DM_HIP(hipMemset(g->fe_flag, 0, sizeof(unsigned long long) * 16));
   if ((rc = dev_alloc(&g->border, g->NT * 256, "frontier borders"))) return fail(rc);
   // [0, 4 NT): the dense passes' pair hand-off words; [4 NT, 8 NT): the
   // sparse passes' per-edge stamps (dm_frontier.hip, EDGE tile kernels)
@@ -582,37 +582,23 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   // so a front-end enqueued early fills what the map chain leaves idle instead
   // of competing with the accumulation for its CUs (round-2/3 A/B of every
   // combination and of CU-masked streams: DESIGN.md §3.3).
-  // (DM_PRIO_GRID / _FE / _PASS: 1 high, 0 low -- A/B builds only)
-#ifndef DM_PRIO_GRID
-#define DM_PRIO_GRID 1
-#endif
-#ifndef DM_PRIO_FE
-#define DM_PRIO_FE 0
-#endif
-#ifndef DM_PRIO_PASS
-#define DM_PRIO_PASS 1
-#endif
-
   int prio_lo = 0, prio_hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-  e = hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, DM_PRIO_GRID ? prio_hi : prio_lo);
+  e = hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, prio_hi);
   if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate"));
   g->own_stream = true;
-  for (int i = 0; i < dm_grid::kFeStreams; ++i) {
-    e = hipStreamCreateWithPriority(&g->fe_streams[i], hipStreamNonBlocking, DM_PRIO_FE ? prio_hi : prio_lo);
-    if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate(front-end)"));
-  }
-  e = hipStreamCreateWithPriority(&g->pass_stream, hipStreamNonBlocking, DM_PRIO_PASS ? prio_hi : prio_lo);
+  e = hipStreamCreateWithPriority(&g->fe_stream, hipStreamNonBlocking, prio_lo);
+  if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate(front-end)"));
+  e = hipStreamCreateWithPriority(&g->pass_stream, hipStreamNonBlocking, prio_hi);
   if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate(pass)"));
-  e = hipStreamCreateWithPriority(&g->big_stream, hipStreamNonBlocking, DM_PRIO_PASS ? prio_hi : prio_lo);
+  e = hipStreamCreateWithPriority(&g->big_stream, hipStreamNonBlocking, prio_hi);
   if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate(big)"));
   // ev_fe / ev_free only order the two streams on the device: no system-
   // scope fence (no host-visible cache writeback at every step).  The host
   // waits on a readback slot's event and then reads mapped host memory:
   // default fences.
   for (hipEvent_t* ev : {&g->ev_fe, &g->ev_bits[0], &g->ev_bits[1], &g->iw[0].ev_free, &g->iw[1].ev_free,
-                         &g->ev_bigfork, &g->ev_big, &g->flist_ev[0], &g->flist_ev[1], &g->ev_fe_end[0],
-                         &g->ev_fe_end[1]}) {
+                         &g->ev_bigfork, &g->ev_big, &g->flist_ev[0], &g->flist_ev[1]}) {
     e = hipEventCreateWithFlags(ev, hipEventDisableTiming | hipEventDisableSystemFence);
     if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
   }
@@ -637,8 +623,7 @@ int dm_destroy(dm_grid* g) {
   (void)dm_sync_all(g);
   for (auto& t : g->pending) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
   for (hipEvent_t ev : {g->ev_fe, g->ev_bits[0], g->ev_bits[1], g->iw[0].ev_free, g->iw[1].ev_free,
-                        g->ev_bigfork, g->ev_big, g->flist_ev[0], g->flist_ev[1], g->ev_fe_end[0],
-                        g->ev_fe_end[1]})
+                        g->ev_bigfork, g->ev_big, g->flist_ev[0], g->flist_ev[1]})
     if (ev) (void)hipEventDestroy(ev);
   for (auto& r : g->rb) {
     if (r.ev) (void)hipEventDestroy(r.ev);
@@ -646,8 +631,7 @@ int dm_destroy(dm_grid* g) {
     if (r.h_out) (void)hipHostFree(r.h_out - kRbHostRecords);
     dev_free(r.m_out);
   }
-  for (hipStream_t& fs : g->fe_streams)
-    if (fs) (void)hipStreamDestroy(fs);
+  if (g->fe_stream) (void)hipStreamDestroy(g->fe_stream);
   if (g->pass_stream) (void)hipStreamDestroy(g->pass_stream);
   if (g->big_stream) (void)hipStreamDestroy(g->big_stream);
   for (auto& f : g->fw) {
@@ -662,7 +646,7 @@ int dm_destroy(dm_grid* g) {
   for (auto& w : g->iw) {
     dev_free(w.pieces); dev_free(w.hitems); dev_free(w.litems); dev_free(w.heavy_list); dev_free(w.slabs);
     dev_free(w.heavy_done); dev_free(w.tile_count); dev_free(w.tile_cur); dev_free(w.cnt); dev_free(w.sh);
-    dev_free(w.pose4); dev_free(w.ranges);
+    dev_free(w.ranges);
     dev_free(w.beams); dev_free(w.blk_hist); dev_free(w.blk_n); dev_free(w.act_raw);
   }
   dev_free(g->L); dev_free(g->state); dev_free(g->fmask); dev_free(g->fedge); dev_free(g->tile_seen);
@@ -731,7 +715,7 @@ int enqueue_host_integrate(dm_grid* g, int32_t S, const double* poses, int32_t N
   if ((rc = grow_integrate(g, S, N))) return rc;
   if ((rc = ensure_trig(g, N, angle_min, angle_increment))) return rc;
   const int64_t nb = (int64_t)S * N;
-  hipStream_t fs = g->overlap ? dm_fe_stream_of(g, dm_next_set(g)) : g->stream;
+  hipStream_t fs = g->overlap ? g->fe_stream : g->stream;
   // the ranges copy goes to the device buffer of the workspace set this call
   // will use (dm_launch_integrate alternates them); with overlap the front-end
   // stream first waits until that set is free (its last accumulation, which
@@ -743,13 +727,9 @@ int enqueue_host_integrate(dm_grid* g, int32_t S, const double* poses, int32_t N
     DM_HIP(dm_mark_ws_free(g));
     DM_HIP(hipStreamWaitEvent(fs, w.free_wait ? w.free_wait : w.ev_free, 0));
   }
-  if ((int64_t)S * 4 > w.pose_cap || nb > w.ranges_cap || (int64_t)S * 4 > g->h_pose_cap) {
-    // the device buffers may still feed an in-flight call
+  if (nb > w.ranges_cap || (int64_t)S * 4 > g->h_pose_cap) {
+    // the buffers may still feed an in-flight call
     DM_HIP(dm_sync_all(g));
-  }
-  if ((int64_t)S * 4 > w.pose_cap) {
-    if ((rc = dev_alloc(&w.pose4, (int64_t)S * 4, "poses"))) return rc;
-    w.pose_cap = (int64_t)S * 4;
   }
   if (nb > w.ranges_cap) {
     if ((rc = dev_alloc(&w.ranges, nb, "ranges"))) return rc;
@@ -767,11 +747,8 @@ int enqueue_host_integrate(dm_grid* g, int32_t S, const double* poses, int32_t N
       // the GPU must not keep it in L2 (non-coherent host memory may be
       // cached there; the other mapped buffers the device reads are
       // Mapped | Coherent too)
-#ifndef DM_POSE_COHERENT
-#define DM_POSE_COHERENT 1  // 0: Mapped only (the round-5 allocation; A/B builds)
-#endif
       DM_HIP(hipHostMalloc((void**)&g->h_pose4[i], sizeof(double) * 4 * (size_t)std::max(S, 1),
-                           hipHostMallocMapped | (DM_POSE_COHERENT ? hipHostMallocCoherent : 0u)));
+                           hipHostMallocMapped | hipHostMallocCoherent));
       DM_HIP(hipHostGetDevicePointer((void**)&g->h_pose4_dev[i], g->h_pose4[i], 0));
     }
     g->h_pose_cap = (int64_t)std::max(S, 1) * 4;
@@ -787,20 +764,14 @@ int enqueue_host_integrate(dm_grid* g, int32_t S, const double* poses, int32_t N
     hp[4 * s + 2] = cos(yaw);  // C library, as the oracle
     hp[4 * s + 3] = sin(yaw);
   }
-  // into the set's buffers: their last readers (the front-end of the set's
-  // previous call, on fs) are done (above: that front-end precedes the set's
-  // last accumulation).  DM_HOST_POSE: no pose copy, k_beam_prep reads the
-  // mapped staging buffer (a 2 KB copy is a blit kernel, which waits for the
+  // the ranges into the set's buffer: its last reader (the front-end of the
+  // set's previous call, on fs) is done (above: that front-end precedes the
+  // set's last accumulation).  No pose copy: k_beam_prep reads the mapped
+  // staging slot (a 2 KB copy is a blit kernel, which waits for the
   // accumulation's CUs and adds a compute -> copy-engine hand-off)
-  const double* d_pose = w.pose4;
-  if (DM_HOST_POSE) {
-    d_pose = g->h_pose4_dev[slot];
-  } else if (S > 0) {
-    DM_HIP(hipMemcpyAsync(w.pose4, hp, sizeof(double) * 4 * (size_t)S, hipMemcpyHostToDevice, fs));
-  }
   if (nb > 0)
     DM_HIP(hipMemcpyAsync(w.ranges, ranges, sizeof(float) * (size_t)nb, hipMemcpyHostToDevice, fs));
-  if ((rc = dm_launch_integrate(g, S, d_pose, N, w.ranges, g->trig))) return rc;
+  if ((rc = dm_launch_integrate(g, S, g->h_pose4_dev[slot], N, w.ranges, g->trig))) return rc;
   // after the front-end (which read the staging buffer) and so after the
   // ranges copy: two calls later this event proves the caller's ranges
   // buffer has been read too (dm.h: reusable after the second call that follows)

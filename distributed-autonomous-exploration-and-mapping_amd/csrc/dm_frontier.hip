@@ -51,19 +51,7 @@ constexpr int kFT = 256;              // threads per frontier workgroup
 //    stamp (rel[4 NT + 4 tile + side] = pass stamp, a region of its own so
 //    the two encodings never meet); k_frontier_edges, launched after them,
 //    unites every tile pair across its edges and corners.
-// DM_EDGE_KERNEL (A/B builds): 1 the split above, 0 every pass in-kernel,
-// 2 every pass with the edge kernel.
-#ifndef DM_EDGE_KERNEL
-#define DM_EDGE_KERNEL 1
-#endif
-#ifndef DM_EDGE_HALVE
-#define DM_EDGE_HALVE 0
-#endif
-#if DM_EDGE_HALVE
-#define EDGE_UNITE dm_uf_unite_idx_halve
-#else
-#define EDGE_UNITE dm_uf_unite_idx2
-#endif
+// dm_enqueue_frontiers picks one per pass (`edge`).
 // waves per SIMD for k_frontier_tile: 7 workgroups per CU (LDS 22.6 KB each,
 // <= 72 VGPRs), so a C3 pass's ~3.3k listed tiles run in two rounds of the
 // chip's 1792 slots instead of three of 1280
@@ -504,9 +492,6 @@ constexpr int64_t kDenseMaxTiles = 4096;  // ... if it has at most this many til
 #define DM_FL_RUNS 384
 #endif
 constexpr int kRunsFast = DM_FL_RUNS;  // runs a tile-wave keeps in LDS
-#ifndef DM_FL_STRIDED
-#define DM_FL_STRIDED 0
-#endif
 #ifndef DM_FL_OCC
 #define DM_FL_OCC 7               // workgroups per CU (LDS 18.7 KB each, <= 72 VGPRs)
 #endif
@@ -579,9 +564,6 @@ __device__ inline uint32_t unknown_at(const FGeom& g, const int8_t* __restrict__
 // are coalesced: load q, lane l reads the 16-B chunk l % 4 of row 16q + l / 4
 // (16 rows x 64 B per wave instruction), then each lane gathers its row's four
 // chunks with shuffles.
-#ifndef DM_SEEN_HALO
-#define DM_SEEN_HALO 1  // 0: every halo cell loaded (A/B builds)
-#endif
 // unseen (wave-uniform): bit 0 left, 1 right, 2 above, 3 below, 4 above-left,
 // 5 above-right, 6 below-left, 7 below-right neighbour tile exists in this
 // band and is still all unknown (tile_seen 0): its facing cells are unknown
@@ -738,18 +720,16 @@ __global__ __launch_bounds__(kFW * 64) void k_frontier_bits(
       // relies on the tile_seen invariant of dm_internal.h (every state writer
       // sets the flag or is followed by k_recount)
       uint32_t unseen = 0u;
-      if (DM_SEEN_HALO) {
-        const bool l = tx > 0, r = tx + 1 < g.TX, u = ty > 0, d = ty + 1 < g.TY;
-        const int64_t t = tile;
-        if (l && !tile_seen[t - 1]) unseen |= 1u;
-        if (r && !tile_seen[t + 1]) unseen |= 2u;
-        if (u && !tile_seen[t - g.TX]) unseen |= 4u;
-        if (d && !tile_seen[t + g.TX]) unseen |= 8u;
-        if (u && l && !tile_seen[t - g.TX - 1]) unseen |= 16u;
-        if (u && r && !tile_seen[t - g.TX + 1]) unseen |= 32u;
-        if (d && l && !tile_seen[t + g.TX - 1]) unseen |= 64u;
-        if (d && r && !tile_seen[t + g.TX + 1]) unseen |= 128u;
-      }
+      const bool l = tx > 0, r = tx + 1 < g.TX, u = ty > 0, d = ty + 1 < g.TY;
+      const int64_t t = tile;
+      if (l && !tile_seen[t - 1]) unseen |= 1u;
+      if (r && !tile_seen[t + 1]) unseen |= 2u;
+      if (u && !tile_seen[t - g.TX]) unseen |= 4u;
+      if (d && !tile_seen[t + g.TX]) unseen |= 8u;
+      if (u && l && !tile_seen[t - g.TX - 1]) unseen |= 16u;
+      if (u && r && !tile_seen[t - g.TX + 1]) unseen |= 32u;
+      if (d && l && !tile_seen[t + g.TX - 1]) unseen |= 64u;
+      if (d && r && !tile_seen[t + g.TX + 1]) unseen |= 128u;
       tile_rows(g, state, halo, tx0, ty0, lane, unseen, U, Fr, uL, uR, Ue, eL, eR);
     } else {
       // fmask: [tile][row][16] nibble bytes (free | unknown << 4)
@@ -819,11 +799,7 @@ __global__ __launch_bounds__(kFW * 64, DM_FL_OCC) void k_frontier_tile(
   // take four consecutive listed tiles (horizontal neighbours share the
   // 128-byte lines of their rows and their halo columns: measured 129 vs
   // 190 us on the explored C3 map against tiles a quarter list apart)
-#if DM_FL_STRIDED
-  const int64_t wid = (int64_t)w * gridDim.x + blockIdx.x;
-#else
   const int64_t wid = (int64_t)blockIdx.x * kFW + w;
-#endif
   const int shard = (int)(wid % kShards);
   const long long sh0 = (long long)shard * g.slot_per;
   const bool dense = g.want_mask || g.want_labels;
@@ -1072,7 +1048,7 @@ __global__ __launch_bounds__(kFW * 64, DM_FL_OCC) void k_frontier_tile(
   DM_PHW_FLUSH(dm_phase_acc_ftile);
 }
 
-// Unions across tile edges, after the tile kernels of a pass (DM_EDGE_KERNEL).
+// Unions across tile edges, after the tile kernels of a pass (EDGE = true).
 // One wave per listed tile, which owns the relations to its right, lower,
 // lower-left and lower-right neighbours (every adjacent tile pair has exactly
 // one owner).  A relation is united only where both tiles published the
@@ -1086,15 +1062,12 @@ __global__ __launch_bounds__(kFW * 64, DM_FL_OCC) void k_frontier_tile(
 // a returning hand-off atomic and the neighbour's border loads (C3: 35 % of
 // k_frontier_tile_big's workgroup time, profiles/r06_phase_c3.log); here
 // they are thousands of short independent waves.
-#ifndef DM_EDGE_WAVES
-#define DM_EDGE_WAVES 1  // waves per listed tile in k_frontier_edges (2: one per relation, A/B)
-#endif
 __global__ __launch_bounds__(kFW * 64) void k_frontier_edges(FGeom g, const int32_t* __restrict__ ftiles,
                                                              const unsigned long long* __restrict__ list_n,
                                                              const int32_t* __restrict__ border,
                                                              const unsigned long long* __restrict__ rel,
                                                              int32_t* slot_parent, unsigned long long* cnt) {
-  constexpr int kRel = DM_EDGE_WAVES == 2 ? 1 : 2;  // relations per wave
+  constexpr int kRel = 2;  // relations per wave
   const unsigned long long stamp = cnt[CNT_STAMP];
   const int w = threadIdx.x >> 6, lane = __lane_id();
   const int64_t nft = (int64_t)*list_n;
@@ -1102,11 +1075,9 @@ __global__ __launch_bounds__(kFW * 64) void k_frontier_edges(FGeom g, const int3
   const unsigned long long* est = rel + 4 * g.NT;  // the per-edge stamps (EDGE tile kernels)
   __shared__ int2 s_pairs[kFW][kRel * 4 * 64];  // a wave's pairs (<= 3 per lane + a corner, per relation)
   // relation 0: the tile's right edge (and both lower corners, on lanes 0 /
-  // 63); relation 1: its lower edge.  One wave per listed tile takes both
-  // (DM_EDGE_WAVES 1), or wave 2j + r relation r of tile j (2)
-  const int64_t nv = DM_EDGE_WAVES == 2 ? 2 * nft : nft;
-  for (int64_t v = (int64_t)blockIdx.x * kFW + w; v < nv; v += (int64_t)gridDim.x * kFW) {
-    const int64_t tile = __builtin_amdgcn_readfirstlane(ftiles[DM_EDGE_WAVES == 2 ? v >> 1 : v]);
+  // 63); relation 1: its lower edge.  One wave per listed tile takes both.
+  for (int64_t v = (int64_t)blockIdx.x * kFW + w; v < nft; v += (int64_t)gridDim.x * kFW) {
+    const int64_t tile = __builtin_amdgcn_readfirstlane(ftiles[v]);
     const int32_t tx = (int32_t)(tile % g.TX), ty = (int32_t)(tile / g.TX);
     const bool right = tx + 1 < g.TX, down = ty + 1 < g.TY, left = tx > 0;
     // everything in ONE round of loads after the tile id: the stamps that
@@ -1117,10 +1088,9 @@ __global__ __launch_bounds__(kFW * 64) void k_frontier_edges(FGeom g, const int3
     bool has_nb[kRel];
 #pragma unroll
     for (int q = 0; q < kRel; ++q) {
-      const int rk = DM_EDGE_WAVES == 2 ? (int)(v & 1) : q;
-      const int64_t nb = rk == 0 ? (right ? tile + 1 : tile) : (down ? tile + g.TX : tile);
-      const int my_side = rk == 0 ? 3 : 1, nb_side = rk == 0 ? 2 : 0;
-      has_nb[q] = rk == 0 ? right : down;
+      const int64_t nb = q == 0 ? (right ? tile + 1 : tile) : (down ? tile + g.TX : tile);
+      const int my_side = q == 0 ? 3 : 1, nb_side = q == 0 ? 2 : 0;
+      has_nb[q] = q == 0 ? right : down;
       m_me[q] = est[4 * tile + my_side];
       m_nb[q] = est[4 * nb + nb_side];
       sl[q] = border[tile * 256 + my_side * 64 + lane];
@@ -1128,8 +1098,7 @@ __global__ __launch_bounds__(kFW * 64) void k_frontier_edges(FGeom g, const int3
     }
     // corners (with relation 0, lanes 0 / 63): this tile's (63, 0) / (63, 63)
     // against the lower-left tile's (0, 63) / the lower-right tile's (0, 0)
-    const bool rel0 = DM_EDGE_WAVES == 2 ? (v & 1) == 0 : true;
-    const bool corner_lane = rel0 && down && ((lane == 0 && left) || (lane == 63 && right));
+    const bool corner_lane = down && ((lane == 0 && left) || (lane == 63 && right));
     const int64_t dn = lane == 0 ? tile + g.TX - 1 : tile + g.TX + 1;
     unsigned long long m_row = 0ull, m_dn = 0ull;
     int32_t c_me = -1, c_dn = -1;
@@ -1188,7 +1157,7 @@ __global__ __launch_bounds__(kFW * 64) void k_frontier_edges(FGeom g, const int3
     wave_lds_sync();
     for (int i = lane; i < total; i += 64) {
       const int2 pr = lst[i];
-      EDGE_UNITE(slot_parent, pr.x, pr.y, uflag, kOvUnionFind);
+      dm_uf_unite_idx2(slot_parent, pr.x, pr.y, uflag, kOvUnionFind);
     }
     wave_lds_sync();
   }
@@ -1891,8 +1860,7 @@ int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool spli
   // clusters than tiles (C5-4096's 4.6 per tile: many distinct pairs per
   // edge, step 2-15 % slower with the edge kernel);
   // profiles/r06_edge_kernel_ab.log.  Both are exact for any map.
-  const bool edge = DM_EDGE_KERNEL == 2 ||
-                    (DM_EDGE_KERNEL == 1 && !dense && g->sort_hint <= std::max<int64_t>(g->ftile_hint, 1));
+  const bool edge = !dense && g->sort_hint <= std::max<int64_t>(g->ftile_hint, 1);
   auto* const big_kernel = edge ? k_frontier_tile_big<true> : k_frontier_tile_big<false>;
   auto* const wave_kernel = edge ? k_frontier_tile<true> : k_frontier_tile<false>;
   dm_timer_begin(g, "frontier_bits", &t);
@@ -1960,8 +1928,8 @@ int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool spli
   }
   if (edge) {
     dm_timer_begin(g, "frontier_edges", &t, ps);
-    // DM_EDGE_WAVES waves per listed tile (the kernel grid-strides)
-    DM_LAUNCH(k_frontier_edges, dim3(grid_for(DM_EDGE_WAVES * std::min<int64_t>(want_waves, g->NT), kFW, 16384)),
+    // one wave per listed tile (the kernel grid-strides)
+    DM_LAUNCH(k_frontier_edges, dim3(grid_for(std::min<int64_t>(want_waves, g->NT), kFW, 16384)),
               dim3(kFW * 64), 0, ps, fg, g->ftiles, list_n, g->border, g->rel,
               g->slot_parent, g->cnt);
     dm_timer_end(g, &t);

@@ -428,9 +428,6 @@ __device__ inline float apply_one(const ApplyArgs& p, float L, uint32_t h, uint3
 // v_cndmask reading it, and the compiler turned the per-cell selects into
 // exec-masked branches (3 scalar instructions + hazard s_nops per cell):
 // the selects below are v_bfi_b32 on masks built by integer arithmetic.
-#ifndef DM_APPLY_BFI
-#define DM_APPLY_BFI 1  // 0: the compare / select form (A/B builds)
-#endif
 // x != 0 ? 0xFFFFFFFF : 0
 __device__ inline uint32_t nz_mask(uint32_t x) {
   uint32_t r;
@@ -606,7 +603,7 @@ struct CellRows {
 #pragma unroll
         for (int e = 0; e < 4; ++e) dU += tx0 + cx + e < g.r.W ? h4[e] + m4[e] : 0u;
       }
-      if (vec && DM_APPLY_BFI) {
+      if (vec) {
         // branch- and compare-free per cell: untouched cells keep their values
         const float lv[4] = {l[rr].x, l[rr].y, l[rr].z, l[rr].w};
         const uint32_t sw = *reinterpret_cast<const uint32_t*>(&s[rr]);
@@ -626,24 +623,6 @@ struct CellRows {
             make_float4(__uint_as_float(nlb[0]), __uint_as_float(nlb[1]), __uint_as_float(nlb[2]),
                         __uint_as_float(nlb[3]));
         *reinterpret_cast<uint32_t*>(state + base) = ns;
-      } else if (vec) {
-        // branch-free per cell: untouched cells keep their values
-        float lv[4] = {l[rr].x, l[rr].y, l[rr].z, l[rr].w};
-        int8_t sv[4] = {(int8_t)s[rr].x, (int8_t)s[rr].y, (int8_t)s[rr].z, (int8_t)s[rr].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const bool hit = (h4[e] | m4[e]) != 0u;
-          const float nl = apply_one(p, lv[e], h4[e], m4[e]);
-          const int8_t ns = state_of(p, nl);
-          lv[e] = hit ? nl : lv[e];
-          sv[e] = hit ? ns : sv[e];
-          dT += hit ? 1 : 0;
-        }
-        const char4 ns4 = make_char4(sv[0], sv[1], sv[2], sv[3]);
-        dFree += zero_bytes(*reinterpret_cast<const uint32_t*>(&ns4)) -
-                 zero_bytes(*reinterpret_cast<const uint32_t*>(&s[rr]));
-        *reinterpret_cast<float4*>(L + base) = make_float4(lv[0], lv[1], lv[2], lv[3]);
-        *reinterpret_cast<char4*>(state + base) = ns4;
       } else {
         for (int e = 0; e < 4; ++e) {
           if ((h4[e] | m4[e]) == 0u || tx0 + cx + e >= g.r.W) continue;
@@ -700,10 +679,6 @@ __device__ inline int32_t walk_piece(uint32_t* tl, const PackedPiece& mine, bool
   return walk_tp(tl, tp, valid ? tp.len : 0, lane);
 }
 
-#ifndef DM_SPLIT_WALK
-#define DM_SPLIT_WALK 1  // 0: one lane per piece (the round-4 walk, for A/B builds)
-#endif
-
 // Light tiles: their pieces cross the tile from different directions and
 // rarely share cells, so each lane walks from its first cell, with no
 // stagger and no wrap.  A lane whose part has ended adds into its own spare
@@ -739,9 +714,9 @@ __device__ inline int32_t walk_tp_split(uint32_t* tl, const TilePiece& tp, int32
 // at most 255 and no partial sum carries into the next cell.
 constexpr int kSparseMax = 15;
 #ifndef DM_SPARSE_LIST
-#define DM_SPARSE_LIST 256  // touched 4-cell groups a wave lists (more: four row passes; 0 = always the passes, A/B)
+#define DM_SPARSE_LIST 256  // touched 4-cell groups a wave lists (more: four row passes)
 #endif
-constexpr int kSparseList = DM_SPARSE_LIST > 0 ? DM_SPARSE_LIST : 1;
+constexpr int kSparseList = DM_SPARSE_LIST;
 
 __device__ inline int32_t to_pitch64(int32_t a) {  // pitch-65 address or step -> pitch 64
   return a >= 0 ? a - a / kLdsPitch : -((-a) - (-a) / kLdsPitch);
@@ -892,9 +867,6 @@ __device__ inline void heavy_quarter(const Geom& g, const ApplyArgs& p, int64_t 
 #ifndef DM_ACCUM_OCC
 #define DM_ACCUM_OCC 7
 #endif
-#ifndef DM_EARLY_PIECES
-#define DM_EARLY_PIECES 1
-#endif
 constexpr int kAccumPerCu = DM_ACCUM_OCC;  // resident k_tile_accum workgroups per CU (4 waves each)
 __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
     Geom g, ApplyArgs p, const int4* __restrict__ list_a, int cnt_a, const int4* __restrict__ list_b,
@@ -961,7 +933,7 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
   auto split_of = [&](const int4& d) -> int32_t {
     const int32_t c = __builtin_amdgcn_readfirstlane(d.z);
     const int32_t heavy = __builtin_amdgcn_readfirstlane(d.w);
-    return DM_SPLIT_WALK && heavy < 0 ? dm_split_factor(c, kQuarter) : 1;
+    return heavy < 0 ? dm_split_factor(c, kQuarter) : 1;
   };
   // this thread's piece of item d (piece tid / f of a split light item)
   auto piece_of = [&](int32_t f) -> int32_t {
@@ -975,11 +947,10 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
     return pieces[c0 + min(piece_of(split_of(d)), max(c - 1, 0))];
   };
   mine = load_pieces(info);
-  // DM_EARLY_PIECES: the next item's pieces are issued right after this
-  // item's walk, BEFORE its apply stores.  Loads and stores share the wave's
-  // in-order vmcnt counter, so pieces issued after the stores (the other
-  // form) make the next walk's wait for them also a wait for the previous
-  // item's stores to drain.
+  // The next item's pieces are issued right after this item's walk, BEFORE
+  // its apply stores.  Loads and stores share the wave's in-order vmcnt
+  // counter, so pieces issued after the stores would make the next walk's
+  // wait for them also a wait for the previous item's stores to drain.
   PackedPiece mine_n = mine;
   for (int e = tid; e < kTileWords; e += kQuarter) tl[e] = 0u;
   if (tid == 0) { s_T = 0; s_free = 0; s_U = 0u; s_accT = 0ull; s_accU = 0ull; }
@@ -999,7 +970,7 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
       // heavy (a sensor's tile): the pieces all start at the sensor's cell;
       // walk_piece's staggered start keeps a wave's lanes on different cells
       walk_piece(tl, mine, tid < c, lane);
-      if (DM_EARLY_PIECES) mine_n = load_pieces(next);
+      mine_n = load_pieces(next);
       __syncthreads();
       DM_PH(dm_phase_acc_integrate, 1);
       DM_PH_COUNT(dm_phase_acc_integrate, 17, 1);
@@ -1088,7 +1059,7 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
         for (int o = 32; o > 0; o >>= 1) u += __shfl_xor(u, o);
         if (lane == 0) atomicAdd(&s_U, (uint32_t)u);
       }
-      if (DM_EARLY_PIECES) mine_n = load_pieces(next);
+      mine_n = load_pieces(next);
       __syncthreads();
       DM_PH(dm_phase_acc_integrate, 3);
       DM_PH_COUNT(dm_phase_acc_integrate, 16, 1);
@@ -1112,11 +1083,10 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
       tile_count[tile] = 0;  // ready for the next call
       tile_seen[tile] = 1;
     }
-    // the next item: its pieces go out now (or went out after the walk),
-    // ahead of its walk
+    // the next item: its pieces went out after this item's walk
     info = next;
     next = item_of(it + 2 * G);
-    mine = DM_EARLY_PIECES ? mine_n : load_pieces(info);
+    mine = mine_n;
     for (int e = tid; e < kTileWords; e += kQuarter) tl[e] = 0u;
     if (tid == 0) { s_T = 0; s_free = 0; s_U = 0u; }
     __syncthreads();
@@ -1148,7 +1118,7 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
     if (lane == 0 && wv == 0) tl_word += 1ull << 16;
     const int32_t tx0 = (tile % g.r.TX) * DM_TS, ty0 = (tile / g.r.TX) * DM_TS;
     // f = 64 / c lanes per piece (walk_piece_bytes' split)
-    const int32_t fs = DM_SPLIT_WALK ? dm_split_factor(c, 64) : 1;
+    const int32_t fs = dm_split_factor(c, 64);
     const float rfs = __builtin_amdgcn_rcpf((float)fs);
     const int32_t spi = fs == 1 ? lane : dm_udiv_small(lane, fs, rfs);
     const PackedPiece sp = spi < c ? pieces[c0 + spi] : no_piece();
@@ -1192,7 +1162,7 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (DM_SPARSE_LIST > 0 && nt <= kSparseList) {
+    if (nt <= kSparseList) {
       for (int e0 = 0; e0 < nt; e0 += 128) {
         const int ea = e0 + lane, eb = e0 + 64 + lane;
         const int wa = ea < nt ? lst[ea] : 0, wb = eb < nt ? lst[eb] : 0;
@@ -1575,7 +1545,7 @@ int dm_launch_integrate(dm_grid* g, int32_t S, const double* d_pose4, int32_t N,
   // accumulation and a frontier pass still in flight on g->stream
   hipStream_t fs = g->stream;
   if (g->overlap) {
-    fs = dm_fe_stream_of(g, g->iw_cur);
+    fs = g->fe_stream;
     DM_HIP(dm_mark_ws_free(g));  // still owed when no frontier pass came in between
     DM_HIP(hipStreamWaitEvent(fs, w.free_wait ? w.free_wait : w.ev_free, 0));
   }
@@ -1622,49 +1592,13 @@ int dm_launch_integrate(dm_grid* g, int32_t S, const double* d_pose4, int32_t N,
   if (g->overlap) {
     // front-end -> map update by a device-side seq gate (an event wait
     // measured 211-213 vs 215-218 x 10^9 updates/s, profiles/r02_fe_gate_ab.log)
-    DM_HIP(hipEventRecord(g->ev_fe_end[g->iw_cur % 2], fs));
-    unsigned long long* flag = dm_fe_flag_of(g, g->iw_cur);
-    if (int rc = dm_launch_signal(fs, flag)) return rc;
+    if (int rc = dm_launch_signal(fs, g->fe_flag)) return rc;
     // a timeout sets the sticky halt word (not this call's counters: the
     // front-end's own reset, still queued, would clear them)
-    if (int rc = dm_launch_gate(g->stream, flag, g->fe_flag + kHaltWord, 1ull, g->fault_gate ? 1000ull : 0ull,
-                                g->fault_gate ? (1ull << 40) : 0ull))
+    if (int rc = dm_launch_gate(g->stream, g->fe_flag, g->fe_flag + kHaltWord, 1ull,
+                                g->fault_gate ? 1000ull : 0ull, g->fault_gate ? (1ull << 40) : 0ull))
       return rc;
   }
-#ifdef DM_FE_DUMMY
-  // Diagnostic build only (never the product): one more k_beam_prep of this
-  // batch into scratch buffers on the front-end stream AFTER the front-end's
-  // hand-off signal (so it delays no accumulation), i.e. extra work beside
-  // the map chain; how much the pipelined step grows tells whether the step
-  // is bound by the chip's occupancy (workgroup-us) or by latency chains.
-  if (g->overlap) {
-    struct Dummy {
-      Beam* beams = nullptr; int32_t* tc = nullptr; int32_t* act = nullptr; int2* hist = nullptr;
-      int32_t* hn = nullptr; unsigned long long* sh = nullptr; unsigned long long* cnt = nullptr;
-      int64_t nb = 0, nt = 0, blocks = 0, act_cap = 0;
-    };
-    static Dummy d;
-    if (d.nb < nb || d.nt < g->NT || d.blocks < nblk || d.act_cap < g->act_cap) {
-      (void)hipDeviceSynchronize();
-      for (void* q : {(void*)d.beams, (void*)d.tc, (void*)d.act, (void*)d.hist, (void*)d.hn, (void*)d.sh,
-                      (void*)d.cnt})
-        if (q) (void)hipFree(q);
-      d.nb = nb; d.nt = g->NT; d.blocks = nblk; d.act_cap = g->act_cap;
-      DM_HIP(hipMalloc((void**)&d.beams, sizeof(Beam) * nb));
-      DM_HIP(hipMalloc((void**)&d.tc, sizeof(int32_t) * g->NT));
-      DM_HIP(hipMalloc((void**)&d.act, sizeof(int32_t) * g->act_cap * kShards));
-      DM_HIP(hipMalloc((void**)&d.hist, sizeof(int2) * 1024 * nblk));
-      DM_HIP(hipMalloc((void**)&d.hn, sizeof(int32_t) * nblk));
-      DM_HIP(hipMalloc((void**)&d.sh, sizeof(unsigned long long) * kShards * kShardWords));
-      DM_HIP(hipMalloc((void**)&d.cnt, sizeof(unsigned long long) * CNT_N));
-    }
-    DM_HIP(hipMemsetAsync(d.tc, 0, sizeof(int32_t) * g->NT, fs));
-    DM_LAUNCH(k_integrate_reset, dim3(2), dim3(256), 0, fs, d.cnt, d.sh);
-    DM_LAUNCH(k_beam_prep, dim3(nblk), dim3(256), 0, fs, a, ge, d_pose4, d_ranges, d_trig, d.beams, d.tc,
-              d.act, d.sh, d.hist, d.hn, d.cnt);
-    DM_HIP(hipGetLastError());
-  }
-#endif
   const int vec_ok = (g->W % 4 == 0) ? 1 : 0;
   // heavy chunks and medium tiles first (the long items), then the light
   // tiles; the last item of each heavy tile applies its merged slab
@@ -1679,10 +1613,7 @@ int dm_launch_integrate(dm_grid* g, int32_t S, const double* d_pose4, int32_t N,
   // instead (+25 % + 256 measured 1-3 % slower, profiles/r04_accum_grid_slack_ab.log)
   const volatile unsigned long long* hint = g->h_hint;
   const int64_t cap = g->hitem_cap + g->act_cap;
-#ifndef DM_ACCUM_HINT
-#define DM_ACCUM_HINT 1  // 0: capacity grids (the round-3 launch, for A/B builds)
-#endif
-  const int64_t hw = DM_ACCUM_HINT ? (int64_t)hint[0] : 0, hi = DM_ACCUM_HINT ? (int64_t)hint[1] : 0;
+  const int64_t hw = (int64_t)hint[0], hi = (int64_t)hint[1];
   const int64_t accum_wgs = hw > 0 ? std::min(cap, dm_quantize_up(hw + hw / 16 + 64)) : cap;
   DM_LAUNCH(k_tile_accum, dim3(grid_for(accum_wgs, 1, dm_grid::kAccumGrid)),
                      dim3(kQuarter), 0,

@@ -161,22 +161,12 @@ struct dm_grid {
   // (iw[p].ev_free), which is long done when the steps are pipelined, so no
   // marker sits behind the accumulation of call k.
   bool overlap = false;
-  // DM_FE_STREAMS = 2: consecutive calls' front-ends alternate between two
-  // streams (call k on fe_streams[set % 2], the set being its workspace
-  // set), so call k+1's front-end may start before call k's has finished
-  // instead of queueing behind it; each stream has its own hand-off words
-  // (dm_fe_flag_of).  1: one front-end stream (fe_streams[0]).
-#ifndef DM_FE_STREAMS
-#define DM_FE_STREAMS 1
-#endif
-  static constexpr int kFeStreams = DM_FE_STREAMS;
-  static_assert(kFeStreams == 1 || kFeStreams == 2, "one or two front-end streams");
-  hipStream_t fe_streams[2] = {nullptr, nullptr};
+  // One front-end stream: consecutive calls' front-ends queue behind each
+  // other.  Two alternating streams (so call k+1's front-end could start
+  // before call k's finished) left the full step where it was and slowed
+  // C1 / C5: DESIGN.md §3.3.3, §5.7.
+  hipStream_t fe_stream = nullptr;
   hipEvent_t ev_fe = nullptr;
-  // the end of the last front-end of each set parity (before its signal):
-  // a caller that refills a buffer every front-end reads (the sharded
-  // handle's peer copies of the inputs) orders itself after it
-  hipEvent_t ev_fe_end[2] = {nullptr, nullptr};
   // front-end completion word (k_fe_signal / k_fe_gate, dm_integrate.hip):
   // the sequence number of the last call whose front-end finished
   unsigned long long* fe_flag = nullptr;  // [kSigWord] / [kGateWord] hand-off counts, [kHaltWord] sticky error
@@ -279,7 +269,8 @@ struct dm_grid {
   // what the front-end hands to the accumulation, one set per call parity
   struct IntWs {
     // the front-end's own scratch (k_beam_prep -> k_plan / k_scatter): per
-    // set, so two calls' front-ends may run at once (DM_FE_STREAMS)
+    // set, like everything it hands over: call k+1's front-end overlaps call
+    // k's accumulation
     Beam* beams = nullptr;          // [beams_cap]
     int2* blk_hist = nullptr;       // [beam blocks][1024] k_beam_prep's (tile, pieces | hash slot << 16) histogram
     int32_t* blk_n = nullptr;       // [beam blocks] its entries
@@ -294,11 +285,10 @@ struct dm_grid {
     int32_t* tile_cur = nullptr;      // [NT] k_scatter's bin cursor per active tile (k_plan)
     unsigned long long* cnt = nullptr;  // [CNT_N] the integrate counters (kIntegrateCounters)
     unsigned long long* sh = nullptr;   // [kShards][kShardWords] integrate shards
-    // device copies of host inputs (dm_integrate / _async) of the calls using
-    // this set, reused only when the set is (free_wait)
-    double* pose4 = nullptr;
+    // device copy of the host ranges (dm_integrate / _async) of the calls
+    // using this set, reused only when the set is (free_wait)
     float* ranges = nullptr;
-    int64_t pose_cap = 0, ranges_cap = 0;
+    int64_t ranges_cap = 0;
     // the next front-end using this set waits for free_wait: an event on
     // `stream` after the set's last accumulation, recorded lazily (at the next
     // frontier pass or integrate call) -- ev_free, or the readback-slot event
@@ -322,9 +312,6 @@ struct dm_grid {
   double* h_pose4[kPoseRing] = {nullptr, nullptr};
   hipEvent_t ev_pose[kPoseRing] = {nullptr, nullptr};
   double* h_pose4_dev[kPoseRing] = {nullptr, nullptr};  // their device addresses (mapped)
-#ifndef DM_HOST_POSE
-#define DM_HOST_POSE 1  // 0: poses copied to the device like the ranges (A/B builds)
-#endif
   int64_t h_pose_cap = 0;
   int pose_head = 0;
   int32_t last_S = 0, last_N = 0;
@@ -502,16 +489,7 @@ inline void dm_select_slot(dm_grid* g, int slot) {
   g->m_out = r.m_out;
 }
 
-// The front-end stream of workspace set `set` and its hand-off words
-// (k_seq_signal / k_seq_gate: [kSigWord], [kGateWord] of 16 words per
-// stream; the sticky halt word fe_flag[kHaltWord] is shared).
-inline hipStream_t dm_fe_stream_of(const dm_grid* g, int set) {
-  return g->fe_streams[set % dm_grid::kFeStreams];
-}
-inline unsigned long long* dm_fe_flag_of(const dm_grid* g, int set) {
-  return g->fe_flag + 16 * (set % dm_grid::kFeStreams);
-}
-// the set (and stream) the next integrate call will use
+// the set the next integrate call will use
 inline int dm_next_set(const dm_grid* g) { return (g->iw_cur + 1) % dm_grid::kIntSets; }
 
 // Settle the free events owed by the integrate workspaces (their last

@@ -2,8 +2,9 @@
 CSV): per step k, relative to k_tile_accum(k)'s start, when the next batch's
 front-end kernels (k_beam_prep / k_plan / k_scatter of batch k+1) start and
 end, when k_tile_accum(k+1) starts, and which hardware queue each kernel ran
-on.  Used to check whether a second front-end stream (DM_FE_STREAMS=2) lets
-batch k+1's front-end start before batch k's accumulation, and what holds it.
+on.  Shows whether batch k+1's front-end starts before batch k's accumulation,
+and what holds it.  (Round 6 used it to judge a build with a second front-end
+stream, which was not kept: DESIGN.md §3.3.3.)
 
 Usage: python tools/fe_trace.py TRACE.csv [first_accum] [n_steps]"""
 import csv
