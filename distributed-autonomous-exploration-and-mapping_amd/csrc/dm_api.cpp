@@ -92,6 +92,10 @@ int validate_params(const dm_params* p) {
   if (!isfinite(p->l_occ) || !isfinite(p->l_free) || !isfinite(p->l_min) || !isfinite(p->l_max) ||
       !(p->l_min <= p->l_max))
     return dm_set_error(DM_ERR_INVALID_ARG, "log-odds constants must be finite with l_min <= l_max");
+  // +-inf is legal ("never occupied" / "never free"); a NaN compares false in
+  // state_of but has a sign bit for state_bits (dm_integrate.hip)
+  if (isnan(p->occ_thresh) || isnan(p->free_thresh))
+    return dm_set_error(DM_ERR_INVALID_ARG, "occ_thresh / free_thresh must not be NaN");
   if (p->band_row0 < 0 || p->band_row0 >= p->height || p->band_row0 % DM_TILE != 0)
     return dm_set_error(DM_ERR_INVALID_ARG, "band_row0 must be in [0, height) and a multiple of %d",
                         DM_TILE);

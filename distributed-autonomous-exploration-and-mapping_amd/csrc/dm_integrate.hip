@@ -1512,8 +1512,9 @@ ApplyArgs make_apply(const dm_grid* g) {
   ApplyArgs a;
   a.l_occ = g->p.l_occ;
   a.l_free = g->p.l_free;
-  // signed zeros normalised to +0: the SPEC's compare-based clamp gives the
-  // same result for a bound of -0 or +0 (L is never -0), v_med3 only for +0
+  // signed zeros normalised to +0 (include/dm.h, dm_params): when the clamp
+  // fires its result is the bound itself, so a -0 bound would store -0; the
+  // SPEC reads it as +0, and so do the oracles
   a.l_min = g->p.l_min == 0.0f ? 0.0f : g->p.l_min;
   a.l_max = g->p.l_max == 0.0f ? 0.0f : g->p.l_max;
   // thresholds without signed zeros either (state_bits: sign-bit compares)

@@ -62,7 +62,11 @@ extern "C" {
 /* Map parameters.  Defaults (dm_default_params) come from the reference where
  * it has them: resolution 0.05 (slam_config.yaml:26), max range 12.0
  * (slam_config.yaml:27), LD06 range_min 0.02f (driver rodata 0xbc840).  The
- * log-odds constants are this build's SPEC. */
+ * log-odds constants are this build's SPEC.
+ * Signed zeros: a -0.0 in l_min, l_max, occ_thresh or free_thresh is read as
+ * +0.0, so a cell clamped to a zero bound stores +0.0, never -0.0.
+ * occ_thresh / free_thresh may be +-inf ("never occupied" / "never free") but
+ * not NaN (DM_ERR_INVALID_ARG). */
 typedef struct dm_params {
   int64_t width;            /* cells along x (columns), global */
   int64_t height;           /* cells along y (rows), global */

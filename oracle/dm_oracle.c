@@ -115,6 +115,19 @@ int64_t or_line_cells(int64_t sx, int64_t sy, int64_t ex, int64_t ey, int64_t* o
 }
 
 /* ----------------------------------------------------------- a6 / a7 --- */
+/* A -0.0 in l_min, l_max, occ_thresh or free_thresh is read as +0.0
+ * (include/dm.h, dm_params): a clamp never stores a -0. */
+static float or_plus_zero(float v) { return v == 0.0f ? 0.0f : v; }
+
+static dm_params or_normalised(const dm_params* p) {
+  dm_params q = *p;
+  q.l_min = or_plus_zero(p->l_min);
+  q.l_max = or_plus_zero(p->l_max);
+  q.occ_thresh = or_plus_zero(p->occ_thresh);
+  q.free_thresh = or_plus_zero(p->free_thresh);
+  return q;
+}
+
 static int8_t or_state_of(const dm_params* p, float L) {
   if (L == 0.0f) return -1;
   if (L >= p->occ_thresh) return 100;
@@ -128,10 +141,12 @@ static int64_t band_rows_of(const dm_params* p) {
 
 /* Integrate one call.  L and state are the band arrays [band_rows][width].
  * h/m counts are per call (uint32), applied once, then dropped.  Returns 0. */
-int or_integrate(const dm_params* p, float* L, int8_t* state, int32_t S,
+int or_integrate(const dm_params* params, float* L, int8_t* state, int32_t S,
                  const double* poses, int32_t N, const float* ranges,
                  float angle_min, float angle_increment, uint64_t* out_U,
                  uint64_t* out_T) {
+  const dm_params np = or_normalised(params);
+  const dm_params* p = &np;
   int64_t W = p->width, H = p->height;
   int64_t r0 = p->band_row0, R = band_rows_of(p);
   size_t cells = (size_t)(W * R);
@@ -193,7 +208,9 @@ int or_integrate(const dm_params* p, float* L, int8_t* state, int32_t S,
 }
 
 /* Recompute state from L for every cell (used after loading L). */
-void or_state_from_logodds(const dm_params* p, const float* L, int8_t* state, int64_t cells) {
+void or_state_from_logodds(const dm_params* params, const float* L, int8_t* state, int64_t cells) {
+  const dm_params np = or_normalised(params);
+  const dm_params* p = &np;
   for (int64_t i = 0; i < cells; ++i) state[i] = or_state_of(p, L[i]);
 }
 

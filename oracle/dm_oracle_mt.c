@@ -89,10 +89,19 @@ static int8_t state_of(const dm_params* p, float L) {
   return -1;
 }
 
-int or_mt_integrate(void* h, const dm_params* p, float* L, int8_t* state, int32_t S, const double* poses,
+/* a -0.0 clamp bound or threshold is read as +0.0 (include/dm.h, dm_params) */
+static float plus_zero(float v) { return v == 0.0f ? 0.0f : v; }
+
+int or_mt_integrate(void* h, const dm_params* params, float* L, int8_t* state, int32_t S, const double* poses,
                     int32_t N, const float* ranges, float angle_min, float angle_increment, uint64_t* out_U,
                     uint64_t* out_T) {
   or_mt_ctx* c = (or_mt_ctx*)h;
+  dm_params np = *params;
+  np.l_min = plus_zero(params->l_min);
+  np.l_max = plus_zero(params->l_max);
+  np.occ_thresh = plus_zero(params->occ_thresh);
+  np.free_thresh = plus_zero(params->free_thresh);
+  const dm_params* p = &np;
   const int64_t W = p->width, H = p->height, r0 = p->band_row0, R = band_rows_of(p);
   const size_t nb = (size_t)S * (size_t)N;
   int64_t* ep = (int64_t*)malloc(sizeof(int64_t) * 4 * (nb ? nb : 1));

@@ -72,6 +72,12 @@ def line(sx, sy, ex, ey):
     return cells
 
 
+def _pz(v):
+    """A -0.0 clamp bound or threshold is read as +0.0 (include/dm.h, dm_params)."""
+    v = np.float32(v)
+    return np.float32(0.0) if v == 0 else v
+
+
 def band_rows(p):
     return int(p.band_rows) if p.band_rows > 0 else int(p.height - p.band_row0)
 
@@ -100,7 +106,7 @@ def integrate(p, L, state, poses, ranges, angle_min, angle_increment):
     l = L[touched]
     l = (l + t).astype(f32)
     l = (l + u).astype(f32)
-    l = np.minimum(np.maximum(l, f32(p.l_min)), f32(p.l_max))
+    l = np.minimum(np.maximum(l, _pz(p.l_min)), _pz(p.l_max))
     L[touched] = l
     state[touched] = state_of(p, l)
     return U, int(touched.sum())
@@ -109,8 +115,9 @@ def integrate(p, L, state, poses, ranges, angle_min, angle_increment):
 def state_of(p, L):
     L = np.asarray(L, np.float32)
     s = np.full(L.shape, -1, np.int8)
-    s[L >= np.float32(p.occ_thresh)] = 100
-    s[(L <= np.float32(p.free_thresh)) & ~(L >= np.float32(p.occ_thresh))] = 0
+    occ_t, free_t = _pz(p.occ_thresh), _pz(p.free_thresh)
+    s[L >= occ_t] = 100
+    s[(L <= free_t) & ~(L >= occ_t)] = 0
     s[L == 0] = -1
     return s
 

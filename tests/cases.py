@@ -57,6 +57,95 @@ def random_scans(seed, p, S, N, spread=1.0, nan_frac=0.05, far_frac=0.1):
     return poses, r, 0.0, inc
 
 
+def mixed_scans(seed, p, S, N, colocate=0):
+    """Scans that reach every state: sensors inside the map, ranges short
+    enough that most beams end inside it (hits, so occupied and dead-band
+    cells, not only free ones), 5 % NaN and 7 % beyond range_max.  The first
+    `colocate` scans share scan 0's position (many pieces on one tile)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    wx, wy = p.width * p.resolution, p.height * p.resolution
+    x = p.origin_x + rng.uniform(0.05, 0.95, S) * wx
+    y = p.origin_y + rng.uniform(0.05, 0.95, S) * wy
+    yaw = rng.uniform(-np.pi, np.pi, S)
+    x[:colocate] = x[0]
+    y[:colocate] = y[0]
+    poses = np.stack([x, y, yaw], 1)
+    r = rng.uniform(p.range_min, min(0.45 * min(wx, wy), 1.2 * p.range_max), (S, N))
+    r = (np.round(r * 1000) / 1000).astype(np.float32)
+    u = rng.random((S, N))
+    r[u < 0.05] = np.nan
+    r[u > 0.93] = np.float32(1.5 * p.range_max)
+    inc = float(np.float32(2 * np.pi / max(N - 1, 1)))
+    return poses, r, 0.0, inc
+
+
+# Named overrides of make_params' map constants (tests/test_gpu_params.py,
+# test_oracle.py, test_emulated_kernels.py) and what each one reaches.
+PARAM_SETS = {
+    # touched cells that stay unknown; free -> unknown by one hit
+    "deadband": dict(occ_thresh=0.6, free_thresh=-0.7),
+    # overlapping thresholds: occupied wins
+    "inverted": dict(occ_thresh=-0.3, free_thresh=0.5),
+    # thresholds equal to the clamp bounds (>= / <= at equality)
+    "asym": dict(l_occ=0.3, l_free=-0.85, l_min=-0.85, l_max=0.6, occ_thresh=0.6, free_thresh=-0.85),
+    # clamp to a zero bound given as -0.0: clamped cells become unknown again
+    "upper_zero": dict(l_min=-2.0, l_max=-0.0, occ_thresh=0.0, free_thresh=-0.4),
+    # l_min == l_max: every touched cell keeps L == 0, state -1, no frontier
+    "zero_clamp": dict(l_min=0.0, l_max=0.0),
+    # exact cancellation: 1 hit + 2 misses gives L == 0 on a touched cell
+    "cancel": dict(l_occ=0.5, l_free=-0.25, occ_thresh=0.25, free_thresh=-0.25),
+    # non-default range gates; most beams truncated
+    "short": dict(range_min=0.5, range_max=1.7, l_occ=2.0, l_free=-1.0, l_min=-4.0, l_max=4.0),
+    # infinite threshold: never occupied
+    "never_occ": dict(occ_thresh=float("inf"), free_thresh=-0.5),
+}
+
+
+def set_params(name, width, height, resolution=0.05, **kw) -> DmParams:
+    """make_params with the named set's overrides and a slightly off-grid origin."""
+    origin = (-width * resolution / 2 + 0.0137, -height * resolution / 2 - 0.0071)
+    return make_params(width, height, resolution=resolution, origin=origin, **{**PARAM_SETS[name], **kw})
+
+
+def limit_params(major) -> DmParams:
+    """range_max / resolution == 16384 cells exactly, the longest ray
+    validate_params admits.  "x": a 192-row band in the middle of a 32768^2
+    map (6.3 M cells; steep rays cross it with large k); "y": a 192-column
+    map, 32768 rows."""
+    if major == "x":
+        return make_params(32768, 32768, resolution=2.0 ** -10, range_max=16.0,
+                           band_row0=16320, band_rows=192)
+    return make_params(192, 32768, resolution=2.0 ** -10, range_max=16.0)
+
+
+def limit_scans(p, S=4, N=720):
+    """Scan 0 near the map's centre with beam 0 along the map's long axis
+    (16384 major steps); the others anywhere within +-15.9 m (x inside the
+    map where it is narrow).  A third of the beams hit at exactly range_max,
+    a third at 15.99, a third are +inf (truncated at range_max)."""
+    rng = np.random.Generator(np.random.PCG64(16384))
+    x = rng.uniform(-15.9, 15.9, S)
+    y = rng.uniform(-15.9, 15.9, S)
+    yaw = rng.uniform(-np.pi, np.pi, S)
+    wx = p.width * p.resolution
+    narrow = p.width < p.height
+    if narrow:
+        x = p.origin_x + (x + 15.9) / 31.8 * wx
+    x[0], y[0], yaw[0] = 0.0003, 0.0004, (np.pi / 2 if narrow else 0.0)
+    r = np.empty((S, N), np.float32)
+    r[:, 0::3] = 16.0
+    r[:, 1::3] = 15.99
+    r[:, 2::3] = np.inf
+    return np.stack([x, y, yaw], 1), r, 0.0, float(np.float32(2 * np.pi / (N - 1)))
+
+
+def limit_chunk_scan(p):
+    """One scan of 8 beams at the limit: so few beams are enumerated in many
+    k-chunks (dm_integrate_chunks)."""
+    r = np.array([[16.0, 15.99, np.inf, 16.0, 15.99, np.inf, 16.0, 15.99]], np.float32)
+    return np.array([[0.0003, 0.0004, 0.1]]), r, 0.0, float(np.float32(2 * np.pi / 8))
+
+
 def random_state(seed, R, W, p_free=0.5, p_occ=0.1):
     rng = np.random.Generator(np.random.PCG64(seed))
     u = rng.random((R, W))

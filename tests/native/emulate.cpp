@@ -18,6 +18,10 @@ extern "C" int emu_integrate(int32_t W, int32_t R, int32_t row0, double ox, doub
                              int8_t* state, int32_t S, const double* pose4, int32_t N,
                              const float* ranges, const double* trig, uint64_t* out_U,
                              uint64_t* out_T, uint64_t* out_segs, int32_t chunk_len) {
+  // a -0.0 clamp bound or threshold is read as +0.0 (make_apply, include/dm.h)
+  auto plus_zero = [](float v) { return v == 0.0f ? 0.0f : v; };
+  l_min = plus_zero(l_min); l_max = plus_zero(l_max);
+  occ_t = plus_zero(occ_t); free_t = plus_zero(free_t);
   RayGeom g;
   g.W = W; g.R = R; g.row0 = row0;
   g.TX = (W + DM_TS - 1) / DM_TS;

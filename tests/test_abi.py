@@ -93,6 +93,43 @@ def test_errors_are_codes_not_aborts():
         dm.default_params(10, 10, no_such_field=1)
 
 
+def _create_rc(p):
+    """dm_create's return code; validate_params runs before the first HIP call."""
+    lib = dm.load_library()
+    h = ctypes.c_void_p()
+    rc = lib.dm_create(ctypes.byref(h), ctypes.byref(p), 0)
+    if rc == 0:
+        lib.dm_destroy(h)
+    return rc
+
+
+def test_nan_thresholds_are_rejected_infinite_ones_are_not():
+    """A NaN threshold compares false in the scalar classifier and has a sign
+    bit in the vector one (csrc/dm_integrate.hip, state_of / state_bits): the
+    two would disagree, so it is refused.  +-inf means never / always."""
+    lib = dm.load_library()
+    for field in ("occ_thresh", "free_thresh"):
+        for nan in (float("nan"), -float("nan")):
+            p = dm.default_params(100, 100, **{field: nan})
+            assert _create_rc(p) == _ffi.DM_ERR_INVALID_ARG
+            assert b"NaN" in lib.dm_last_error()
+        for inf in (float("inf"), -float("inf")):
+            p = dm.default_params(100, 100, **{field: inf})
+            assert _create_rc(p) in (0, _ffi.DM_ERR_HIP)  # valid: only a missing GPU may stop it
+
+
+def test_ray_length_limit_is_exact():
+    """range_max / resolution == 16384 is admitted, one ulp of range_max above is not."""
+    import numpy as np
+
+    p = dm.default_params(192, 192, resolution=2.0 ** -10, range_max=16.0)
+    assert _create_rc(p) in (0, _ffi.DM_ERR_HIP)
+    p.range_max = np.nextafter(np.float32(16.0), np.float32(np.inf))
+    assert p.range_max > 16.0
+    assert _create_rc(p) == _ffi.DM_ERR_INVALID_ARG
+    assert b"16384" in dm.load_library().dm_last_error()
+
+
 def test_product_fails_loudly_without_gpu():
     from conftest import gpu_available
 

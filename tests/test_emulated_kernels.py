@@ -81,3 +81,50 @@ def test_emulated_kernels_random(emu, oracle_lib, W, H, S, N, res, seed, r0, row
         assert m.integrate(poses, ranges, amin, inc) == om.integrate(poses, ranges, amin, inc)
     np.testing.assert_array_equal(m.L.view(np.uint32), om.L.view(np.uint32))
     np.testing.assert_array_equal(m.state, om.state)
+
+
+@pytest.mark.parametrize("name", ["deadband", "cancel"])
+@pytest.mark.parametrize("W,H,S,N,res,colocate", [(130, 70, 4, 90, 0.05, 0), (256, 192, 6, 180, 0.05, 0),
+                                                  (320, 256, 5, 720, 0.02, 3)])
+@pytest.mark.parametrize("chunk_len", [0, 97])
+def test_emulated_kernels_param_sets(emu, oracle_lib, name, W, H, S, N, res, colocate, chunk_len):
+    """Non-default thresholds (cases.PARAM_SETS: a dead band, exact
+    cancellation to L == 0) on cases.mixed_scans, which reach every state."""
+    p = cases.set_params(name, W, H, res)
+    om = oracle_lib.OracleMap(p)
+    # the same geometry with make_params' log-odds constants: L != 0 marks the touched cells
+    tm = oracle_lib.OracleMap(cases.make_params(W, H, resolution=res, origin=(p.origin_x, p.origin_y)))
+    m = EmuMap(emu, p, chunk_len)
+    for k in range(5):
+        poses, ranges, amin, inc = cases.mixed_scans(70 + k % 3, p, S, N, colocate)
+        tm.integrate(poses, ranges, amin, inc)
+        assert m.integrate(poses, ranges, amin, inc) == om.integrate(poses, ranges, amin, inc)
+    np.testing.assert_array_equal(m.L.view(np.uint32), om.L.view(np.uint32))
+    np.testing.assert_array_equal(m.state, om.state)
+    # the cells the set is about exist (counted on the oracle's arrays)
+    touched = tm.L != 0
+    if name == "deadband":
+        assert (touched & (om.state == -1)).sum() >= 1000
+    else:
+        assert (touched & (om.L == 0)).sum() >= 100
+
+
+@pytest.mark.parametrize("major", ["x", "y"])
+@pytest.mark.parametrize("chunk_len", [0, 97])
+def test_emulated_kernels_ray_length_limit(emu, oracle_lib, major, chunk_len):
+    """Rays of exactly 16384 cells (range_max / resolution at validate_params'
+    bound): dm_pack_piece's 16-bit fields (two_n up to 32774), the < 2^31
+    products of dm_for_each_piece and dm_udiv_small's num < 2^22."""
+    p = cases.limit_params(major)
+    om = oracle_lib.OracleMap(p)
+    m = EmuMap(emu, p, chunk_len)
+    poses, ranges, amin, inc = cases.limit_scans(p)
+    cells, flags = oracle_lib.endpoints(p, poses, ranges, amin, inc)
+    n = np.maximum(np.abs(cells[:, 2] - cells[:, 0]), np.abs(cells[:, 3] - cells[:, 1]))
+    assert n[(flags & 1) != 0].max() == 16384
+    for args in ((poses, ranges, amin, inc), cases.limit_chunk_scan(p)):
+        exp = om.integrate(*args)
+        assert exp[1] > 1000
+        assert m.integrate(*args) == exp
+    np.testing.assert_array_equal(m.L.view(np.uint32), om.L.view(np.uint32))
+    np.testing.assert_array_equal(m.state, om.state)

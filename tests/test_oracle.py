@@ -39,19 +39,31 @@ def test_endpoints_match_numpy(oracle_lib):
         assert bool(flags[b] & 2) == hit
 
 
-@pytest.mark.parametrize("seed,W,H,S,N", [(2, 64, 64, 3, 90), (3, 100, 70, 5, 120), (4, 130, 150, 2, 360)])
-def test_integrate_matches_numpy(oracle_lib, seed, W, H, S, N):
-    p = cases.make_params(W, H)
+@pytest.mark.parametrize("seed,W,H,S,N,pset", [
+    pytest.param(2, 64, 64, 3, 90, None, id="2-64-64-3-90"),
+    pytest.param(3, 100, 70, 5, 120, None, id="3-100-70-5-120"),
+    pytest.param(4, 130, 150, 2, 360, None, id="4-130-150-2-360"),
+] + [pytest.param(70, 130, 70, 4, 90, name, id=name) for name in cases.PARAM_SETS])
+def test_integrate_matches_numpy(oracle_lib, seed, W, H, S, N, pset):
+    """pset: a named set of cases.PARAM_SETS on cases.mixed_scans, five
+    batches of which two repeat (cells cross thresholds both ways);
+    upper_zero gives l_max as -0.0, which both oracles read as +0.0."""
+    p = cases.make_params(W, H) if pset is None else cases.set_params(pset, W, H)
     m = oracle_lib.OracleMap(p)
     L = np.zeros((H, W), np.float32)
     st = np.full((H, W), -1, np.int8)
-    for k in range(3):
-        poses, ranges, amin, inc = cases.random_scans(seed * 10 + k, p, S, N)
+    for k in range(3 if pset is None else 5):
+        if pset is None:
+            poses, ranges, amin, inc = cases.random_scans(seed * 10 + k, p, S, N)
+        else:
+            poses, ranges, amin, inc = cases.mixed_scans(seed + k % 3, p, S, N)
         U1, T1 = m.integrate(poses, ranges, amin, inc)
         U2, T2 = np_oracle.integrate(p, L, st, poses, ranges, amin, inc)
         assert (U1, T1) == (U2, T2)
         np.testing.assert_array_equal(m.L.view(np.uint32), L.view(np.uint32))
         np.testing.assert_array_equal(m.state, st)
+    assert not (L.view(np.uint32) == 0x80000000).any()  # a clamp never stores -0.0
+    np.testing.assert_array_equal(np_oracle.state_of(p, L), st)
 
 
 def test_integrate_band_matches_full(oracle_lib):
@@ -143,22 +155,34 @@ def test_oracle_golden_fixtures(oracle_lib):
 @pytest.mark.parametrize("seed,W,H,S,N,threads", [(31, 300, 260, 8, 720, 4), (32, 1000, 700, 16, 2048, 8),
                                                   (33, 130, 70, 5, 500, 3)])
 def test_openmp_restatement_equals_single_thread(oracle_lib, seed, W, H, S, N, threads):
+    _openmp_vs_single(oracle_lib, cases.make_params(W, H, min_frontier_size=1 + seed % 3), seed, S, N, threads,
+                      cases.random_scans)
+
+
+@pytest.mark.parametrize("name", ["deadband", "upper_zero"])
+def test_openmp_restatement_param_sets(oracle_lib, name):
+    """The same at non-default thresholds / a -0.0 clamp bound, on scans that reach every state."""
+    _openmp_vs_single(oracle_lib, cases.set_params(name, 256, 192), 70, 6, 180, 4, cases.mixed_scans)
+
+
+def _openmp_vs_single(oracle_lib, p, seed, S, N, threads, scans):
     """dm_oracle_mt.c (bench.py's strong-CPU line) gives dm_oracle.c's
     results bit for bit: U / T, L, state, mask, labels, clusters; also on a
     band with halo rows and with a size filter."""
-    p = cases.make_params(W, H, min_frontier_size=1 + seed % 3)
+    W, H = int(p.width), int(p.height)
     one = oracle_lib.OracleMap(p)
     mt = oracle_lib.OracleMapMT(p, threads=threads)
     assert mt.threads == threads
     for k in range(3):
-        poses, ranges, amin, inc = cases.random_scans(seed * 10 + k, p, S, N)
+        poses, ranges, amin, inc = scans(seed * 10 + k, p, S, N)
         assert mt.integrate(poses, ranges, amin, inc) == one.integrate(poses, ranges, amin, inc)
     np.testing.assert_array_equal(mt.L.view(np.uint32), one.L.view(np.uint32))
     np.testing.assert_array_equal(mt.state, one.state)
     for a, b in zip(mt.frontiers(), one.frontiers()):
         np.testing.assert_array_equal(a, b)
     # a band of the same map with halo rows
-    bp = cases.make_params(W, H, band_row0=64, band_rows=min(128, H - 64))
+    bp = cases.make_params(W, H, resolution=p.resolution, origin=(p.origin_x, p.origin_y), band_row0=64,
+                           band_rows=min(128, H - 64))
     ob, mb = oracle_lib.OracleMap(bp), oracle_lib.OracleMapMT(bp, threads=threads)
     st = one.state
     ob.state[...] = st[64:64 + ob.state.shape[0]]
