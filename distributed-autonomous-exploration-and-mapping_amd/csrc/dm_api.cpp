@@ -511,7 +511,7 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   if ((rc = dev_alloc(&g->fmask, g->NT * DM_TILE * 16, "tile free / unknown bit rows"))) return fail(rc);
   if ((rc = dev_alloc(&g->fedge, g->NT * 4, "tile unknown edge words"))) return fail(rc);
   if ((rc = dev_alloc(&g->tile_seen, g->NT, "tile seen flags"))) return fail(rc);
-  // The five run-time switches (read once, here): DM_SPARSE_PIECES (0: no
+  // The run-time switches (read once, here): DM_SPARSE_PIECES (0: no
   // sparse work items), DM_FMASK=on|off (fmask maintenance forced either way),
   // DM_FRONTIER_KERNEL=wave|wg (one frontier tile kernel for every pass),
   // DM_SORT_MIN (cluster count above which the row sort runs) and
@@ -525,6 +525,9 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   g->frontier_kernel = fk && !strcmp(fk, "wave") ? 1 : (fk && !strcmp(fk, "wg") ? 2 : 0);
   if (const char* sm = getenv("DM_SORT_MIN")) g->sort_min = std::max<int64_t>(0, atoll(sm));
   g->fault_gate = dm_env_on("DM_FAULT_GATE");
+  // and DM_PLAN_MAX_ROUNDS: the distance field's round bound (dm_plan_field's
+  // DM_ERR_INCOMPLETE path; a complete field is the same under any bound)
+  if (const char* pr = getenv("DM_PLAN_MAX_ROUNDS")) g->plan_max_rounds = std::max<int64_t>(0, atoll(pr));
   for (auto& f : g->fw) {
     e = hipEventCreateWithFlags(&f.ev_split, hipEventDisableTiming | hipEventDisableSystemFence);
     if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
@@ -647,6 +650,11 @@ int dm_destroy(dm_grid* g) {
   for (int i = 0; i < 2; ++i) { dev_free(g->flist[i]); dev_free(g->flist_n[i]); }
   for (int b = 0; b < 2; ++b) { dev_free(g->goal_k[b]); dev_free(g->goal_i[b]); }
   dev_free(g->goal_io); dev_free(g->goal_idx);
+  dev_free(g->plan_cost); dev_free(g->plan_trav); dev_free(g->plan_travs); dev_free(g->plan_list[0]);
+  dev_free(g->plan_list[1]); dev_free(g->plan_stamp); dev_free(g->plan_len); dev_free(g->plan_stat);
+  dev_free(g->plan_src); dev_free(g->plan_qxy); dev_free(g->plan_qcost); dev_free(g->plan_qcell);
+  dev_free(g->plan_path);
+  if (g->h_plan) (void)hipHostFree(g->h_plan);
   for (auto& w : g->iw) {
     dev_free(w.pieces); dev_free(w.hitems); dev_free(w.litems); dev_free(w.heavy_list); dev_free(w.slabs);
     dev_free(w.heavy_done); dev_free(w.tile_count); dev_free(w.tile_cur); dev_free(w.cnt); dev_free(w.sh);
@@ -691,6 +699,7 @@ int dm_reset(dm_grid* g) {
   for (auto& f : g->fw) DM_HIP(hipMemsetAsync(f.cnt, 0, sizeof(unsigned long long) * CNT_N, g->stream));
   DM_HIP(hipMemsetAsync(g->fe_flag + kHaltWord, 0, sizeof(unsigned long long), g->stream));  // sticky error
   DM_HIP(hipStreamSynchronize(g->stream));
+  ++g->reset_seq;  // the map changed: a distance field of the old one is stale
   return DM_OK;
 }
 
@@ -1299,6 +1308,286 @@ int dm_assign_goals(dm_grid* g, const double* robots_xy, int32_t n_robots, int64
   DM_HIP(hipMemcpyAsync(out_xy, g->goal_io + 2 * 256, sizeof(double) * 2 * (size_t)R, hipMemcpyDeviceToHost,
                         g->stream));
   DM_HIP(hipStreamSynchronize(g->stream));
+  memcpy(out_index, idx.data(), sizeof(int64_t) * (size_t)R);
+  return DM_OK;
+}
+
+// ---- path planning (csrc/dm_plan.h): traversability, distance field, snapped
+// queries, paths, path-length goals ---------------------------------------------
+
+// The planner needs the whole map in one handle.
+static int plan_check_handle(const dm_grid* g, const char* what) {
+  if (g && g->sh)
+    return dm_set_error(DM_ERR_INVALID_ARG, "%s needs one handle that covers the whole map: it is not available "
+                        "on a sharded handle (dm_create_sharded)", what);
+  int rc = check_grid(g);
+  if (rc) return rc;
+  if (g->R != g->H)
+    return dm_set_error(DM_ERR_INVALID_ARG, "%s needs a handle that covers the whole map; this one is the band "
+                        "of rows [%lld, %lld) of %lld", what, (long long)g->row0, (long long)(g->row0 + g->R),
+                        (long long)g->H);
+  return DM_OK;
+}
+
+static int ensure_plan(dm_grid* g) {
+  if (g->plan_cost) return DM_OK;  // allocated last: everything else is there too
+  int rc = DM_OK;
+  if (!g->h_plan) {
+    hipError_t e = hipHostMalloc((void**)&g->h_plan, sizeof(unsigned long long) * 16,
+                                 hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess) {
+      g->h_plan = nullptr;
+      return dm_hip_check(e, "hipHostMalloc(plan rounds)");
+    }
+    memset(g->h_plan, 0, sizeof(unsigned long long) * 16);
+    DM_HIP(hipHostGetDevicePointer((void**)&g->h_plan_dev, g->h_plan, 0));
+  }
+  const int64_t rows = g->NT * DM_TILE;
+  if ((rc = dev_alloc(&g->plan_trav, rows, "traversable bit rows"))) return rc;
+  if ((rc = dev_alloc(&g->plan_travs, rows, "traversable bit rows with sources"))) return rc;
+  if ((rc = dev_alloc(&g->plan_list[0], g->NT, "plan tile list"))) return rc;
+  if ((rc = dev_alloc(&g->plan_list[1], g->NT, "plan tile list"))) return rc;
+  if ((rc = dev_alloc(&g->plan_stamp, g->NT, "plan tile stamps"))) return rc;
+  if ((rc = dev_alloc(&g->plan_len, 4, "plan list lengths"))) return rc;
+  if ((rc = dev_alloc(&g->plan_stat, 8, "plan statistics"))) return rc;
+  DM_HIP(hipMemset(g->plan_stat, 0, sizeof(unsigned long long) * 8));
+  if ((rc = dev_alloc(&g->plan_src, 256, "plan sources"))) return rc;
+  return dev_alloc(&g->plan_cost, g->W * g->H, "distance field");
+}
+
+static int grow_plan_query(dm_grid* g, int64_t n) {
+  if (n <= g->plan_qcap) return DM_OK;
+  g->plan_qcap = 0;
+  int rc = dev_alloc(&g->plan_qxy, 2 * n, "plan query targets");
+  if (!rc) rc = dev_alloc(&g->plan_qcost, n, "plan query costs");
+  if (!rc) rc = dev_alloc(&g->plan_qcell, n, "plan query cells");
+  if (!rc) g->plan_qcap = n;
+  return rc;
+}
+
+// SPEC a4's cell of a point: floor((x - origin) / resolution) per axis
+static bool plan_cell_of(const dm_grid* g, double x, double y, int64_t* cell) {
+  const double fx = floor((x - g->p.origin_x) / g->p.resolution);
+  const double fy = floor((y - g->p.origin_y) / g->p.resolution);
+  if (!(fx >= 0.0 && fx < (double)g->W && fy >= 0.0 && fy < (double)g->H)) return false;  // NaN too
+  *cell = (int64_t)fy * g->W + (int64_t)fx;
+  return true;
+}
+
+static uint64_t plan_map_version(const dm_grid* g) { return g->integrate_seq + g->reset_seq; }
+
+static int plan_need_field(const dm_grid* g, const char* what) {
+  if (!g->plan_cost || !g->plan_valid)
+    return dm_set_error(DM_ERR_STATE, "%s: no distance field (call dm_plan_field first)", what);
+  if (g->plan_version != plan_map_version(g))
+    return dm_set_error(DM_ERR_STATE, "%s: the map changed since the distance field was computed (call "
+                        "dm_plan_field again)", what);
+  return DM_OK;
+}
+
+// The field from n sources (metres) over g->plan_trav, which the caller computed.
+static int plan_field_from(dm_grid* g, const double* sources_xy, int32_t n, uint32_t max_cost, uint64_t* stats) {
+  std::vector<int64_t> cells((size_t)n);
+  std::vector<int32_t> tiles;
+  for (int32_t i = 0; i < n; ++i) {
+    if (!plan_cell_of(g, sources_xy[2 * i], sources_xy[2 * i + 1], &cells[(size_t)i]))
+      return dm_set_error(DM_ERR_INVALID_ARG, "source %d (%g, %g) is outside the grid", i, sources_xy[2 * i],
+                          sources_xy[2 * i + 1]);
+    const int64_t x = cells[(size_t)i] % g->W, y = cells[(size_t)i] / g->W;
+    const int32_t t = (int32_t)((y / DM_TILE) * g->TX + x / DM_TILE);
+    if (std::find(tiles.begin(), tiles.end(), t) == tiles.end()) tiles.push_back(t);
+  }
+  if (max_cost == 0u || max_cost > 0xFFFFFFEFu) max_cost = 0xFFFFFFEFu;
+  g->plan_valid = false;
+  int rc = dm_plan_run_field(g, cells.data(), n, tiles.data(), (int32_t)tiles.size(), max_cost, stats);
+  if (rc) return rc;
+  g->plan_valid = true;
+  g->plan_version = plan_map_version(g);
+  return DM_OK;
+}
+
+static int plan_check_inflate(int32_t inflate_cells) {
+  if (inflate_cells < 0 || inflate_cells > 32)
+    return dm_set_error(DM_ERR_INVALID_ARG, "inflate_cells must be in [0, 32] (got %d)", inflate_cells);
+  return DM_OK;
+}
+
+static int plan_check_snap(int32_t snap_cells) {
+  if (snap_cells < 0 || snap_cells > 16)
+    return dm_set_error(DM_ERR_INVALID_ARG, "snap_cells must be in [0, 16] (got %d)", snap_cells);
+  return DM_OK;
+}
+
+int dm_plan_traversable(dm_grid* g, int32_t inflate_cells, uint8_t* out) {
+  int rc = plan_check_handle(g, "dm_plan_traversable");
+  if (rc || (rc = use_device(g))) return rc;
+  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
+  if ((rc = plan_check_inflate(inflate_cells)) || (rc = ensure_plan(g))) return rc;
+  DM_HIP(dm_join_pass_stream(g));
+  const int64_t cells = g->W * g->H;
+  uint8_t* d = nullptr;
+  if ((rc = dev_alloc(&d, cells, "traversable image"))) return rc;
+  rc = dm_plan_launch_travers(g, inflate_cells);
+  if (!rc) rc = dm_plan_launch_expand(g, d);
+  hipError_t e = hipSuccess;
+  if (!rc) e = hipMemcpyAsync(out, d, (size_t)cells, hipMemcpyDeviceToHost, g->stream);
+  if (!rc && e == hipSuccess) e = hipStreamSynchronize(g->stream);
+  (void)hipFree(d);
+  if (e != hipSuccess) return dm_hip_check(e, "dm_plan_traversable");
+  return rc;
+}
+
+int dm_plan_field(dm_grid* g, const double* sources_xy, int32_t n_sources, int32_t inflate_cells,
+                  uint32_t max_cost, uint64_t* out_stats) {
+  int rc = plan_check_handle(g, "dm_plan_field");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n_sources < 1 || n_sources > 256)
+    return dm_set_error(DM_ERR_INVALID_ARG, "n_sources must be in [1, 256] (got %d)", n_sources);
+  if (!sources_xy) return dm_set_error(DM_ERR_INVALID_ARG, "sources_xy is NULL");
+  if ((rc = plan_check_inflate(inflate_cells)) || (rc = ensure_plan(g))) return rc;
+  DM_HIP(dm_join_pass_stream(g));
+  if ((rc = dm_plan_launch_travers(g, inflate_cells))) return rc;
+  return plan_field_from(g, sources_xy, n_sources, max_cost, out_stats);
+}
+
+int dm_plan_get_field(dm_grid* g, uint32_t* out) {
+  int rc = plan_check_handle(g, "dm_plan_get_field");
+  if (rc || (rc = use_device(g))) return rc;
+  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
+  if ((rc = plan_need_field(g, "dm_plan_get_field"))) return rc;
+  DM_HIP(hipMemcpyAsync(out, g->plan_cost, sizeof(uint32_t) * (size_t)(g->W * g->H), hipMemcpyDeviceToHost,
+                        g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  return DM_OK;
+}
+
+int dm_plan_query(dm_grid* g, const double* targets_xy, int64_t n, int32_t snap_cells, uint32_t* out_cost,
+                  int64_t* out_cell) {
+  int rc = plan_check_handle(g, "dm_plan_query");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n < 0) return dm_set_error(DM_ERR_INVALID_ARG, "n must be >= 0");
+  if (n > 0 && (!targets_xy || !out_cost || !out_cell))
+    return dm_set_error(DM_ERR_INVALID_ARG, "targets_xy / out_cost / out_cell is NULL");
+  if ((rc = plan_check_snap(snap_cells)) || (rc = plan_need_field(g, "dm_plan_query"))) return rc;
+  if (n == 0) return DM_OK;
+  if ((rc = grow_plan_query(g, n))) return rc;
+  DM_HIP(hipMemcpyAsync(g->plan_qxy, targets_xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, g->stream));
+  if ((rc = dm_plan_launch_query(g, g->plan_qxy, 2, n, snap_cells, g->plan_qcost, g->plan_qcell))) return rc;
+  DM_HIP(hipMemcpyAsync(out_cost, g->plan_qcost, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipMemcpyAsync(out_cell, g->plan_qcell, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  return DM_OK;
+}
+
+int dm_plan_path(dm_grid* g, double tx, double ty, int32_t snap_cells, int64_t* out_cells, int64_t cap,
+                 int64_t* n_out) {
+  int rc = plan_check_handle(g, "dm_plan_path");
+  if (rc || (rc = use_device(g))) return rc;
+  if (!n_out) return dm_set_error(DM_ERR_INVALID_ARG, "n_out is NULL");
+  *n_out = 0;
+  if (cap < 0 || (cap > 0 && !out_cells)) return dm_set_error(DM_ERR_INVALID_ARG, "cap < 0 or out_cells is NULL");
+  if ((rc = plan_check_snap(snap_cells)) || (rc = plan_need_field(g, "dm_plan_path"))) return rc;
+  if ((rc = grow_plan_query(g, 1))) return rc;
+  // a path visits no cell twice: H * W entries hold any
+  const int64_t dcap = std::max<int64_t>(1, std::min<int64_t>(cap, g->W * g->H));
+  if (dcap > g->plan_pathcap) {
+    g->plan_pathcap = 0;
+    if ((rc = dev_alloc(&g->plan_path, dcap, "path cells"))) return rc;
+    g->plan_pathcap = dcap;
+  }
+  const double txy[2] = {tx, ty};
+  DM_HIP(hipMemcpyAsync(g->plan_qxy, txy, sizeof txy, hipMemcpyHostToDevice, g->stream));
+  if ((rc = dm_plan_launch_query(g, g->plan_qxy, 2, 1, snap_cells, g->plan_qcost, g->plan_qcell))) return rc;
+  if ((rc = dm_plan_launch_path(g, g->plan_qcell, std::min(cap, dcap)))) return rc;
+  unsigned long long st[2] = {0ull, 0ull};
+  DM_HIP(hipMemcpyAsync(st, g->plan_stat + 4, sizeof st, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  if (st[1])
+    return dm_set_error(DM_ERR_INCOMPLETE, "dm_plan_path: the walk found no predecessor after %llu cells (the "
+                        "field is not a fixpoint)", st[0]);
+  const int64_t n = (int64_t)st[0];
+  *n_out = n;
+  if (n > cap)
+    return dm_set_error(DM_ERR_CAPACITY, "the path has %lld cells, cap is %lld", (long long)n, (long long)cap);
+  if (n > 0) {
+    std::vector<int64_t> rev((size_t)n);
+    DM_HIP(hipMemcpy(rev.data(), g->plan_path, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) out_cells[i] = rev[(size_t)(n - 1 - i)];  // source first
+  }
+  return DM_OK;
+}
+
+int dm_assign_goals_path(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size,
+                         double distance_weight, double min_distance, int32_t inflate_cells, uint32_t max_cost,
+                         int32_t snap_cells, int64_t* out_index, double* out_xy, int64_t* out_cell) {
+  int rc = plan_check_handle(g, "dm_assign_goals_path");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n_robots < 0 || n_robots > 256)
+    return dm_set_error(DM_ERR_INVALID_ARG, "n_robots must be in [0, 256] (got %d)", n_robots);
+  if (n_robots > 0 && (!robots_xy || !out_index || !out_xy || !out_cell))
+    return dm_set_error(DM_ERR_INVALID_ARG, "robots_xy / out_index / out_xy / out_cell is NULL");
+  if (!isfinite(distance_weight) || !isfinite(min_distance))
+    return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight / min_distance must be finite");
+  if (distance_weight < 0.0)  // as dm_assign_goals: the device ranks by the util's IEEE bits
+    return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight must be >= 0");
+  if ((rc = plan_check_inflate(inflate_cells)) || (rc = plan_check_snap(snap_cells))) return rc;
+  const int s = g->goal_slot;
+  if (s < 0 || g->goal_gen != g->rb_gen ||
+      (g->goal_kind == 1 ? g->rb[s].wepoch : g->rb[s].mepoch) != g->goal_epoch)
+    return dm_set_error(DM_ERR_INVALID_ARG, "no collected frontier result on the device (call dm_frontiers, "
+                                            "dm_frontiers_end or dm_merge_bands first; a later pass may have "
+                                            "reused its readback slot)");
+  if (n_robots == 0) return DM_OK;
+  for (int32_t r = 0; r < n_robots; ++r) {
+    int64_t c;
+    if (!plan_cell_of(g, robots_xy[2 * r], robots_xy[2 * r + 1], &c))
+      return dm_set_error(DM_ERR_INVALID_ARG, "robot %d (%g, %g) is outside the grid", r, robots_xy[2 * r],
+                          robots_xy[2 * r + 1]);
+  }
+  const dm_cluster* recs = g->goal_kind == 1 ? g->rb[s].out_clu : g->rb[s].m_out;
+  const int64_t K = g->goal_n;
+  if ((rc = ensure_plan(g)) || (rc = grow_plan_query(g, std::max<int64_t>(K, 1)))) return rc;
+  DM_HIP(dm_join_pass_stream(g));
+  if ((rc = dm_plan_launch_travers(g, inflate_cells))) return rc;
+  const int32_t R = n_robots, T = n_robots;
+  std::vector<int64_t> idx((size_t)R, -1);
+  std::vector<unsigned long long> hk((size_t)T);
+  std::vector<uint32_t> hi((size_t)T);
+  for (int32_t r = 0; r < R; ++r) {
+    // robot r's field, then its path cost to every cluster's snapped centroid
+    if ((rc = plan_field_from(g, robots_xy + 2 * r, 1, max_cost, nullptr))) return rc;
+    out_cell[r] = -1;
+    out_xy[2 * r] = out_xy[2 * r + 1] = NAN;
+    if (K == 0) continue;
+    if ((rc = dm_plan_launch_query(g, &recs[0].cx_m, (int64_t)(sizeof(dm_cluster) / sizeof(double)), K, snap_cells,
+                                   g->plan_qcost, g->plan_qcell)))
+      return rc;
+    const unsigned long long* dk = nullptr;
+    const uint32_t* di = nullptr;
+    if ((rc = dm_launch_goal_topk(g, recs, K, nullptr, 1, T, min_size, distance_weight, min_distance, &dk, &di,
+                                  g->plan_qcost)))
+      return rc;
+    DM_HIP(hipMemcpyAsync(hk.data(), dk, sizeof(unsigned long long) * (size_t)T, hipMemcpyDeviceToHost, g->stream));
+    DM_HIP(hipMemcpyAsync(hi.data(), di, sizeof(uint32_t) * (size_t)T, hipMemcpyDeviceToHost, g->stream));
+    DM_HIP(hipStreamSynchronize(g->stream));
+    // greedy in robot order, as dm_assign_goals: the robot's choice is within
+    // the first r + 1 entries of its best-first list
+    for (int32_t t = 0; t < T; ++t) {
+      if (hk[(size_t)t] == 0ull) break;
+      const int64_t c = hi[(size_t)t];
+      if (std::find(idx.begin(), idx.begin() + r, c) != idx.begin() + r) continue;
+      idx[(size_t)r] = c;
+      break;
+    }
+    if (idx[(size_t)r] >= 0) {
+      int64_t cell = -1;
+      DM_HIP(hipMemcpy(&cell, g->plan_qcell + idx[(size_t)r], sizeof cell, hipMemcpyDeviceToHost));
+      out_cell[r] = cell;
+      // the centre of the snapped cell: a reachable goal, not the centroid
+      out_xy[2 * r] = g->p.origin_x + ((double)(cell % g->W) + 0.5) * g->p.resolution;
+      out_xy[2 * r + 1] = g->p.origin_y + ((double)(cell / g->W) + 0.5) * g->p.resolution;
+    }
+  }
   memcpy(out_index, idx.data(), sizeof(int64_t) * (size_t)R);
   return DM_OK;
 }

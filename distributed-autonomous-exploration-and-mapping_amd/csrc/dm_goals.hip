@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "dm_internal.h"
+#include "dm_plan.h"
 
 namespace {
 
@@ -53,23 +54,37 @@ __device__ inline void goal_sort(unsigned long long* s_k, uint32_t* s_i) {
 }
 
 // Workgroup (chunk, robot): the chunk's best T records for the robot.
+// kPath (dm_assign_goals_path): the distance is the path length to the
+// cluster's snapped centroid, cost_rows[r][c] * res / 5 (two rounded
+// operations), and a cluster that is not reached is not eligible; `robots`
+// is not read.
+template <bool kPath>
 __global__ __launch_bounds__(kGoalThreads) void k_goal_topk(const dm_cluster* __restrict__ recs, int64_t K,
                                                             const double* __restrict__ robots, int32_t T,
                                                             int64_t min_size, double w, double min_dist,
                                                             unsigned long long* __restrict__ out_k,
-                                                            uint32_t* __restrict__ out_i) {
+                                                            uint32_t* __restrict__ out_i,
+                                                            const uint32_t* __restrict__ cost_rows, double res) {
   __shared__ unsigned long long s_k[kGoalN];
   __shared__ uint32_t s_i[kGoalN];
   const int64_t chunk = blockIdx.x, r = blockIdx.y, nch = gridDim.x;
-  const double rx = robots[2 * r], ry = robots[2 * r + 1];
+  const double rx = kPath ? 0.0 : robots[2 * r], ry = kPath ? 0.0 : robots[2 * r + 1];
   for (int e = threadIdx.x; e < kGoalN; e += kGoalThreads) {
     const int64_t c = chunk * kGoalN + e;
     unsigned long long key = 0ull;
     if (c < K) {
       const dm_cluster q = recs[c];
-      const double dx = q.cx_m - rx, dy = q.cy_m - ry;
-      const double dist = __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
-      if (q.size >= min_size && dist >= min_dist) {
+      double dist;
+      bool reached = true;
+      if (kPath) {
+        const uint32_t pc = cost_rows[r * K + c];
+        reached = pc != DM_PLAN_UNREACHABLE;
+        dist = __ddiv_rn(__dmul_rn((double)pc, res), 5.0);
+      } else {
+        const double dx = q.cx_m - rx, dy = q.cy_m - ry;
+        dist = __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
+      }
+      if (reached && q.size >= min_size && dist >= min_dist) {
         const double util = __ddiv_rn((double)q.size, __dadd_rn(1.0, __dmul_rn(w, dist)));
         key = (unsigned long long)__double_as_longlong(util);
       }
@@ -133,9 +148,11 @@ int dm_launch_goal_gather(dm_grid* g, const dm_cluster* d_recs, const int64_t* d
 
 // Top-T lists of R robots over K label-sorted records; on return *d_k / *d_i
 // point at the final [R][T] lists (in g->goal_* workspace).  T <= 256.
+// d_cost: [R][K] path costs in place of the Euclidean distance (d_robots is
+// then not read), or nullptr.
 int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, const double* d_robots, int32_t R,
                         int32_t T, int64_t min_size, double w, double min_dist,
-                        const unsigned long long** d_k, const uint32_t** d_i) {
+                        const unsigned long long** d_k, const uint32_t** d_i, const uint32_t* d_cost) {
   const int64_t nch = (K + kGoalN - 1) / kGoalN;
   const int64_t need = (int64_t)R * std::max<int64_t>(nch, 1) * T;
   if (need > g->goal_cap) {
@@ -155,8 +172,13 @@ int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, const d
   int cur = 0;
   KernelTimer t;
   dm_timer_begin(g, "goal_topk", &t);
-  hipLaunchKernelGGL(k_goal_topk, dim3((unsigned)std::max<int64_t>(nch, 1), (unsigned)R), dim3(kGoalThreads), 0,
-                     g->stream, d_recs, K, d_robots, T, min_size, w, min_dist, g->goal_k[0], g->goal_i[0]);
+  const dim3 tgrid((unsigned)std::max<int64_t>(nch, 1), (unsigned)R);
+  if (d_cost)
+    hipLaunchKernelGGL(k_goal_topk<true>, tgrid, dim3(kGoalThreads), 0, g->stream, d_recs, K, d_robots, T, min_size,
+                       w, min_dist, g->goal_k[0], g->goal_i[0], d_cost, g->p.resolution);
+  else
+    hipLaunchKernelGGL(k_goal_topk<false>, tgrid, dim3(kGoalThreads), 0, g->stream, d_recs, K, d_robots, T,
+                       min_size, w, min_dist, g->goal_k[0], g->goal_i[0], (const uint32_t*)nullptr, 0.0);
   DM_HIP(hipGetLastError());
   int64_t nl = std::max<int64_t>(nch, 1);
   const int32_t per = kGoalN / T;  // lists one merge workgroup takes (>= 16)
@@ -171,5 +193,127 @@ int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, const d
   dm_timer_end(g, &t);
   *d_k = g->goal_k[cur];
   *d_i = g->goal_i[cur];
+  return DM_OK;
+}
+
+// ---- path planning (dm_plan.h) ----------------------------------------------
+
+int dm_plan_launch_travers(dm_grid* g, int32_t inflate_cells) {
+  DM_HIP(hipMemsetAsync(g->plan_stat + dm_plan::ST_TRAV, 0, sizeof(unsigned long long), g->stream));
+  KernelTimer t;
+  dm_timer_begin(g, "plan_travers", &t);
+  hipLaunchKernelGGL(dm_plan::k_plan_travers, dim3((unsigned)g->NT), dim3(dm_plan::kThreads), 0, g->stream,
+                     g->state, g->tile_seen, g->W, g->H, g->TX, inflate_cells, g->plan_trav, g->plan_stat);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  return DM_OK;
+}
+
+int dm_plan_launch_expand(dm_grid* g, uint8_t* d_out) {
+  const int64_t cells = g->W * g->H;
+  hipLaunchKernelGGL(dm_plan::k_plan_expand, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, g->stream,
+                     g->plan_trav, g->W, g->H, g->TX, d_out);
+  DM_HIP(hipGetLastError());
+  return DM_OK;
+}
+
+int dm_plan_run_field(dm_grid* g, const int64_t* cells, int32_t n, const int32_t* tiles, int32_t n_tiles,
+                      uint32_t max_cost, uint64_t* stats) {
+  using namespace dm_plan;
+  const int64_t ncell = g->W * g->H;
+  hipStream_t s = g->stream;
+  DM_HIP(hipMemcpyAsync(g->plan_travs, g->plan_trav, sizeof(uint64_t) * (size_t)g->NT * DM_TILE,
+                        hipMemcpyDeviceToDevice, s));
+  DM_HIP(hipMemsetAsync(g->plan_cost, 0xFF, sizeof(uint32_t) * (size_t)ncell, s));
+  DM_HIP(hipMemsetAsync(g->plan_stamp, 0, sizeof(uint32_t) * (size_t)g->NT, s));
+  const unsigned long long zero3[3] = {0ull, 0ull, 0ull};
+  DM_HIP(hipMemcpyAsync(g->plan_stat + ST_REACHED, zero3, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+  DM_HIP(hipMemcpyAsync(g->plan_stat + ST_ROUNDS, zero3, 2 * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+  const unsigned int len3[3] = {(unsigned int)n_tiles, 0u, 0u};
+  DM_HIP(hipMemcpyAsync(g->plan_len, len3, sizeof len3, hipMemcpyHostToDevice, s));
+  DM_HIP(hipMemcpyAsync(g->plan_src, cells, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, s));
+  DM_HIP(hipMemcpyAsync(g->plan_list[0], tiles, sizeof(int32_t) * (size_t)n_tiles, hipMemcpyHostToDevice, s));
+  for (int i = 0; i < 4; ++i) g->h_plan[i] = 0ull;
+  hipLaunchKernelGGL(k_plan_sources, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, g->plan_src, n, g->W, g->TX,
+                     g->plan_travs, g->plan_cost);
+  DM_HIP(hipGetLastError());
+  // Round bound.  Induction over rounds: after round k every cell whose
+  // shortest path crosses at most k tile borders holds its final cost (round
+  // k's visit of a tile relaxes it to its fixpoint against ring values that
+  // were final after round k - 1, and a tile whose ring changed is on the
+  // list).  A shortest path visits no cell twice, so it has fewer moves, and
+  // crosses fewer tile borders, than there are traversable cells T (sources
+  // included: T + n).  Two more rounds see the last lowered border cell's
+  // neighbours find nothing to lower and the list run empty; a visit that
+  // stops at its sweep bound (kMaxSweeps) lists its tile again, at most
+  // 4096 / kMaxSweeps + 1 = 5 visits for one ring state.
+  // The traversable count is on the host after the first wait; until then
+  // the bound is the map's cell count.
+  const auto bound_of = [&](unsigned long long trav) { return (int64_t)(5 * (trav + (unsigned long long)n) + 2); };
+  int64_t bound = g->plan_max_rounds > 0 ? g->plan_max_rounds : bound_of((unsigned long long)ncell);
+  // The list length comes back through mapped host memory, read after a wait
+  // for the rounds enqueued so far; several rounds go out per wait (4, 8, 16,
+  // ...: short fields end after one wait, long ones pay ~ one wait per 32
+  // rounds), the launches after the list ran empty exit at once.
+  const unsigned grid = (unsigned)std::min<int64_t>(g->NT, 4 * (int64_t)(g->n_cu > 0 ? g->n_cu : 256));
+  int64_t done = 0;
+  int batch = 4;
+  bool empty = false;
+  KernelTimer t;
+  while (!empty && done < bound) {
+    const int64_t nb = std::min<int64_t>(batch, bound - done);
+    dm_timer_begin(g, "plan_relax", &t);
+    for (int64_t k = 0; k < nb; ++k, ++done) {
+      hipLaunchKernelGGL(k_plan_relax, dim3(grid), dim3(kThreads), 0, s, g->plan_cost, g->plan_travs, g->W, g->H,
+                         g->TX, g->TY, max_cost, g->plan_list[done & 1], g->plan_list[(done + 1) & 1], g->plan_len,
+                         g->plan_stamp, (uint32_t)done, g->plan_stat, g->h_plan_dev);
+      DM_HIP(hipGetLastError());
+    }
+    dm_timer_end(g, &t);
+    DM_HIP(hipStreamSynchronize(s));
+    empty = g->h_plan[HS_LEN] == 0ull;
+    if (g->plan_max_rounds <= 0) bound = std::min(bound, bound_of(g->h_plan[HS_TRAV]));
+    batch = std::min(batch * 2, 32);
+  }
+  if (!empty) {  // the bound is reached: did the last round leave work?
+    unsigned int len[3];
+    DM_HIP(hipMemcpy(len, g->plan_len, sizeof len, hipMemcpyDeviceToHost));
+    if (len[done % 3] != 0u)
+      return dm_set_error(DM_ERR_INCOMPLETE, "the distance field did not settle within %lld rounds (%u tiles "
+                          "still active)%s", (long long)bound, len[done % 3],
+                          g->plan_max_rounds > 0 ? "; DM_PLAN_MAX_ROUNDS is set" : "");
+  }
+  if (stats) {
+    hipLaunchKernelGGL(k_plan_count, dim3((unsigned)std::min<int64_t>((ncell + kThreads - 1) / kThreads, 1024)),
+                       dim3(kThreads), 0, s, g->plan_cost, ncell, g->plan_stat);
+    DM_HIP(hipGetLastError());
+    unsigned long long st[4];
+    DM_HIP(hipMemcpyAsync(st, g->plan_stat, sizeof st, hipMemcpyDeviceToHost, s));
+    DM_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < 4; ++i) stats[i] = st[i];
+  }
+  return DM_OK;
+}
+
+int dm_plan_launch_query(dm_grid* g, const double* d_xy, int64_t stride, int64_t n, int32_t snap_cells,
+                         uint32_t* d_cost, int64_t* d_cell) {
+  if (n <= 0) return DM_OK;
+  KernelTimer t;
+  dm_timer_begin(g, "plan_query", &t);
+  hipLaunchKernelGGL(dm_plan::k_plan_query, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, g->stream,
+                     g->plan_cost, g->W, g->H, g->p.origin_x, g->p.origin_y, g->p.resolution, d_xy, stride, n,
+                     snap_cells, d_cost, d_cell);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  return DM_OK;
+}
+
+int dm_plan_launch_path(dm_grid* g, const int64_t* d_start, int64_t cap) {
+  KernelTimer t;
+  dm_timer_begin(g, "plan_path", &t);
+  hipLaunchKernelGGL(dm_plan::k_plan_path, dim3(1), dim3(64), 0, g->stream, g->plan_cost, g->plan_travs, g->W,
+                     g->H, g->TX, d_start, g->plan_path, cap, g->plan_stat + 4);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
   return DM_OK;
 }

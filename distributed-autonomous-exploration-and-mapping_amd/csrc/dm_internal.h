@@ -471,6 +471,34 @@ struct dm_grid {
   double* goal_io = nullptr;          // [4 * 256] robots xy, then centroids xy
   int64_t* goal_idx = nullptr;        // [256]
 
+  // path planning (dm_plan.h; dm_plan_* and dm_assign_goals_path), allocated
+  // on first use (ensure_plan).  The field is valid for the map version it was
+  // computed on: integrate_seq + reset_seq, which every state writer bumps
+  // (the integrate calls, dm_set_state, dm_set_logodds and through it dm_load:
+  // integrate_seq; dm_reset: reset_seq).
+  uint32_t* plan_cost = nullptr;      // [H][W] row-major field
+  uint64_t* plan_trav = nullptr;      // [NT][64] traversable bit rows of the last inflation
+  uint64_t* plan_travs = nullptr;     // [NT][64] the same with the field's source cells set
+  int32_t* plan_list[2] = {nullptr, nullptr};  // [NT] active tiles of even / odd rounds
+  uint32_t* plan_stamp = nullptr;     // [NT] round + 2 of the list the tile was last put on
+  unsigned int* plan_len = nullptr;   // [3] list lengths (k_plan_relax)
+  unsigned long long* plan_stat = nullptr;    // [4] reached, traversable, rounds, tile relaxations; [4..5] path length, error
+  unsigned long long* h_plan = nullptr;       // mapped: the last round's list length, rounds, relaxations, traversable
+  unsigned long long* h_plan_dev = nullptr;   // its device address
+  int64_t* plan_src = nullptr;        // [256] source cells
+  double* plan_qxy = nullptr;         // [plan_qcap][2] query targets
+  uint32_t* plan_qcost = nullptr;     // [plan_qcap]
+  int64_t* plan_qcell = nullptr;      // [plan_qcap]
+  int64_t plan_qcap = 0;
+  int64_t* plan_path = nullptr;       // [plan_pathcap] a path, target first
+  int64_t plan_pathcap = 0;
+  bool plan_valid = false;
+  uint64_t plan_version = 0;
+  uint64_t reset_seq = 0;             // dm_reset calls so far
+  // DM_PLAN_MAX_ROUNDS (read at dm_create; the test of DM_ERR_INCOMPLETE):
+  // overrides the relaxation's round bound; 0: the derived bound
+  int64_t plan_max_rounds = 0;
+
   // profiling
   bool profile = false;
   std::vector<KernelTimer> pending;
@@ -636,7 +664,20 @@ inline hipStream_t dm_exchange_stream_of(const dm_grid* g) { return g->overlap ?
 // goal selection (dm_goals.hip)
 int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, const double* d_robots, int32_t R,
                         int32_t T, int64_t min_size, double w, double min_dist,
-                        const unsigned long long** d_k, const uint32_t** d_i);
+                        const unsigned long long** d_k, const uint32_t** d_i, const uint32_t* d_cost = nullptr);
+// path planning (dm_plan.h, launched from dm_goals.hip); the plan_* arrays
+// of the handle are allocated by the caller (dm_api.cpp: ensure_plan)
+int dm_plan_launch_travers(dm_grid* g, int32_t inflate_cells);
+int dm_plan_launch_expand(dm_grid* g, uint8_t* d_out);
+// The field from n source cells (host arrays: cells, and their distinct
+// tiles) over g->plan_trav; synchronous.  stats: [4] or nullptr.
+int dm_plan_run_field(dm_grid* g, const int64_t* cells, int32_t n, const int32_t* tiles, int32_t n_tiles,
+                      uint32_t max_cost, uint64_t* stats);
+int dm_plan_launch_query(dm_grid* g, const double* d_xy, int64_t stride, int64_t n, int32_t snap_cells,
+                         uint32_t* d_cost, int64_t* d_cell);
+// walk back from *d_start into g->plan_path (cap entries); length and error
+// word go to g->plan_stat[4], [5]
+int dm_plan_launch_path(dm_grid* g, const int64_t* d_start, int64_t cap);
 int dm_launch_goal_gather(dm_grid* g, const dm_cluster* d_recs, const int64_t* d_idx, int32_t R, double* d_xy);
 int dm_launch_ld06(dm_grid* g, int32_t S, const dm_ld06_point* d_pts, const int64_t* d_offsets,
                    int32_t N, int dir, float* d_ranges, float* d_intensities);

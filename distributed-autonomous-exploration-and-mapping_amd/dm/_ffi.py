@@ -26,6 +26,7 @@ DM_ERR_INCOMPLETE = -8
 DM_ERR_PIPELINE = -9
 DM_ERR_COLLECTIVE = -10
 DM_TILE = 64
+DM_PLAN_UNREACHABLE = 0xFFFFFFFF
 
 _ERR_NAMES = {
     DM_ERR_INVALID_ARG: "DM_ERR_INVALID_ARG",
@@ -173,6 +174,13 @@ SIGNATURES = {
     "dm_set_overlap": [_vp, _i32],
     "dm_atomic_peak": [ctypes.c_int, _vp, _i32, ctypes.POINTER(_i32)],
     "dm_assign_goals": [_vp, _vp, _i32, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _vp, _vp],
+    "dm_plan_traversable": [_vp, _i32, _vp],
+    "dm_plan_field": [_vp, _vp, _i32, _i32, ctypes.c_uint32, _vp],
+    "dm_plan_get_field": [_vp, _vp],
+    "dm_plan_query": [_vp, _vp, _i64, _i32, _vp, _vp],
+    "dm_plan_path": [_vp, ctypes.c_double, ctypes.c_double, _i32, _vp, _i64, ctypes.POINTER(_i64)],
+    "dm_assign_goals_path": [_vp, _vp, _i32, _i64, ctypes.c_double, ctypes.c_double, _i32, ctypes.c_uint32, _i32,
+                             _vp, _vp, _vp],
 }
 # functions returning const char*
 STRING_FUNCS = ("dm_last_error", "dm_version")

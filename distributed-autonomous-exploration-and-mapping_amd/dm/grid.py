@@ -257,6 +257,86 @@ class OccupancyMapper:
                                             float(min_distance), _vp(idx), _vp(out)))
         return [(int(i), (float(p[0]), float(p[1]))) if i >= 0 else None for i, p in zip(idx, out)]
 
+    # -- path planning (csrc/dm_plan.h; host restatement: dm/plan.py) ------
+    PLAN_STAT_NAMES = ("reached", "traversable", "rounds", "tile_relaxations")
+
+    def plan_traversable(self, inflate_cells: int = 2) -> np.ndarray:
+        """The obstacle-inflated traversability mask (dm_plan_traversable):
+        bool [rows, W]."""
+        out = np.empty((self.rows, self.width), np.uint8)
+        with self._lock:
+            check(self._lib.dm_plan_traversable(self._handle(), int(inflate_cells), _vp(out)))
+        return out.astype(bool)
+
+    def plan_field(self, sources_xy, inflate_cells: int = 2, max_cost: int = 0) -> dict:
+        """Compute the shortest-path distance field from the source points
+        (metres) on the device (dm_plan_field); it stays in the handle for
+        plan_cost_field / plan_query / plan_path until the map changes.
+        Returns the call's statistics (PLAN_STAT_NAMES)."""
+        xy = np.ascontiguousarray(np.asarray(sources_xy, np.float64).reshape(-1, 2))
+        st = (ctypes.c_uint64 * 4)()
+        with self._lock:
+            check(self._lib.dm_plan_field(self._handle(), _vp(xy), xy.shape[0], int(inflate_cells), int(max_cost), st))
+        return {k: int(st[i]) for i, k in enumerate(self.PLAN_STAT_NAMES)}
+
+    def plan_cost_field(self) -> np.ndarray:
+        """The field (dm_plan_get_field): uint32 [rows, W], costs in fifths of
+        a cell (orthogonal move 5, diagonal 7), dm.plan.UNREACHABLE where no
+        path leads."""
+        out = np.empty((self.rows, self.width), np.uint32)
+        with self._lock:
+            check(self._lib.dm_plan_get_field(self._handle(), _vp(out)))
+        return out
+
+    def plan_query(self, targets_xy, snap_cells: int = 5):
+        """Snap target points (metres) to the field (dm_plan_query): (cost
+        uint32 [n], cell int64 [n]); (UNREACHABLE, -1) where nothing within
+        snap_cells of the target is reached."""
+        xy = np.ascontiguousarray(np.asarray(targets_xy, np.float64).reshape(-1, 2))
+        n = xy.shape[0]
+        cost = np.empty(n, np.uint32)
+        cell = np.empty(n, np.int64)
+        with self._lock:
+            check(self._lib.dm_plan_query(self._handle(), _vp(xy), n, int(snap_cells), _vp(cost), _vp(cell)))
+        return cost, cell
+
+    def plan_path(self, target_xy, snap_cells: int = 5, cap: int | None = None) -> np.ndarray:
+        """The path to the target's snapped cell, source first, as linear cell
+        indices int64 [n] (dm_plan_path); empty if the target is not reached.
+        `cap`: the buffer size to use; by default it is grown to the length
+        the library reports."""
+        n = ctypes.c_int64(0)
+        size = 4096 if cap is None else int(cap)
+        with self._lock:
+            while True:
+                buf = np.empty(max(size, 1), np.int64)
+                rc = self._lib.dm_plan_path(self._handle(), float(target_xy[0]), float(target_xy[1]),
+                                            int(snap_cells), _vp(buf), size, ctypes.byref(n))
+                if rc == _ffi.DM_ERR_CAPACITY and cap is None and n.value > size:
+                    size = int(n.value)
+                    continue
+                check(rc)
+                return buf[: int(n.value)].copy()
+
+    def assign_goals_path(self, robots_xy, min_size: int = 8, distance_weight: float = 1.0,
+                          min_distance: float = 0.0, inflate_cells: int = 2, max_cost: int = 0,
+                          snap_cells: int = 5):
+        """assign_goals scored by path length (dm_assign_goals_path): per
+        robot, in order, (cluster index, (x, y), cell) or None, where (x, y) is
+        the centre of the reachable cell the cluster's centroid snaps to.
+        Same policy as dm.plan.assign_goals_path."""
+        xy = np.ascontiguousarray(np.asarray(robots_xy, np.float64).reshape(-1, 2))
+        R = xy.shape[0]
+        idx = np.empty(R, np.int64)
+        out = np.empty((R, 2), np.float64)
+        cell = np.empty(R, np.int64)
+        with self._lock:
+            check(self._lib.dm_assign_goals_path(self._handle(), _vp(xy), R, int(min_size), float(distance_weight),
+                                                 float(min_distance), int(inflate_cells), int(max_cost),
+                                                 int(snap_cells), _vp(idx), _vp(out), _vp(cell)))
+        return [(int(i), (float(p[0]), float(p[1])), int(c)) if i >= 0 else None
+                for i, p, c in zip(idx, out, cell)]
+
     # -- frontiers --------------------------------------------------------
     def frontiers(self, want_mask=False, want_labels=False, cap=None) -> Frontiers:
         """Frontier mask / labels (optional dense copies) and the cluster

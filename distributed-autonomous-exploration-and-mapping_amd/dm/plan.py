@@ -1,0 +1,219 @@
+"""Path planning on the occupancy grid: host restatement and test reference
+of dm_plan_* and dm_assign_goals_path (csrc/dm_plan.h), as dm/goals.py is for
+dm_assign_goals.
+
+The reference explores reactively (server/thymio_project/thymio_project/
+main.py:123-188) and names map-based navigation (Nav2) as future work
+(report.pdf p.5 §VI-2), so there is no reference behaviour to match; the
+definitions are this build's SPEC (include/dm.h).  They use
+integers only, so the results are unique:
+
+* a cell is traversable iff its state is 0 and no in-grid occupied cell (100)
+  lies within ``dx*dx + dy*dy <= r*r``; source cells are traversable whatever
+  their state;
+* moves are 8-connected, cost 5 orthogonal and 7 diagonal; a diagonal move
+  needs both cells it passes between traversable (no corner cutting);
+* ``cost`` is the least total move cost from any source, ``UNREACHABLE`` where
+  there is no path of cost <= max_cost.
+
+The device computes the field by tile-wise min-relaxation; here it is
+Dijkstra (scipy) over the legal-move graph.  The fixpoint of min-relaxation is
+unique, so both give the same bits.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+UNREACHABLE = 0xFFFFFFFF
+MAX_COST = 0xFFFFFFEF  # what max_cost == 0 means: a stored cost plus a move never wraps
+ORTHOGONAL, DIAGONAL = 5, 7
+# predecessor order of a path, (dy, dx)
+NEIGHBOURS = ((-1, -1), (-1, 0), (-1, 1), (0, -1), (0, 1), (1, -1), (1, 0), (1, 1))
+
+
+def _shifted(a: np.ndarray, dy: int, dx: int) -> np.ndarray:
+    """out[y, x] = a[y + dy, x + dx], False outside the grid."""
+    H, W = a.shape
+    out = np.zeros_like(a)
+    ys, ye = max(0, -dy), min(H, H - dy)
+    xs, xe = max(0, -dx), min(W, W - dx)
+    if ys < ye and xs < xe:
+        out[ys:ye, xs:xe] = a[ys + dy:ye + dy, xs + dx:xe + dx]
+    return out
+
+
+def traversable(state, r: int) -> np.ndarray:
+    """bool [H, W]: free and no occupied cell within the disc of radius r."""
+    st = np.asarray(state)
+    r = int(r)
+    if not 0 <= r <= 32:
+        raise ValueError("inflate_cells must be in [0, 32]")
+    occ = st == 100
+    blocked = np.zeros(st.shape, bool)
+    if occ.any():
+        for dy in range(-r, r + 1):
+            for dx in range(-r, r + 1):
+                if dx * dx + dy * dy <= r * r:
+                    blocked |= _shifted(occ, dy, dx)
+    return (st == 0) & ~blocked
+
+
+def cell_of(x: float, y: float, origin_x: float, origin_y: float, resolution: float, width: int, height: int):
+    """(cx, cy) of a point in metres (floor((x - origin) / resolution), as
+    the integration's endpoints), or None outside the grid."""
+    fx = math.floor((float(x) - origin_x) / resolution) if math.isfinite(x) else -1
+    fy = math.floor((float(y) - origin_y) / resolution) if math.isfinite(y) else -1
+    if not (0 <= fx < width and 0 <= fy < height):
+        return None
+    return int(fx), int(fy)
+
+
+def with_sources(trav: np.ndarray, sources_cells) -> np.ndarray:
+    t = np.array(trav, bool)
+    H, W = t.shape
+    for cx, cy in sources_cells:
+        if not (0 <= cx < W and 0 <= cy < H):
+            raise ValueError(f"source cell ({cx}, {cy}) is outside the grid")
+        t[cy, cx] = True
+    return t
+
+
+def legal_moves(trav: np.ndarray):
+    """For each (dy, dx) of NEIGHBOURS: bool [H, W], the move c -> c + (dy, dx)
+    is legal (c itself traversable included)."""
+    out = []
+    for dy, dx in NEIGHBOURS:
+        ok = trav & _shifted(trav, dy, dx)
+        if dy != 0 and dx != 0:
+            ok &= _shifted(trav, dy, 0) & _shifted(trav, 0, dx)
+        out.append(ok)
+    return out
+
+
+def field(state, sources_cells, r: int, max_cost: int = 0, trav: np.ndarray | None = None) -> np.ndarray:
+    """uint32 [H, W] distance field from the source cells [(cx, cy), ...].
+    `trav`: a traversable mask to use instead of traversable(state, r)."""
+    from scipy.sparse import csr_matrix
+    from scipy.sparse.csgraph import dijkstra
+
+    sources = [(int(cx), int(cy)) for cx, cy in sources_cells]
+    if not sources:
+        raise ValueError("need at least one source")
+    t = with_sources(traversable(state, r) if trav is None else trav, sources)
+    H, W = t.shape
+    max_cost = MAX_COST if int(max_cost) == 0 or int(max_cost) > MAX_COST else int(max_cost)
+    src, dst, wgt = [], [], []
+    for (dy, dx), ok in zip(NEIGHBOURS, legal_moves(t)):
+        c = np.flatnonzero(ok)
+        src.append(c)
+        dst.append(c + dy * W + dx)
+        wgt.append(np.full(c.shape, DIAGONAL if dy and dx else ORTHOGONAL, np.float64))
+    g = csr_matrix((np.concatenate(wgt), (np.concatenate(src), np.concatenate(dst))), shape=(H * W, H * W))
+    idx = sorted({cy * W + cx for cx, cy in sources})
+    d = dijkstra(g, directed=True, indices=idx, min_only=True, limit=float(max_cost))
+    out = np.full(H * W, UNREACHABLE, np.uint32)
+    ok = np.isfinite(d) & (d <= max_cost)
+    out[ok] = d[ok].astype(np.uint32)  # integer costs are exact in float64
+    return out.reshape(H, W)
+
+
+def snap(cost: np.ndarray, cell, s: int):
+    """(cost, linear cell) of the reached cell within Chebyshev distance s of
+    `cell` = (cx, cy) that minimises (dx*dx + dy*dy, linear index);
+    (UNREACHABLE, -1) if none or cell is None."""
+    if cell is None:
+        return UNREACHABLE, -1
+    H, W = cost.shape
+    cx, cy = cell
+    best = None
+    for dy in range(-s, s + 1):
+        for dx in range(-s, s + 1):
+            x, y = cx + dx, cy + dy
+            if not (0 <= x < W and 0 <= y < H) or cost[y, x] == UNREACHABLE:
+                continue
+            key = (dx * dx + dy * dy, y * W + x)
+            if best is None or key < best:
+                best = key
+    if best is None:
+        return UNREACHABLE, -1
+    return int(cost.reshape(-1)[best[1]]), int(best[1])
+
+
+def path(cost: np.ndarray, trav: np.ndarray, cell: int) -> list[int]:
+    """Linear indices from a source to `cell` (a reached cell; -1: empty
+    path).  `trav` includes the sources (with_sources).  The predecessor of c
+    is the first neighbour in NEIGHBOURS order that is reached, moves legally
+    to c and has cost + w == cost[c]."""
+    if cell < 0:
+        return []
+    H, W = cost.shape
+    out = [int(cell)]
+    x, y = cell % W, cell // W
+    if cost[y, x] == UNREACHABLE:
+        return []
+    while cost[y, x] != 0:
+        for dy, dx in NEIGHBOURS:
+            nx, ny = x + dx, y + dy
+            if not (0 <= nx < W and 0 <= ny < H) or cost[ny, nx] == UNREACHABLE:
+                continue
+            w = DIAGONAL if dy and dx else ORTHOGONAL
+            if int(cost[ny, nx]) + w != int(cost[y, x]):
+                continue
+            if dy and dx and not (trav[ny, x] and trav[y, nx]):
+                continue
+            x, y = nx, ny
+            break
+        else:
+            raise AssertionError("the field is not a fixpoint: no predecessor")
+        out.append(y * W + x)
+    return out[::-1]
+
+
+def assign_goals_path(state, clusters: np.ndarray, robots_xy, origin_x: float, origin_y: float, resolution: float,
+                      min_size: int = 8, distance_weight: float = 1.0, min_distance: float = 0.0,
+                      inflate_cells: int = 2, max_cost: int = 0, snap_cells: int = 5, cache: dict | None = None):
+    """dm.goals.assign_goals scored by path length: per robot, in order,
+    (cluster index, (x, y) centre of the snapped cell, snapped cell) or None.
+    dist = cost * resolution / 5 from the robot's own field to the cluster
+    centroid's snapped cell; clusters that are not reached are not eligible.
+    `cache`: a dict the per-robot fields are kept in (keyed by the robot's
+    cell) for further calls on the same state, inflation and max_cost."""
+    if not float(distance_weight) >= 0.0:
+        raise ValueError("distance_weight must be >= 0 (dm_assign_goals_path rejects it too)")
+    st = np.asarray(state)
+    H, W = st.shape
+    robots = [(float(x), float(y)) for x, y in robots_xy]
+    cells = [cell_of(x, y, origin_x, origin_y, resolution, W, H) for x, y in robots]
+    if any(c is None for c in cells):
+        raise ValueError("a robot is outside the grid")
+    if clusters is None or len(clusters) == 0:
+        return [None] * len(robots)
+    trav = traversable(st, inflate_cells)
+    targets = [cell_of(float(c["cx_m"]), float(c["cy_m"]), origin_x, origin_y, resolution, W, H) for c in clusters]
+    size = clusters["size"].astype(np.float64)
+    taken = np.zeros(len(clusters), bool)
+    out = []
+    for rc in cells:
+        f = cache.get(rc) if cache is not None else None
+        if f is None:
+            f = field(st, [rc], inflate_cells, max_cost, trav=trav)
+            if cache is not None:
+                cache[rc] = f
+        snapped = [snap(f, t, snap_cells) for t in targets]
+        cost = np.array([s[0] for s in snapped], np.uint32)
+        dist = cost.astype(np.float64) * float(resolution) / 5.0
+        ok = (clusters["size"] >= min_size) & (cost != UNREACHABLE) & (dist >= min_distance) & ~taken
+        util = np.where(ok, size / (1.0 + float(distance_weight) * dist), -np.inf)
+        m = util.max()
+        if not np.isfinite(m):
+            out.append(None)
+            continue
+        best = np.flatnonzero(util == m)
+        i = int(best[np.argmin(clusters["label"][best])])  # ties: the smaller label
+        taken[i] = True
+        cell = snapped[i][1]
+        xy = (origin_x + ((cell % W) + 0.5) * resolution, origin_y + ((cell // W) + 0.5) * resolution)
+        out.append((i, xy, cell))
+    return out

@@ -97,6 +97,13 @@ class PoseStamped:
 
 
 @dataclass
+class Path:
+    """nav_msgs/Path: the poses of a plan, start first."""
+    header: Header = field(default_factory=Header)
+    poses: list = field(default_factory=list)
+
+
+@dataclass
 class MapMetaData:
     map_load_time: float = 0.0
     resolution: float = 0.05
@@ -189,6 +196,11 @@ class SlamParams:
     dm_goal_min_size: int = 8
     dm_goal_distance_weight: float = 1.0
     dm_goal_min_distance: float = 0.3
+    # score goals by path length over the inflated map (dm_assign_goals_path)
+    # and publish the path on /plan; off: straight-line distance, as before
+    dm_goal_path_distance: bool = False
+    dm_goal_inflate_m: float = 0.10       # obstacle inflation radius (the robot's)
+    dm_goal_snap_m: float = 0.25          # how far a goal may move to reach a traversable cell
 
     @classmethod
     def from_dict(cls, d: dict) -> "SlamParams":
@@ -208,6 +220,14 @@ class SlamParams:
             doc = yaml.safe_load(fh) or {}
         section = doc.get(node_name, doc.get("/**", {}))
         return cls.from_dict(section.get("ros__parameters", {}))
+
+    def goal_cells(self) -> tuple[int, int]:
+        """(inflate_cells, snap_cells): the two lengths in cells,
+        ceil(x / resolution), clamped to the C-ABI's limits (32, 16)."""
+        res = float(self.resolution)
+        inflate = int(math.ceil(float(self.dm_goal_inflate_m) / res))
+        snap = int(math.ceil(float(self.dm_goal_snap_m) / res))
+        return min(max(inflate, 0), 32), min(max(snap, 0), 16)
 
     def grid_params(self):
         kw = dict(resolution=float(self.resolution), range_max=float(self.max_laser_range))
@@ -316,7 +336,7 @@ class MappingNode:
 
     def __init__(self, params: SlamParams | None = None, pose_provider=None, map_publisher=None,
                  frontier_publisher=None, goal_publisher=None, clock=time.monotonic, gate: bool = True,
-                 mapper=None, **overrides):
+                 mapper=None, plan_publisher=None, **overrides):
         """`overrides` set SlamParams fields (tests: dm_width=..., ...).
         `mapper`: an object with OccupancyMapper's interface to use instead of
         creating one (tests inject CPU stand-ins)."""
@@ -340,6 +360,8 @@ class MappingNode:
         self.map_pub = map_publisher or ListPublisher("/map")
         self.frontier_pub = frontier_publisher or ListPublisher("/frontiers")
         self.goal_pub = goal_publisher or ListPublisher("/goal_pose")
+        self.plan_pub = plan_publisher or ListPublisher("/plan")
+        self.last_plan = None  # the Path of the last goal chosen by path length
         self.clock = clock
         self._last_publish = -math.inf
         self._pass_stamp = None  # stamp of the frontier pass in flight (None: none)
@@ -421,6 +443,9 @@ class MappingNode:
             return None
         x, y, _ = self.latest_pose
         s = self.slam
+        self.last_plan = None
+        if s.dm_goal_path_distance:
+            return self._choose_goal_by_path(x, y, self._last_publish if stamp is None else stamp)
         g = self.mapper.assign_goals([(x, y)], min_size=s.dm_goal_min_size,
                                      distance_weight=s.dm_goal_distance_weight,
                                      min_distance=s.dm_goal_min_distance)[0]
@@ -429,6 +454,37 @@ class MappingNode:
         gx, gy = g[1]
         msg = PoseStamped(header=Header(stamp=self._last_publish if stamp is None else stamp,
                                         frame_id=s.map_frame))
+        msg.pose.position = Point(gx, gy, 0.0)
+        msg.pose.orientation = quaternion_from_yaw(math.atan2(gy - y, gx - x))
+        return msg
+
+    def _choose_goal_by_path(self, x: float, y: float, stamp: float):
+        """dm_goal_path_distance: the goal is the centre of a reachable cell,
+        scored by the path length from the robot (dm_assign_goals_path), and
+        the path to it (dm_plan_path over the field that call left) becomes
+        ``last_plan``, a nav_msgs/Path whose poses face along the path."""
+        s = self.slam
+        inflate, snap = s.goal_cells()
+        g = self.mapper.assign_goals_path([(x, y)], min_size=s.dm_goal_min_size,
+                                          distance_weight=s.dm_goal_distance_weight,
+                                          min_distance=s.dm_goal_min_distance, inflate_cells=inflate,
+                                          snap_cells=snap)[0]
+        if g is None:
+            return None
+        gx, gy = g[1]
+        header = Header(stamp=stamp, frame_id=s.map_frame)
+        p = self.params
+        cells = self.mapper.plan_path((gx, gy), snap_cells=0)
+        px = float(p.origin_x) + ((cells % int(p.width)) + 0.5) * float(p.resolution)
+        py = float(p.origin_y) + ((cells // int(p.width)) + 0.5) * float(p.resolution)
+        plan = Path(header=header)
+        for i in range(len(cells)):
+            j = min(i + 1, len(cells) - 1)
+            yaw = math.atan2(py[j] - py[j - 1], px[j] - px[j - 1]) if len(cells) > 1 else 0.0
+            plan.poses.append(PoseStamped(header=header, pose=Pose(position=Point(float(px[i]), float(py[i]), 0.0),
+                                                                   orientation=quaternion_from_yaw(yaw))))
+        self.last_plan = plan
+        msg = PoseStamped(header=header)
         msg.pose.position = Point(gx, gy, 0.0)
         msg.pose.orientation = quaternion_from_yaw(math.atan2(gy - y, gx - x))
         return msg
@@ -459,6 +515,8 @@ class MappingNode:
             goal = self.choose_goal(stamp)
             if goal is not None:
                 self.goal_pub.publish(goal)
+                if self.last_plan is not None:
+                    self.plan_pub.publish(self.last_plan)
         return True
 
     def map_image_png(self) -> bytes:
@@ -492,7 +550,7 @@ def main(args=None):  # pragma: no cover - needs ROS 2
     import rclpy
     from rclpy.node import Node
     from sensor_msgs.msg import LaserScan as RosLaserScan
-    from nav_msgs.msg import OccupancyGrid as RosGrid
+    from nav_msgs.msg import OccupancyGrid as RosGrid, Path as RosPath
     from geometry_msgs.msg import PoseArray, Pose as RosPose, PoseStamped as RosPoseStamped
     import tf2_ros
 
@@ -540,8 +598,23 @@ def main(args=None):  # pragma: no cover - needs ROS 2
             m.pose.orientation.z, m.pose.orientation.w = q.z, q.w
             goal_pub.publish(m)
 
+    plan_pub = node.create_publisher(RosPath, "/plan", 10)
+
+    class _PlanAdapter:
+        def publish(self, plan):
+            m = RosPath()
+            m.header.frame_id = plan.header.frame_id
+            m.header.stamp = node.get_clock().now().to_msg()
+            for ps in plan.poses:
+                q = RosPoseStamped()
+                q.header = m.header
+                q.pose.position.x, q.pose.position.y = ps.pose.position.x, ps.pose.position.y
+                q.pose.orientation.z, q.pose.orientation.w = ps.pose.orientation.z, ps.pose.orientation.w
+                m.poses.append(q)
+            plan_pub.publish(m)
+
     mn = MappingNode(sp, pose_provider=lookup, map_publisher=map_pub, frontier_publisher=_FrontierAdapter(),
-                     goal_publisher=_GoalAdapter(), clock=lambda: node.get_clock().now().nanoseconds * 1e-9)
+                     goal_publisher=_GoalAdapter(), plan_publisher=_PlanAdapter(), clock=lambda: node.get_clock().now().nanoseconds * 1e-9)
     node.create_subscription(RosLaserScan, sp.scan_topic, mn.scan_cb, 10)
     # slam_toolbox publishes the map on its own period, not per scan
     node.create_timer(sp.map_update_interval, mn.timer_cb)

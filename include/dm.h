@@ -15,6 +15,10 @@
  *   the reference; its contract is SURVEY.md §8(a) rows a8-a10.
  *   Each entry point below names the step of that pipeline it takes over.  The
  *   ctypes binding a ROS node would add is shown in INTEGRATION.md.
+ *   The dm_plan_* calls and dm_assign_goals_path go past the reference: they
+ *   are the map-based navigation its report lists as future work (§VI-2,
+ *   Nav2): an inflated traversability mask, a shortest-path distance field,
+ *   reachable goals and the paths to them, all on the device-resident map.
  *
  * CONVENTIONS
  *   - Every function returns int: DM_OK (0) or a negative DM_ERR_* code; on
@@ -46,8 +50,9 @@ extern "C" {
 #define DM_ERR_CAPACITY (-5)
 #define DM_ERR_IO (-6)
 #define DM_ERR_STATE (-7)
-#define DM_ERR_INCOMPLETE (-8) /* a pass has no result: an export record was incomplete, or a
-                                  union-find loop hit its iteration bound */
+#define DM_ERR_INCOMPLETE (-8) /* a pass has no result: an export record was incomplete, a
+                                  union-find loop hit its iteration bound, or dm_plan_field's
+                                  relaxation hit its round bound */
 #define DM_ERR_PIPELINE (-9)   /* a cross-stream hand-off of the overlapped pipeline (dm_set_overlap)
                                   timed out: the map update it guarded was skipped, so the map
                                   misses batches; sticky until dm_reset */
@@ -58,6 +63,9 @@ extern "C" {
 
 /* Tile edge (cells) used by the kernels; band_row0 must be a multiple of it. */
 #define DM_TILE 64
+
+/* Distance-field value of a cell no path reaches (dm_plan_field). */
+#define DM_PLAN_UNREACHABLE 0xFFFFFFFFu
 
 /* Map parameters.  Defaults (dm_default_params) come from the reference where
  * it has them: resolution 0.05 (slam_config.yaml:26), max range 12.0
@@ -241,7 +249,9 @@ int dm_set_overlap(dm_grid* g, int32_t on);
  * rows and band export records between the devices with peer copies (xGMI)
  * and merges on band 0's device (dm_merge_bands).  The multi-process building
  * blocks below (halos, edge rows / labels, exports, merges, dm_set_stream)
- * return DM_ERR_INVALID_ARG on such a handle.  Replaces: slam_toolbox's
+ * return DM_ERR_INVALID_ARG on such a handle, and so do the path planning
+ * calls (dm_plan_*, dm_assign_goals_path), which need the whole map in one
+ * handle: sharded planning is not implemented.  Replaces: slam_toolbox's
  * single map thread for a map too large (or too many robots) for one GPU;
  * the caller is the ROS node wired at pc_server.launch.py:12-19. */
 int dm_create_sharded(dm_grid** out, const dm_params* p, int32_t nranks, const int32_t* devices);
@@ -371,6 +381,92 @@ int dm_map_image(dm_grid* g, uint8_t* out);
  * (none collected yet, or a later pass reused its readback slot). */
 int dm_assign_goals(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size,
                     double distance_weight, double min_distance, int64_t* out_index, double* out_xy);
+
+/* ---- Path planning on the device-resident map.  The reference has none: its
+ * robots move by the reactive IR / LiDAR policy of main.py:123-188, and its
+ * report (§VI-2) names Nav2 as future work.  These calls take over what Nav2's
+ * global costmap (inflation layer) and global planner would compute, from the
+ * map this library already holds.  All of them are synchronous, ordered after
+ * everything enqueued on the handle, and need a handle that covers the whole
+ * map: a band handle (band_rows != height) or a dm_create_sharded handle
+ * returns DM_ERR_INVALID_ARG.
+ *
+ * Definitions (integers only: every result is unique and bit-exact).
+ *   Traversable cell, for inflate_cells = r in [0, 32]: state == 0 and no
+ *     in-grid cell with state == 100 within dx*dx + dy*dy <= r*r.  Out-of-grid
+ *     cells are not obstacles; unknown cells are not traversable; the source
+ *     cells of a field are traversable whatever their state.
+ *   Moves: 8-connected, orthogonal cost 5, diagonal cost 7; a diagonal move
+ *     (x, y) -> (x+sx, y+sy) is legal only if (x+sx, y) and (x, y+sy) are both
+ *     traversable (no corner cutting).
+ *   Field: uint32 cost[height*width], the least total move cost from any
+ *     source cell over traversable cells; sources have cost 0;
+ *     DM_PLAN_UNREACHABLE marks cells that are not reached.  SATURATION: a
+ *     cost above max_cost is never stored, such cells stay
+ *     DM_PLAN_UNREACHABLE; max_cost == 0 (or any value above it) means
+ *     0xFFFFFFEF, so a stored cost plus a move cost never wraps.
+ *     metres = (double)cost * resolution / 5.0 (two rounded operations).
+ *   Cell of a point: floor((x - origin_x) / resolution), likewise y (as the
+ *     integration's endpoints).
+ *   Snap, for snap_cells = s in [0, 16]: the reached in-grid cell within
+ *     Chebyshev distance s of the target's cell that minimises (dx*dx + dy*dy,
+ *     linear index); none, or a target out of the grid: cost
+ *     DM_PLAN_UNREACHABLE and cell -1.
+ *   Path: from the snapped cell back to cost 0; the predecessor of c is the
+ *     first neighbour n, in the order (dy, dx) = (-1,-1), (-1,0), (-1,1),
+ *     (0,-1), (0,1), (1,-1), (1,0), (1,1), that is reached, whose move n -> c
+ *     is legal and with cost[n] + w(n, c) == cost[c].
+ * The field lives on the device in the handle (allocated on first use,
+ * DM_ERR_OOM if that fails; freed by dm_destroy) and is stamped with the map's
+ * version: after any call that writes the map (dm_integrate*, dm_set_state,
+ * dm_set_logodds, dm_reset, dm_load) dm_plan_get_field, dm_plan_query and
+ * dm_plan_path return DM_ERR_STATE until dm_plan_field ran again. */
+
+/* The traversability mask: out[height*width] = 1 / 0, row-major.  Replaces
+ * the inflation layer of Nav2's global costmap (binary: lethal within the
+ * inflation radius).  Does not touch the handle's field. */
+int dm_plan_traversable(dm_grid* g, int32_t inflate_cells, uint8_t* out);
+/* Compute the field from n_sources (1..256) points sources_xy[2i], [2i+1]
+ * (metres; one outside the grid: DM_ERR_INVALID_ARG).  out_stats (may be
+ * NULL) receives [4]: reached cells, traversable cells (sources not
+ * counted), relaxation rounds, tile relaxations.  DM_ERR_INCOMPLETE if the
+ * relaxation did not settle within its round bound (the handle then has no
+ * field); the environment variable DM_PLAN_MAX_ROUNDS, read at dm_create,
+ * overrides the bound (tests).  Replaces Nav2's global planner's expansion
+ * (NavFn's potential field), from the robots instead of from the goal. */
+int dm_plan_field(dm_grid* g, const double* sources_xy, int32_t n_sources, int32_t inflate_cells,
+                  uint32_t max_cost, uint64_t* out_stats);
+/* The field: out[height*width] row-major. */
+int dm_plan_get_field(dm_grid* g, uint32_t* out);
+/* Snap n targets (metres) to the field: out_cost[i], out_cell[i] (linear
+ * index cy*width + cx, or -1). */
+int dm_plan_query(dm_grid* g, const double* targets_xy, int64_t n, int32_t snap_cells,
+                  uint32_t* out_cost, int64_t* out_cell);
+/* The path to the target's snapped cell, source first, as linear indices
+ * cy*width + cx; *n_out = its length.  An unreachable target is DM_OK with
+ * *n_out = 0; cap too small is DM_ERR_CAPACITY with *n_out = the full length
+ * (out_cells unspecified).  Replaces the path Nav2's planner server returns
+ * for the goal published on /goal_pose. */
+int dm_plan_path(dm_grid* g, double tx, double ty, int32_t snap_cells, int64_t* out_cells, int64_t cap,
+                 int64_t* n_out);
+/* dm_assign_goals scored by path length: over the same clusters, with the
+ * same availability rule, errors, greedy order, ties and n_robots <= 256
+ * limit.  For robot r the field is computed from r's cell alone (a robot
+ * outside the grid: DM_ERR_INVALID_ARG), every centroid is snapped to it, and
+ *   dist = (double)cost * resolution / 5.0
+ *   util = size / (1 + distance_weight * dist)
+ * over clusters with size >= min_size that are reached and have
+ * dist >= min_distance.  out_index[r] as dm_assign_goals; out_cell[r] = the
+ * snapped cell (-1: none) and out_xy[2r], [2r+1] = its centre,
+ * origin + (c + 0.5) * resolution (NaN if none): a goal that can be driven
+ * to, where a concave frontier's centroid may lie in unknown or occupied
+ * space.  The handle's field is left as the last robot's.  Replaces the
+ * reactive policy of main.py:123-188 like dm_assign_goals, with the distance
+ * Nav2's planner would report. */
+int dm_assign_goals_path(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size,
+                         double distance_weight, double min_distance, int32_t inflate_cells,
+                         uint32_t max_cost, int32_t snap_cells, int64_t* out_index, double* out_xy,
+                         int64_t* out_cell);
 
 /* Measured uncontended atomic throughput of HIP device `device` (the
  * north star's "atomic throughput against MI355X peak": no vendor figure
