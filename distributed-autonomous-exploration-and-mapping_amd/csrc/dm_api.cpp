@@ -72,6 +72,16 @@ void dev_free(T*& p) {
   p = nullptr;
 }
 
+// grow-on-demand scratch: (re)allocate *p to n elements when *cap is smaller
+template <class T>
+int dev_grow(T** p, int64_t* cap, int64_t n, const char* what) {
+  if (n <= *cap) return DM_OK;
+  *cap = 0;
+  const int rc = dev_alloc(p, n, what);
+  if (!rc) *cap = n;
+  return rc;
+}
+
 int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 int validate_params(const dm_params* p) {
@@ -655,6 +665,9 @@ int dm_destroy(dm_grid* g) {
   dev_free(g->plan_src); dev_free(g->plan_qxy); dev_free(g->plan_qcost); dev_free(g->plan_qcell);
   dev_free(g->plan_path);
   if (g->h_plan) (void)hipHostFree(g->h_plan);
+  dev_free(g->match_V); dev_free(g->match_kern); dev_free(g->match_tiles); dev_free(g->match_pose4);
+  dev_free(g->match_trig); dev_free(g->match_ranges); dev_free(g->match_q); dev_free(g->match_vol);
+  dev_free(g->match_out);
   for (auto& w : g->iw) {
     dev_free(w.pieces); dev_free(w.hitems); dev_free(w.litems); dev_free(w.heavy_list); dev_free(w.slabs);
     dev_free(w.heavy_done); dev_free(w.tile_count); dev_free(w.tile_cur); dev_free(w.cnt); dev_free(w.sh);
@@ -1589,6 +1602,165 @@ int dm_assign_goals_path(dm_grid* g, const double* robots_xy, int32_t n_robots, 
     }
   }
   memcpy(out_index, idx.data(), sizeof(int64_t) * (size_t)R);
+  return DM_OK;
+}
+
+// ---- scan matcher (csrc/dm_match.h): response field, score volume, best
+// candidate ----------------------------------------------------------------------
+
+static int match_check_table(int32_t smear_cells, const uint8_t* kern) {
+  if (smear_cells < 0 || smear_cells > 16)
+    return dm_set_error(DM_ERR_INVALID_ARG, "smear_cells must be in [0, 16] (got %d)", smear_cells);
+  if (!kern) return dm_set_error(DM_ERR_INVALID_ARG, "kern is NULL");
+  return DM_OK;
+}
+
+// The field's table and map version: a change drops every built tile.
+static int match_set_table(dm_grid* g, int32_t r, const uint8_t* kern) {
+  int rc = DM_OK;
+  if (!g->match_V) {
+    if ((rc = dev_alloc(&g->match_kern, 16 * 16 + 1, "smear table"))) return rc;
+    if ((rc = dev_alloc(&g->match_tiles, g->NT, "match tile list"))) return rc;
+    if ((rc = dev_alloc(&g->match_V, g->W * g->H, "response field"))) return rc;
+    g->match_r = -1;
+  }
+  const size_t n = (size_t)r * r + 1;
+  const uint64_t version = plan_map_version(g);
+  if (g->match_r == r && g->match_version == version && g->match_kern_h.size() == n &&
+      memcmp(g->match_kern_h.data(), kern, n) == 0)
+    return DM_OK;
+  g->match_r = -1;
+  g->match_built.assign((size_t)g->NT, 0);
+  g->match_kern_h.assign(kern, kern + n);
+  // pageable source: the copy is staged before the call returns
+  DM_HIP(hipMemcpyAsync(g->match_kern, g->match_kern_h.data(), n, hipMemcpyHostToDevice, g->stream));
+  g->match_r = r;
+  g->match_version = version;
+  return DM_OK;
+}
+
+// Build the tiles of `want` (one flag per tile) that the field does not hold yet.
+static int match_build_tiles(dm_grid* g, const std::vector<uint8_t>& want) {
+  std::vector<int32_t> list;
+  for (int64_t t = 0; t < g->NT; ++t)
+    if (want[(size_t)t] && !g->match_built[(size_t)t]) list.push_back((int32_t)t);
+  if (list.empty()) return DM_OK;
+  bool mono = true;  // kern does not increase in d2: the nearest occupied cell decides
+  for (size_t i = 1; i < g->match_kern_h.size(); ++i) mono = mono && g->match_kern_h[i] <= g->match_kern_h[i - 1];
+  DM_HIP(hipMemcpyAsync(g->match_tiles, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));  // `list` is a local
+  int rc = dm_match_launch_field(g, (int32_t)list.size(), g->match_r, mono);
+  if (rc) return rc;
+  for (int32_t t : list) g->match_built[(size_t)t] = 1;
+  return DM_OK;
+}
+
+int dm_match_field(dm_grid* g, int32_t smear_cells, const uint8_t* kern, uint8_t* out) {
+  int rc = plan_check_handle(g, "dm_match_field");
+  if (rc || (rc = use_device(g))) return rc;
+  if ((rc = match_check_table(smear_cells, kern))) return rc;
+  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
+  DM_HIP(dm_sync_all(g));
+  if ((rc = match_set_table(g, smear_cells, kern))) return rc;
+  if ((rc = match_build_tiles(g, std::vector<uint8_t>((size_t)g->NT, 1)))) return rc;
+  DM_HIP(hipMemcpyAsync(out, g->match_V, (size_t)(g->W * g->H), hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  return DM_OK;
+}
+
+int dm_match_scans(dm_grid* g, int32_t S, const double* poses, int32_t N, const float* ranges, float angle_min,
+                   float angle_increment, int32_t A, const double* yaw_offsets, int32_t k0, int32_t sub,
+                   int32_t half, int32_t stride, int32_t smear_cells, const uint8_t* kern, int32_t* out_best,
+                   uint32_t* out_score, int32_t* out_n_used, double* out_pose, uint32_t* out_volume) {
+  int rc = plan_check_handle(g, "dm_match_scans");
+  if (rc || (rc = use_device(g))) return rc;
+  if ((rc = check_integrate_args(S, N, poses, ranges))) return rc;
+  if (A < 1 || A > 64) return dm_set_error(DM_ERR_INVALID_ARG, "A must be in [1, 64] (got %d)", A);
+  if (k0 < 0 || k0 >= A) return dm_set_error(DM_ERR_INVALID_ARG, "k0 must be in [0, A) (got %d, A = %d)", k0, A);
+  if (sub < 1 || sub > 16) return dm_set_error(DM_ERR_INVALID_ARG, "sub must be in [1, 16] (got %d)", sub);
+  if (half < 0 || half > 32) return dm_set_error(DM_ERR_INVALID_ARG, "half must be in [0, 32] (got %d)", half);
+  if (stride < 1 || stride > 16)
+    return dm_set_error(DM_ERR_INVALID_ARG, "stride must be in [1, 16] (got %d)", stride);
+  if ((rc = match_check_table(smear_cells, kern))) return rc;
+  if (!yaw_offsets) return dm_set_error(DM_ERR_INVALID_ARG, "yaw_offsets is NULL");
+  if (S > 0 && (!poses || !out_best || !out_score || !out_n_used || !out_pose))
+    return dm_set_error(DM_ERR_INVALID_ARG, "poses / out_best / out_score / out_n_used / out_pose is NULL");
+  if ((int64_t)S * A * std::max(N, 1) > (1ll << 31) - 1)
+    return dm_set_error(DM_ERR_SHAPE, "S*A*N must be < 2^31");
+  if (S == 0) return DM_OK;
+  DM_HIP(dm_sync_all(g));  // after everything enqueued on the handle, on every stream of it
+  if ((rc = match_set_table(g, smear_cells, kern))) return rc;
+
+  const int64_t SA = (int64_t)S * A, T1 = 2 * half + 1, T = T1 * T1, nb = (int64_t)S * N;
+  if ((rc = dev_grow(&g->match_pose4, &g->match_pose_cap, 4 * SA, "candidate poses")) ||
+      (rc = dev_grow(&g->match_trig, &g->match_trig_cap, 2 * (int64_t)N, "beam angle table")) ||
+      (rc = dev_grow(&g->match_ranges, &g->match_ranges_cap, nb, "ranges")) ||
+      (rc = dev_grow(&g->match_q, &g->match_q_cap, SA * N, "fine coordinates")) ||
+      (rc = dev_grow(&g->match_vol, &g->match_vol_cap, SA * T, "score volume")) ||
+      (rc = dev_grow(&g->match_out, &g->match_out_cap, 5 * (int64_t)S, "match results")))
+    return rc;
+
+  // host trigonometry with the C library, as dm_integrate: the beam angle
+  // table and cos / sin of every candidate yaw (one double add each)
+  const double step = g->p.resolution / (double)sub;
+  std::vector<double> trig(2 * (size_t)N), pose4(4 * (size_t)SA);
+  for (int32_t i = 0; i < N; ++i) {
+    const double phi = (double)angle_min + (double)i * (double)angle_increment;
+    trig[2 * (size_t)i] = cos(phi);
+    trig[2 * (size_t)i + 1] = sin(phi);
+  }
+  // the tiles the search windows reach: every used beam ends within range_max
+  // of its pose and a translation moves it by at most half * stride fine
+  // steps; two cells of slack cover the rounding of the endpoint arithmetic
+  std::vector<uint8_t> want((size_t)g->NT, 0);
+  const double reach = (double)g->p.range_max + (double)(half * stride + 1) * step + 2.0 * g->p.resolution;
+  for (int32_t s = 0; s < S; ++s) {
+    const double x = poses[3 * s], y = poses[3 * s + 1], yaw = poses[3 * s + 2];
+    for (int32_t k = 0; k < A; ++k) {
+      const double yk = yaw + yaw_offsets[k];
+      double* p4 = &pose4[4 * ((size_t)s * A + k)];
+      p4[0] = x;
+      p4[1] = y;
+      p4[2] = cos(yk);
+      p4[3] = sin(yk);
+    }
+    if (!(isfinite(x) && isfinite(y)) || N == 0) continue;
+    const double fx0 = floor((x - reach - g->p.origin_x) / g->p.resolution) - 1.0;
+    const double fx1 = floor((x + reach - g->p.origin_x) / g->p.resolution) + 1.0;
+    const double fy0 = floor((y - reach - g->p.origin_y) / g->p.resolution) - 1.0;
+    const double fy1 = floor((y + reach - g->p.origin_y) / g->p.resolution) + 1.0;
+    if (!(fx1 >= 0.0 && fy1 >= 0.0 && fx0 < (double)g->W && fy0 < (double)g->H)) continue;
+    const int64_t tx0 = (int64_t)std::max(fx0, 0.0) / DM_TILE, ty0 = (int64_t)std::max(fy0, 0.0) / DM_TILE;
+    const int64_t tx1 = (int64_t)std::min(fx1, (double)(g->W - 1)) / DM_TILE;
+    const int64_t ty1 = (int64_t)std::min(fy1, (double)(g->H - 1)) / DM_TILE;
+    for (int64_t ty = ty0; ty <= ty1; ++ty)
+      for (int64_t tx = tx0; tx <= tx1; ++tx) want[(size_t)(ty * g->TX + tx)] = 1;
+  }
+  if ((rc = match_build_tiles(g, want))) return rc;
+
+  hipStream_t st = g->stream;
+  DM_HIP(hipMemcpyAsync(g->match_pose4, pose4.data(), sizeof(double) * pose4.size(), hipMemcpyHostToDevice, st));
+  if (N > 0) {
+    DM_HIP(hipMemcpyAsync(g->match_trig, trig.data(), sizeof(double) * trig.size(), hipMemcpyHostToDevice, st));
+    DM_HIP(hipMemcpyAsync(g->match_ranges, ranges, sizeof(float) * (size_t)nb, hipMemcpyHostToDevice, st));
+  }
+  if ((rc = dm_match_launch_scans(g, S, N, A, k0, sub, half, stride))) return rc;
+  std::vector<int32_t> res(5 * (size_t)S);
+  DM_HIP(hipMemcpyAsync(res.data(), g->match_out, sizeof(int32_t) * res.size(), hipMemcpyDeviceToHost, st));
+  if (out_volume)
+    DM_HIP(hipMemcpyAsync(out_volume, g->match_vol, sizeof(uint32_t) * (size_t)(SA * T), hipMemcpyDeviceToHost, st));
+  DM_HIP(hipStreamSynchronize(st));
+  for (int32_t s = 0; s < S; ++s) {
+    const int32_t k = res[4 * (size_t)s], i = res[4 * (size_t)s + 1], j = res[4 * (size_t)s + 2];
+    out_best[3 * s] = k;
+    out_best[3 * s + 1] = i;
+    out_best[3 * s + 2] = j;
+    out_score[s] = (uint32_t)res[4 * (size_t)s + 3];
+    out_n_used[s] = res[4 * (size_t)S + s];
+    out_pose[3 * s] = poses[3 * s] + (double)(i * stride) * step;
+    out_pose[3 * s + 1] = poses[3 * s + 1] + (double)(j * stride) * step;
+    out_pose[3 * s + 2] = poses[3 * s + 2] + yaw_offsets[k];
+  }
   return DM_OK;
 }
 

@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "dm_internal.h"
+#include "dm_match.h"
 #include "dm_plan.h"
 
 namespace {
@@ -313,6 +314,62 @@ int dm_plan_launch_path(dm_grid* g, const int64_t* d_start, int64_t cap) {
   dm_timer_begin(g, "plan_path", &t);
   hipLaunchKernelGGL(dm_plan::k_plan_path, dim3(1), dim3(64), 0, g->stream, g->plan_cost, g->plan_travs, g->W,
                      g->H, g->TX, d_start, g->plan_path, cap, g->plan_stat + 4);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  return DM_OK;
+}
+
+// ---- scan matcher (dm_match.h) ------------------------------------------------
+
+int dm_match_launch_field(dm_grid* g, int32_t n_tiles, int32_t r, bool mono) {
+  if (n_tiles <= 0) return DM_OK;
+  KernelTimer t;
+  dm_timer_begin(g, "match_field", &t);
+  hipLaunchKernelGGL(dm_match::k_match_field, dim3((unsigned)n_tiles), dim3(dm_match::kThreads), 0, g->stream,
+                     g->state, g->tile_seen, g->W, g->H, g->TX, r, g->match_kern, mono ? 1 : 0, g->match_tiles,
+                     g->match_V);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  return DM_OK;
+}
+
+int dm_match_launch_scans(dm_grid* g, int32_t S, int32_t N, int32_t A, int32_t k0, int32_t sub, int32_t half,
+                          int32_t stride) {
+  using namespace dm_match;
+  hipStream_t s = g->stream;
+  const int64_t SA = (int64_t)S * A, T = (int64_t)(2 * half + 1) * (2 * half + 1);
+  int32_t* d_used = g->match_out + 4 * (int64_t)S;
+  DM_HIP(hipMemsetAsync(d_used, 0, sizeof(int32_t) * (size_t)S, s));
+  DM_HIP(hipMemsetAsync(g->match_vol, 0, sizeof(uint32_t) * (size_t)(SA * T), s));
+  KernelTimer t;
+  if (N > 0) {
+    MatchArgs a;
+    a.N = N;
+    a.ox = g->p.origin_x;
+    a.oy = g->p.origin_y;
+    a.step = g->p.resolution / (double)sub;
+    a.range_min = g->p.range_min;
+    a.range_max = g->p.range_max;
+    dm_timer_begin(g, "match_prep", &t);
+    hipLaunchKernelGGL(k_match_prep, dim3((unsigned)SA, (unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       s, a, g->match_pose4, g->match_ranges, g->match_trig, A, k0, g->match_q, d_used);
+    DM_HIP(hipGetLastError());
+    dm_timer_end(g, &t);
+    // beam chunks: at least what one workgroup's LDS stage holds; more (down
+    // to 32 beams each) while the candidate yaws alone leave the chip idle
+    const int64_t want = (2048 + SA - 1) / SA;
+    int64_t chunks = std::max<int64_t>((N + kBeamsPerChunk - 1) / kBeamsPerChunk,
+                                       std::min<int64_t>(want, (N + 31) / 32));
+    const int32_t chunk_len = (int32_t)((N + chunks - 1) / chunks);
+    chunks = (N + chunk_len - 1) / chunk_len;
+    dm_timer_begin(g, "match_score", &t);
+    hipLaunchKernelGGL(k_match_score, dim3((unsigned)SA, (unsigned)chunks), dim3(kThreads), 0, s, g->match_q, N,
+                       chunk_len, g->match_V, g->W, g->H, sub, half, stride, g->match_vol);
+    DM_HIP(hipGetLastError());
+    dm_timer_end(g, &t);
+  }
+  dm_timer_begin(g, "match_best", &t);
+  hipLaunchKernelGGL(k_match_best, dim3((unsigned)S), dim3(kThreads), 0, s, g->match_vol, A, half, k0, g->match_out);
   DM_HIP(hipGetLastError());
   dm_timer_end(g, &t);
   return DM_OK;

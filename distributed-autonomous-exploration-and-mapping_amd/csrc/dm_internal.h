@@ -499,6 +499,32 @@ struct dm_grid {
   // overrides the relaxation's round bound; 0: the derived bound
   int64_t plan_max_rounds = 0;
 
+  // scan matcher (dm_match.h; dm_match_field and dm_match_scans), allocated
+  // on first use.  match_V is the response field of (match_r, match_kern_h)
+  // on map version match_version, built for the tiles flagged in match_built
+  // only: a call builds the tiles its search windows reach and are not built
+  // yet, so the fine stage of a two-stage match reuses the coarse stage's.
+  uint8_t* match_V = nullptr;         // [H][W] row-major
+  uint8_t* match_kern = nullptr;      // [16 * 16 + 1] the smear table
+  int32_t* match_tiles = nullptr;     // [NT] tiles to build
+  std::vector<uint8_t> match_built;   // [NT] host flags
+  std::vector<uint8_t> match_kern_h;  // the table match_V was built from
+  int32_t match_r = -1;
+  uint64_t match_version = 0;
+  // per-call scratch, grown on demand
+  double* match_pose4 = nullptr;      // [S * A][4] x, y, cos, sin of every candidate yaw
+  int64_t match_pose_cap = 0;
+  double* match_trig = nullptr;       // [N][2] cos, sin of the beam angles
+  int64_t match_trig_cap = 0;
+  float* match_ranges = nullptr;      // [S][N]
+  int64_t match_ranges_cap = 0;
+  int2* match_q = nullptr;            // [S * A][N] fine coordinates
+  int64_t match_q_cap = 0;
+  uint32_t* match_vol = nullptr;      // [S][A][2 half + 1][2 half + 1] scores
+  int64_t match_vol_cap = 0;
+  int32_t* match_out = nullptr;       // [S][4] k, i, j, score, then [S] used beams
+  int64_t match_out_cap = 0;
+
   // profiling
   bool profile = false;
   std::vector<KernelTimer> pending;
@@ -679,6 +705,14 @@ int dm_plan_launch_query(dm_grid* g, const double* d_xy, int64_t stride, int64_t
 // word go to g->plan_stat[4], [5]
 int dm_plan_launch_path(dm_grid* g, const int64_t* d_start, int64_t cap);
 int dm_launch_goal_gather(dm_grid* g, const dm_cluster* d_recs, const int64_t* d_idx, int32_t R, double* d_xy);
+// scan matcher (dm_match.h, launched from dm_goals.hip); the match_* arrays of
+// the handle are allocated by the caller (dm_api.cpp)
+// the response field of the first n_tiles tiles of g->match_tiles into g->match_V
+int dm_match_launch_field(dm_grid* g, int32_t n_tiles, int32_t r, bool mono);
+// fine coordinates (g->match_q, used beams at g->match_out + 4 S), the score
+// volume (g->match_vol) and the best candidates (g->match_out) of S scans
+int dm_match_launch_scans(dm_grid* g, int32_t S, int32_t N, int32_t A, int32_t k0, int32_t sub, int32_t half,
+                          int32_t stride);
 int dm_launch_ld06(dm_grid* g, int32_t S, const dm_ld06_point* d_pts, const int64_t* d_offsets,
                    int32_t N, int dir, float* d_ranges, float* d_intensities);
 

@@ -351,3 +351,43 @@ DM_HD inline SplitPart dm_split_part(int32_t len, int32_t f, int32_t part, float
   s.n = left < 0 ? 0 : (left < plen ? left : plen);
   return s;
 }
+
+// ---- scan matcher (dm_match.h; SPEC: dm_match_scans in include/dm.h) --------
+// Fine coordinates of one beam's endpoint for one candidate yaw: the grid of
+// step = resolution / sub metres with the map's origin.
+struct MatchArgs {
+  int32_t N;
+  double ox, oy, step;
+  float range_min, range_max;
+};
+
+// pose4 = (x, y, cos, sin) of the candidate yaw, trig = (cos, sin) of the
+// beam angle, both from the host C library.  The endpoint is dm_make_beam's,
+// product by product; the matcher scores hits only, so a beam is used iff
+// range_min <= r <= range_max, the pose is finite and |qx|, |qy| < 2^30.
+// Returns false (and leaves *qx, *qy alone) for a beam that is not used.
+DM_HD inline bool dm_match_endpoint(const MatchArgs& a, const double* pose4, float r, const double* trig,
+                                    int32_t* qx, int32_t* qy) {
+  const double x = pose4[0], y = pose4[1], cyaw = pose4[2], syaw = pose4[3];
+  if (!(isfinite(x) && isfinite(y) && isfinite(cyaw) && isfinite(syaw))) return false;
+  if (!(r >= a.range_min) || !(r <= a.range_max)) return false;
+  const double rr = (double)r;
+  const double cphi = trig[0], sphi = trig[1];
+  const double a1 = cyaw * cphi;
+  const double a2 = syaw * sphi;
+  const double dcx = a1 - a2;
+  const double b1 = syaw * cphi;
+  const double b2 = cyaw * sphi;
+  const double dcy = b1 + b2;
+  const double t1 = rr * dcx;
+  const double ex = x + t1;
+  const double t2 = rr * dcy;
+  const double ey = y + t2;
+  const double fx = floor((ex - a.ox) / a.step);
+  const double fy = floor((ey - a.oy) / a.step);
+  const double lim = 1073741824.0;
+  if (!(fabs(fx) < lim && fabs(fy) < lim)) return false;
+  *qx = (int32_t)fx;
+  *qy = (int32_t)fy;
+  return true;
+}

@@ -337,6 +337,74 @@ class OccupancyMapper:
         return [(int(i), (float(p[0]), float(p[1])), int(c)) if i >= 0 else None
                 for i, p, c in zip(idx, out, cell)]
 
+    # -- scan matching (csrc/dm_match.h; host restatement: dm/match.py) ----
+    def match_field(self, smear_cells: int, kern) -> np.ndarray:
+        """The matcher's response field (dm_match_field): uint8 [rows, W], per
+        cell the largest kern[d2] over the occupied cells within smear_cells
+        of it.  kern: uint8 [smear_cells**2 + 1] (dm.match.kernel_table)."""
+        kern = None if kern is None else np.ascontiguousarray(kern, dtype=np.uint8).reshape(-1)
+        if kern is not None and 0 <= int(smear_cells) <= 16 and kern.shape[0] < int(smear_cells) ** 2 + 1:
+            raise DmError(_ffi.DM_ERR_INVALID_ARG, "kern needs smear_cells**2 + 1 entries")
+        out = np.empty((self.rows, self.width), np.uint8)
+        with self._lock:
+            check(self._lib.dm_match_field(self._handle(), int(smear_cells), _vp(kern), _vp(out)))
+        return out
+
+    def match_scans(self, poses, ranges, angle_min, angle_increment, yaw_offsets, k0: int, sub: int, half: int,
+                    stride: int, smear_cells: int, kern, want_volume: bool = False) -> dict:
+        """One stage of the correlative matcher on the device (dm_match_scans)
+        for S scans: every candidate (yaw + yaw_offsets[k], i * stride, j *
+        stride fine steps of resolution / sub) is scored against the response
+        field of the map as it is now.  Returns best int32 [S, 3] = (k, i, j),
+        score uint32 [S], n_used int32 [S], pose float64 [S, 3] and, with
+        want_volume, volume uint32 [S, A, 2*half+1, 2*half+1] (k, j, i).
+        Same results as dm.match.match_scans, bit for bit."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        ranges = np.ascontiguousarray(ranges, dtype=np.float32)
+        if ranges.ndim != 2:
+            ranges = ranges.reshape(poses.shape[0], -1)
+        S, N = ranges.shape
+        off = np.ascontiguousarray(yaw_offsets, dtype=np.float64).reshape(-1)
+        A = off.shape[0]
+        kern = None if kern is None else np.ascontiguousarray(kern, dtype=np.uint8).reshape(-1)
+        if kern is not None and 0 <= int(smear_cells) <= 16 and kern.shape[0] < int(smear_cells) ** 2 + 1:
+            raise DmError(_ffi.DM_ERR_INVALID_ARG, "kern needs smear_cells**2 + 1 entries")
+        T1 = 2 * min(max(int(half), 0), 32) + 1
+        best = np.zeros((S, 3), np.int32)
+        score = np.zeros(S, np.uint32)
+        n_used = np.zeros(S, np.int32)
+        pose = np.zeros((S, 3), np.float64)
+        vol = np.zeros((S, max(A, 1), T1, T1), np.uint32) if want_volume else None
+        with self._lock:
+            check(self._lib.dm_match_scans(self._handle(), S, _vp(poses), N, _vp(ranges), float(angle_min),
+                                           float(angle_increment), A, _vp(off), int(k0), int(sub), int(half),
+                                           int(stride), int(smear_cells), _vp(kern), _vp(best), _vp(score),
+                                           _vp(n_used), _vp(pose), _vp(vol)))
+        out = {"best": best, "score": score, "n_used": n_used, "pose": pose}
+        if want_volume:
+            out["volume"] = vol
+        return out
+
+    def match_scan(self, scan, pose, slam=None) -> dict:
+        """Correct the prior pose (x, y, yaw) of one LaserScan-like message
+        against the map: the two-stage search this build derives from
+        slam_toolbox's matcher settings (dm.match.search_params documents the
+        mapping; `slam`: a SlamParams or None for slam_config.yaml's values),
+        each stage one dm_match_scans call.  Returns dm.match.two_stage's
+        dict: pose, response = score / (255 * n_used), score, n_used, coarse,
+        fine."""
+        from . import match
+
+        ranges = np.asarray(scan.ranges, dtype=np.float32)[None, :]
+        amin, inc = np.float32(scan.angle_min), np.float32(scan.angle_increment)
+
+        def match_one(p, yaw_offsets, k0, sub, half, stride, smear_cells, kern):
+            return match.first_scan(self.match_scans([p], ranges, amin, inc, yaw_offsets, k0, sub, half, stride,
+                                                     smear_cells, kern))
+
+        with self._lock:  # both stages against one map
+            return match.two_stage_with(match_one, pose, slam, float(self.params.resolution))
+
     # -- frontiers --------------------------------------------------------
     def frontiers(self, want_mask=False, want_labels=False, cap=None) -> Frontiers:
         """Frontier mask / labels (optional dense copies) and the cluster

@@ -31,6 +31,12 @@ callback signatures:
   and RViz's "2D Goal Pose" use) — the map-based replacement of the reactive
   IR/LiDAR policy (main.py:123-188) that the report lists as future work
   (report.pdf p.5 §VI-2);
+* with ``dm_scan_matching`` (default off), takes the pose provider's pose as the
+  odometry pose (``odom -> base_laser``) and corrects every accepted scan
+  against the map with the device's correlative matcher (``dm_match_scans``;
+  slam_toolbox's, slam_config.yaml:35,50-53,64-66) before integrating it; the
+  correction is kept as ``map_to_odom`` and, under ROS, broadcast as
+  ``map -> odom``: the part of the TF chain slam_toolbox published;
 * with ``dm_devices`` naming several GPUs, the map is one sharded handle
   (``dm_create_sharded``: row bands over those devices, the exchange inside
   libdm) behind the same calls.
@@ -175,6 +181,7 @@ class SlamParams:
     server/thymio_project/config/slam_config.yaml as defaults (line numbers
     there), plus this build's fixed grid size and exploration switches."""
 
+    odom_frame: str = "odom"              # :16 (parent of the pose with dm_scan_matching)
     map_frame: str = "map"                # :17
     base_frame: str = "base_link"         # :18
     scan_topic: str = "/scan"             # :19
@@ -185,6 +192,15 @@ class SlamParams:
     minimum_time_interval: float = 0.5    # :28
     minimum_travel_distance: float = 0.1  # :37
     minimum_travel_heading: float = 0.1   # :38
+    # the correlative scan matcher's settings (used with dm_scan_matching)
+    use_scan_matching: bool = True                          # :35
+    link_match_minimum_response_fine: float = 0.1           # :41
+    correlation_search_space_dimension: float = 0.5         # :51
+    correlation_search_space_resolution: float = 0.01       # :52
+    correlation_search_space_smear_deviation: float = 0.1   # :53
+    fine_search_angle_offset: float = 0.00349               # :64
+    coarse_search_angle_offset: float = 0.349               # :65
+    coarse_angle_resolution: float = 0.0349                 # :66
     # this build (not slam_toolbox parameters)
     dm_width: int = 4096                  # cells; a 204.8 m square at 5 cm
     dm_height: int = 4096
@@ -201,11 +217,17 @@ class SlamParams:
     dm_goal_path_distance: bool = False
     dm_goal_inflate_m: float = 0.10       # obstacle inflation radius (the robot's)
     dm_goal_snap_m: float = 0.25          # how far a goal may move to reach a traversable cell
+    # correct every accepted scan's pose against the map on the device
+    # (dm_match_scans) and keep the correction as map -> odom; off: the pose
+    # provider's pose is taken as it is, as before.  Needs use_scan_matching
+    # too (the reference's own switch, true in its yaml).
+    dm_scan_matching: bool = False
 
     @classmethod
     def from_dict(cls, d: dict) -> "SlamParams":
         """Known keys of a ros__parameters mapping; others are ignored
-        (slam_toolbox's matcher / loop-closure settings are not this stage's)."""
+        (slam_toolbox's loop-closure and variance-penalty settings are not
+        this stage's; its correlative matcher's are, see dm_scan_matching)."""
         p = cls()
         for f in fields(cls):
             if f.name in d:
@@ -319,6 +341,20 @@ class ScanGate:
         return True
 
 
+def se2_compose(a, b):
+    """a o b for planar poses (x, y, yaw): b expressed in a's frame, in a's parent."""
+    ax, ay, at = (float(v) for v in a)
+    bx, by, bt = (float(v) for v in b)
+    c, s = math.cos(at), math.sin(at)
+    return (ax + (c * bx - s * by), ay + (s * bx + c * by), at + bt)
+
+
+def se2_inverse(a):
+    ax, ay, at = (float(v) for v in a)
+    c, s = math.cos(at), math.sin(at)
+    return (-(c * ax + s * ay), -(c * ay - s * ax), -at)
+
+
 def parse_devices(spec) -> list[int]:
     """dm_devices: "0,1,2,3" (or a list) -> [0, 1, 2, 3]; "" -> []."""
     if isinstance(spec, (list, tuple)):
@@ -349,6 +385,9 @@ class MappingNode:
         self.params = p.grid_params()
         if mapper is None:
             devices = parse_devices(p.dm_devices)
+            if len(devices) > 1 and p.dm_scan_matching and p.use_scan_matching:
+                raise ValueError("dm_scan_matching needs the whole map in one handle: it is not available "
+                                 "with a map sharded over dm_devices")
             if len(devices) > 1:
                 mapper = OccupancyMapper(self.params, devices=devices)
             else:
@@ -371,6 +410,15 @@ class MappingNode:
         self.scans_integrated = 0
         self.updates = 0
         self.last_frontiers = None
+        # dm_scan_matching: the pose provider's pose is the odometry pose and
+        # map_to_odom the correction C (x, y, yaw), identity until a match is
+        # accepted; every scan's prior is C o odom
+        self.matching = bool(p.dm_scan_matching) and bool(p.use_scan_matching)
+        self.map_to_odom = (0.0, 0.0, 0.0)
+        self.scans_matched = 0
+        self.scans_rejected = 0
+        self.last_match = None             # mapper.match_scan's result for the last matched scan
+        self.last_integrated_pose = None   # the pose the last scan was integrated at
 
     # main.py:77-78 keeps the signature scan_cb(self, msg)
     def scan_cb(self, msg):
@@ -380,13 +428,37 @@ class MappingNode:
         pose = self.pose_provider(msg) if self.pose_provider is not None else None
         if pose is None:
             return  # no transform yet: slam_toolbox drops such scans too
+        odom = tuple(float(v) for v in pose)
+        if self.matching:
+            pose = se2_compose(self.map_to_odom, odom)  # the prior
         self.latest_pose = tuple(float(v) for v in pose)
         stamp = stamp_seconds(msg.header.stamp)
         if self.gate is not None and not self.gate.accept(stamp, pose):
             return
+        if self.matching and self.scans_integrated > 0:
+            pose = self._match(msg, odom, pose)
+            self.latest_pose = pose
         u, _ = self.mapper.integrate_scan(msg, pose)
+        self.last_integrated_pose = tuple(float(v) for v in pose)
         self.updates += u
         self.scans_integrated += 1
+
+    def _match(self, msg, odom, prior):
+        """Correct an accepted scan's prior against the map (the device's
+        two-stage correlative search, OccupancyMapper.match_scan; what
+        slam_toolbox's matcher does for the reference, slam_config.yaml:35,
+        50-53, 64-66).  A response of at least link_match_minimum_response_fine
+        (:41) accepts the match: the scan is integrated at the matched pose and
+        map_to_odom becomes matched o odom^-1.  Otherwise the prior stands."""
+        res = self.mapper.match_scan(msg, prior, self.slam)
+        self.last_match = res
+        if res["response"] >= float(self.slam.link_match_minimum_response_fine):
+            matched = tuple(float(v) for v in res["pose"])
+            self.map_to_odom = se2_compose(matched, se2_inverse(odom))
+            self.scans_matched += 1
+            return matched
+        self.scans_rejected += 1
+        return tuple(float(v) for v in prior)
 
     def timer_cb(self):
         """The map_update_interval timer: publish /map and start a frontier
@@ -567,7 +639,10 @@ def main(args=None):  # pragma: no cover - needs ROS 2
 
     def lookup(msg):
         try:
-            t = tf_buffer.lookup_transform(sp.map_frame, msg.header.frame_id, msg.header.stamp)
+            # with dm_scan_matching this node publishes map -> odom itself: the
+            # pose it corrects is the laser's in the odometry frame
+            parent = sp.odom_frame if (sp.dm_scan_matching and sp.use_scan_matching) else sp.map_frame
+            t = tf_buffer.lookup_transform(parent, msg.header.frame_id, msg.header.stamp)
         except Exception:
             return None
         tr = t.transform
@@ -619,6 +694,25 @@ def main(args=None):  # pragma: no cover - needs ROS 2
     # slam_toolbox publishes the map on its own period, not per scan
     node.create_timer(sp.map_update_interval, mn.timer_cb)
     node.create_timer(0.01, mn.poll_frontiers)  # frontiers go out as soon as the GPU pass is done
+    if mn.matching:
+        # slam_toolbox's part of the TF chain map -> odom -> base_link -> base_laser
+        # (slam_config.yaml:24 transform_publish_period)
+        from geometry_msgs.msg import TransformStamped
+
+        broadcaster = tf2_ros.TransformBroadcaster(node)
+
+        def broadcast_map_to_odom():
+            x, y, yaw = mn.map_to_odom
+            t = TransformStamped()
+            t.header.stamp = node.get_clock().now().to_msg()
+            t.header.frame_id = sp.map_frame
+            t.child_frame_id = sp.odom_frame
+            t.transform.translation.x, t.transform.translation.y = x, y
+            q = quaternion_from_yaw(yaw)
+            t.transform.rotation.z, t.transform.rotation.w = q.z, q.w
+            broadcaster.sendTransform(t)
+
+        node.create_timer(0.1, broadcast_map_to_odom)
     try:
         rclpy.spin(node)
     finally:

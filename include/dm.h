@@ -250,8 +250,9 @@ int dm_set_overlap(dm_grid* g, int32_t on);
  * and merges on band 0's device (dm_merge_bands).  The multi-process building
  * blocks below (halos, edge rows / labels, exports, merges, dm_set_stream)
  * return DM_ERR_INVALID_ARG on such a handle, and so do the path planning
- * calls (dm_plan_*, dm_assign_goals_path), which need the whole map in one
- * handle: sharded planning is not implemented.  Replaces: slam_toolbox's
+ * calls (dm_plan_*, dm_assign_goals_path) and the scan matcher (dm_match_*),
+ * which need the whole map in one handle: sharded planning and matching are
+ * not implemented.  Replaces: slam_toolbox's
  * single map thread for a map too large (or too many robots) for one GPU;
  * the caller is the ROS node wired at pc_server.launch.py:12-19. */
 int dm_create_sharded(dm_grid** out, const dm_params* p, int32_t nranks, const int32_t* devices);
@@ -467,6 +468,74 @@ int dm_assign_goals_path(dm_grid* g, const double* robots_xy, int32_t n_robots, 
                          double distance_weight, double min_distance, int32_t inflate_cells,
                          uint32_t max_cost, int32_t snap_cells, int64_t* out_index, double* out_xy,
                          int64_t* out_cell);
+
+/* ---- Correlative scan matching against the device-resident map.  In the
+ * reference the pose of a scan comes from slam_toolbox's correlative scan
+ * matcher (slam_config.yaml:35 use_scan_matching; :50-53 the correlation
+ * search space, :64-66 the angle search), which corrects odometry and
+ * publishes the correction as map -> odom.  slam_toolbox is not vendored, so
+ * the definitions below are this build's SPEC (parity unpinned).  Everything
+ * is integer arithmetic or separately rounded doubles (no FMA): every result
+ * is unique and bit-exact.  Both calls are synchronous, ordered after
+ * everything enqueued on the handle, read the map as it is at the call, never
+ * write it and do not change the map version (a dm_plan_field result stays
+ * valid).  They need a handle that covers the whole map: a band handle
+ * (band_rows != height) or a dm_create_sharded handle returns
+ * DM_ERR_INVALID_ARG.
+ *
+ *   Response field, for smear_cells = r in [0, 16] and a caller-supplied table
+ *     kern[r*r + 1] of uint8: V[c] = max over in-grid cells o with
+ *     state[o] == 100 and d2 = dx*dx + dy*dy <= r*r of kern[d2]; 0 if there is
+ *     none.  Out-of-grid cells are never occupied.  The library computes no
+ *     exp; a Gaussian smear of deviation sigma is kern[d2] =
+ *     floor(255 * exp(-0.5 * d2 * resolution^2 / sigma^2) + 0.5) (dm/match.py
+ *     kernel_table).  The max holds for any table, monotone or not.
+ *   Fine coordinates, for sub in [1, 16]: step = resolution / (double)sub.
+ *     Candidate angle k has yaw + yaw_offsets[k] (one double add); its cos /
+ *     sin, and those of the beam angles, come from the host C library as in
+ *     dm_integrate.  A beam is used iff range_min <= r <= range_max (NaN and
+ *     beams past range_max are not: the matcher scores hits only).  Its
+ *     endpoint ex, ey is that of dm_integrate, product by
+ *     product; qx = floor((ex - origin_x) / step), likewise qy.  A beam of a
+ *     non-finite pose, or with |qx| or |qy| >= 2^30, is not used.
+ *     n_used[s] = the used beams of candidate k0.
+ *   Score, for translation indices i, j in [-half, half], half in [0, 32],
+ *     stride in [1, 16]: cell = (floordiv(qx + i*stride, sub),
+ *     floordiv(qy + j*stride, sub)), floor division for negative values too;
+ *     score[s][k][j][i] = sum over used beams of V[cell] as uint32, a cell
+ *     out of the grid adding 0.
+ *   Best candidate: the maximal score, ties to the lexicographically least
+ *     (i*i + j*j, |k - k0|, k, j, i); k0 in [0, A) is the caller's "no
+ *     rotation" candidate, so an empty or unknown map gives (k0, 0, 0), score 0.
+ *   Output pose: x + (double)(i*stride) * step, y + (double)(j*stride) * step,
+ *     yaw + yaw_offsets[k].
+ *   Limits: A in [1, 64]; S, N as for dm_integrate; anything outside the
+ *     limits above is DM_ERR_INVALID_ARG.
+ * The field lives on the device in the handle (allocated on first use,
+ * DM_ERR_OOM if that or the per-call scratch cannot be allocated; freed by
+ * dm_destroy).  It is kept per (map version, smear_cells, kern): a second
+ * call on an unchanged map with the same table rebuilds nothing. */
+
+/* The response field: out[height*width] row-major.  Diagnostic and test entry
+ * (like dm_plan_traversable).  Replaces the smeared correlation grid of
+ * slam_toolbox's correlative matcher (slam_config.yaml:50-53:
+ * correlation_search_space_smear_deviation). */
+int dm_match_field(dm_grid* g, int32_t smear_cells, const uint8_t* kern, uint8_t* out);
+/* Score every candidate pose of S scans and pick the best of each.  poses
+ * [S][3], ranges [S][N], angle_min, angle_increment as dm_integrate;
+ * yaw_offsets[A].  out_best: int32[S][3] = (k, i, j); out_score: uint32[S];
+ * out_n_used: int32[S]; out_pose: double[S][3]; out_volume (may be NULL):
+ * uint32[S][A][2*half+1][2*half+1], index order k, j, i.  Only the tiles the
+ * search windows reach are built into the field; only the S results cross to
+ * the host unless out_volume is asked for.  Replaces slam_toolbox's
+ * correlative scan matcher (one search stage of it; slam_config.yaml:50-53
+ * correlation_search_space_*, :64-66 fine_search_angle_offset,
+ * coarse_search_angle_offset, coarse_angle_resolution); its variance penalties
+ * and covariance are not computed, out_volume holds what they need. */
+int dm_match_scans(dm_grid* g, int32_t S, const double* poses, int32_t N, const float* ranges, float angle_min,
+                   float angle_increment, int32_t A, const double* yaw_offsets, int32_t k0, int32_t sub,
+                   int32_t half, int32_t stride, int32_t smear_cells, const uint8_t* kern, int32_t* out_best,
+                   uint32_t* out_score, int32_t* out_n_used, double* out_pose, uint32_t* out_volume);
 
 /* Measured uncontended atomic throughput of HIP device `device` (the
  * north star's "atomic throughput against MI355X peak": no vendor figure
