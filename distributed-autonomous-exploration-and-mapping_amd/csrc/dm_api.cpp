@@ -668,6 +668,8 @@ int dm_destroy(dm_grid* g) {
   dev_free(g->match_V); dev_free(g->match_kern); dev_free(g->match_tiles); dev_free(g->match_pose4);
   dev_free(g->match_trig); dev_free(g->match_ranges); dev_free(g->match_q); dev_free(g->match_vol);
   dev_free(g->match_out);
+  dev_free(g->gain_xy); dev_free(g->gain_cell); dev_free(g->gain_out); dev_free(g->gain_skip);
+  dev_free(g->gain_memo_cell); dev_free(g->gain_memo_gain);
   for (auto& w : g->iw) {
     dev_free(w.pieces); dev_free(w.hitems); dev_free(w.litems); dev_free(w.heavy_list); dev_free(w.slabs);
     dev_free(w.heavy_done); dev_free(w.tile_count); dev_free(w.tile_cur); dev_free(w.cnt); dev_free(w.sh);
@@ -1597,6 +1599,138 @@ int dm_assign_goals_path(dm_grid* g, const double* robots_xy, int32_t n_robots, 
       DM_HIP(hipMemcpy(&cell, g->plan_qcell + idx[(size_t)r], sizeof cell, hipMemcpyDeviceToHost));
       out_cell[r] = cell;
       // the centre of the snapped cell: a reachable goal, not the centroid
+      out_xy[2 * r] = g->p.origin_x + ((double)(cell % g->W) + 0.5) * g->p.resolution;
+      out_xy[2 * r + 1] = g->p.origin_y + ((double)(cell / g->W) + 0.5) * g->p.resolution;
+    }
+  }
+  memcpy(out_index, idx.data(), sizeof(int64_t) * (size_t)R);
+  return DM_OK;
+}
+
+// ---- information gain (csrc/dm_gain.h): visible-unknown counts of view
+// points, gain-scored goals ---------------------------------------------------------
+
+static int grow_gain(dm_grid* g, int64_t n) {
+  if (n <= g->gain_cap) return DM_OK;
+  g->gain_cap = 0;
+  int rc = dev_alloc(&g->gain_xy, 2 * n, "view points");
+  if (!rc) rc = dev_alloc(&g->gain_cell, n, "view cells");
+  if (!rc) rc = dev_alloc(&g->gain_out, n, "view gains");
+  if (!rc) rc = dev_alloc(&g->gain_skip, n, "view skip flags");
+  if (!rc) rc = dev_alloc(&g->gain_memo_cell, n, "gain memo cells");
+  if (!rc) rc = dev_alloc(&g->gain_memo_gain, n, "gain memo gains");
+  if (!rc) g->gain_cap = n;
+  return rc;
+}
+
+static int gain_check_radius(int32_t radius_cells) {
+  if (radius_cells < 1 || radius_cells > 511)
+    return dm_set_error(DM_ERR_INVALID_ARG, "radius_cells must be in [1, 511] (got %d)", radius_cells);
+  return DM_OK;
+}
+
+int dm_gain_views(dm_grid* g, const double* views_xy, int64_t n, int32_t radius_cells, uint32_t* out_gain,
+                  int64_t* out_cell) {
+  int rc = plan_check_handle(g, "dm_gain_views");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n < 0 || n > (1ll << 20))
+    return dm_set_error(DM_ERR_INVALID_ARG, "n must be in [0, 2^20] (got %lld)", (long long)n);
+  if (n > 0 && (!views_xy || !out_gain || !out_cell))
+    return dm_set_error(DM_ERR_INVALID_ARG, "views_xy / out_gain / out_cell is NULL");
+  if ((rc = gain_check_radius(radius_cells))) return rc;
+  if (n == 0) return DM_OK;
+  if ((rc = grow_gain(g, n))) return rc;
+  DM_HIP(dm_sync_all(g));  // after everything enqueued on the handle, on every stream of it
+  DM_HIP(hipMemcpyAsync(g->gain_xy, views_xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, g->stream));
+  if ((rc = dm_gain_launch_cells(g, n))) return rc;
+  if ((rc = dm_gain_launch_views(g, g->gain_cell, nullptr, n, radius_cells, false))) return rc;
+  DM_HIP(hipMemcpyAsync(out_gain, g->gain_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipMemcpyAsync(out_cell, g->gain_cell, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  return DM_OK;
+}
+
+int dm_assign_goals_gain(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size, int64_t min_gain,
+                         double distance_weight, double min_distance, int32_t inflate_cells, uint32_t max_cost,
+                         int32_t snap_cells, int32_t radius_cells, int64_t* out_index, double* out_xy,
+                         int64_t* out_cell, uint32_t* out_gain) {
+  int rc = plan_check_handle(g, "dm_assign_goals_gain");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n_robots < 0 || n_robots > 256)
+    return dm_set_error(DM_ERR_INVALID_ARG, "n_robots must be in [0, 256] (got %d)", n_robots);
+  if (n_robots > 0 && (!robots_xy || !out_index || !out_xy || !out_cell || !out_gain))
+    return dm_set_error(DM_ERR_INVALID_ARG, "robots_xy / out_index / out_xy / out_cell / out_gain is NULL");
+  if (!isfinite(distance_weight) || !isfinite(min_distance))
+    return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight / min_distance must be finite");
+  if (distance_weight < 0.0)  // as dm_assign_goals: the device ranks by the util's IEEE bits
+    return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight must be >= 0");
+  if (min_gain < 0) return dm_set_error(DM_ERR_INVALID_ARG, "min_gain must be >= 0 (got %lld)", (long long)min_gain);
+  if ((rc = plan_check_inflate(inflate_cells)) || (rc = plan_check_snap(snap_cells)) ||
+      (rc = gain_check_radius(radius_cells)))
+    return rc;
+  const int s = g->goal_slot;
+  if (s < 0 || g->goal_gen != g->rb_gen ||
+      (g->goal_kind == 1 ? g->rb[s].wepoch : g->rb[s].mepoch) != g->goal_epoch)
+    return dm_set_error(DM_ERR_INVALID_ARG, "no collected frontier result on the device (call dm_frontiers, "
+                                            "dm_frontiers_end or dm_merge_bands first; a later pass may have "
+                                            "reused its readback slot)");
+  if (n_robots == 0) return DM_OK;
+  for (int32_t r = 0; r < n_robots; ++r) {
+    int64_t c;
+    if (!plan_cell_of(g, robots_xy[2 * r], robots_xy[2 * r + 1], &c))
+      return dm_set_error(DM_ERR_INVALID_ARG, "robot %d (%g, %g) is outside the grid", r, robots_xy[2 * r],
+                          robots_xy[2 * r + 1]);
+  }
+  const dm_cluster* recs = g->goal_kind == 1 ? g->rb[s].out_clu : g->rb[s].m_out;
+  const int64_t K = g->goal_n;
+  if ((rc = ensure_plan(g)) || (rc = grow_plan_query(g, std::max<int64_t>(K, 1))) ||
+      (rc = grow_gain(g, std::max<int64_t>(K, 1))))
+    return rc;
+  DM_HIP(dm_join_pass_stream(g));
+  if ((rc = dm_plan_launch_travers(g, inflate_cells))) return rc;
+  // the memo of this call: no cluster has a cast yet (every byte 0xFF: cell -1,
+  // which no cast view has)
+  if (K > 0) DM_HIP(hipMemsetAsync(g->gain_memo_cell, 0xFF, sizeof(int64_t) * (size_t)K, g->stream));
+  const int32_t R = n_robots, T = n_robots;
+  std::vector<int64_t> idx((size_t)R, -1);
+  std::vector<unsigned long long> hk((size_t)T);
+  std::vector<uint32_t> hi((size_t)T);
+  for (int32_t r = 0; r < R; ++r) {
+    // robot r's field, its path cost to every cluster's snapped centroid, then
+    // the gain of every snapped cell that can still be a goal
+    if ((rc = plan_field_from(g, robots_xy + 2 * r, 1, max_cost, nullptr))) return rc;
+    out_cell[r] = -1;
+    out_gain[r] = 0u;
+    out_xy[2 * r] = out_xy[2 * r + 1] = NAN;
+    if (K == 0) continue;
+    if ((rc = dm_plan_launch_query(g, &recs[0].cx_m, (int64_t)(sizeof(dm_cluster) / sizeof(double)), K, snap_cells,
+                                   g->plan_qcost, g->plan_qcell)))
+      return rc;
+    if ((rc = dm_gain_launch_skip(g, recs, g->plan_qcost, K, min_size))) return rc;
+    if ((rc = dm_gain_launch_views(g, g->plan_qcell, g->gain_skip, K, radius_cells, true))) return rc;
+    const unsigned long long* dk = nullptr;
+    const uint32_t* di = nullptr;
+    if ((rc = dm_launch_goal_topk(g, recs, K, nullptr, 1, T, min_size, distance_weight, min_distance, &dk, &di,
+                                  g->plan_qcost, g->gain_out, min_gain)))
+      return rc;
+    DM_HIP(hipMemcpyAsync(hk.data(), dk, sizeof(unsigned long long) * (size_t)T, hipMemcpyDeviceToHost, g->stream));
+    DM_HIP(hipMemcpyAsync(hi.data(), di, sizeof(uint32_t) * (size_t)T, hipMemcpyDeviceToHost, g->stream));
+    DM_HIP(hipStreamSynchronize(g->stream));
+    // greedy in robot order, as dm_assign_goals_path
+    for (int32_t t = 0; t < T; ++t) {
+      if (hk[(size_t)t] == 0ull) break;
+      const int64_t c = hi[(size_t)t];
+      if (std::find(idx.begin(), idx.begin() + r, c) != idx.begin() + r) continue;
+      idx[(size_t)r] = c;
+      break;
+    }
+    if (idx[(size_t)r] >= 0) {
+      int64_t cell = -1;
+      uint32_t gain = 0u;
+      DM_HIP(hipMemcpy(&cell, g->plan_qcell + idx[(size_t)r], sizeof cell, hipMemcpyDeviceToHost));
+      DM_HIP(hipMemcpy(&gain, g->gain_out + idx[(size_t)r], sizeof gain, hipMemcpyDeviceToHost));
+      out_cell[r] = cell;
+      out_gain[r] = gain;
       out_xy[2 * r] = g->p.origin_x + ((double)(cell % g->W) + 0.5) * g->p.resolution;
       out_xy[2 * r + 1] = g->p.origin_y + ((double)(cell / g->W) + 0.5) * g->p.resolution;
     }

@@ -17,6 +17,7 @@
 // "smaller label" is "smaller record index".
 #include <algorithm>
 
+#include "dm_gain.h"
 #include "dm_internal.h"
 #include "dm_match.h"
 #include "dm_plan.h"
@@ -59,13 +60,19 @@ __device__ inline void goal_sort(unsigned long long* s_k, uint32_t* s_i) {
 // cluster's snapped centroid, cost_rows[r][c] * res / 5 (two rounded
 // operations), and a cluster that is not reached is not eligible; `robots`
 // is not read.
-template <bool kPath>
+// kGain (dm_assign_goals_gain, with kPath): the numerator is the cluster's
+// visible-unknown count gain_row[c] in place of its size, and a cluster with
+// gain < min_gain is not eligible; a gain of 0 gives util 0, the key of "not
+// eligible".
+template <bool kPath, bool kGain>
 __global__ __launch_bounds__(kGoalThreads) void k_goal_topk(const dm_cluster* __restrict__ recs, int64_t K,
                                                             const double* __restrict__ robots, int32_t T,
                                                             int64_t min_size, double w, double min_dist,
                                                             unsigned long long* __restrict__ out_k,
                                                             uint32_t* __restrict__ out_i,
-                                                            const uint32_t* __restrict__ cost_rows, double res) {
+                                                            const uint32_t* __restrict__ cost_rows, double res,
+                                                            const uint32_t* __restrict__ gain_row,
+                                                            int64_t min_gain) {
   __shared__ unsigned long long s_k[kGoalN];
   __shared__ uint32_t s_i[kGoalN];
   const int64_t chunk = blockIdx.x, r = blockIdx.y, nch = gridDim.x;
@@ -85,8 +92,10 @@ __global__ __launch_bounds__(kGoalThreads) void k_goal_topk(const dm_cluster* __
         const double dx = q.cx_m - rx, dy = q.cy_m - ry;
         dist = __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
       }
-      if (reached && q.size >= min_size && dist >= min_dist) {
-        const double util = __ddiv_rn((double)q.size, __dadd_rn(1.0, __dmul_rn(w, dist)));
+      const uint32_t gain = kGain ? gain_row[c] : 0u;
+      if (reached && q.size >= min_size && dist >= min_dist && (!kGain || (int64_t)gain >= min_gain)) {
+        const double num = kGain ? (double)gain : (double)q.size;
+        const double util = __ddiv_rn(num, __dadd_rn(1.0, __dmul_rn(w, dist)));
         key = (unsigned long long)__double_as_longlong(util);
       }
     }
@@ -150,10 +159,12 @@ int dm_launch_goal_gather(dm_grid* g, const dm_cluster* d_recs, const int64_t* d
 // Top-T lists of R robots over K label-sorted records; on return *d_k / *d_i
 // point at the final [R][T] lists (in g->goal_* workspace).  T <= 256.
 // d_cost: [R][K] path costs in place of the Euclidean distance (d_robots is
-// then not read), or nullptr.
+// then not read), or nullptr.  d_gain (with d_cost, R == 1): [K] gains, the
+// numerator in place of the size, with min_gain; or nullptr.
 int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, const double* d_robots, int32_t R,
                         int32_t T, int64_t min_size, double w, double min_dist,
-                        const unsigned long long** d_k, const uint32_t** d_i, const uint32_t* d_cost) {
+                        const unsigned long long** d_k, const uint32_t** d_i, const uint32_t* d_cost,
+                        const uint32_t* d_gain, int64_t min_gain) {
   const int64_t nch = (K + kGoalN - 1) / kGoalN;
   const int64_t need = (int64_t)R * std::max<int64_t>(nch, 1) * T;
   if (need > g->goal_cap) {
@@ -174,12 +185,17 @@ int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, const d
   KernelTimer t;
   dm_timer_begin(g, "goal_topk", &t);
   const dim3 tgrid((unsigned)std::max<int64_t>(nch, 1), (unsigned)R);
-  if (d_cost)
-    hipLaunchKernelGGL(k_goal_topk<true>, tgrid, dim3(kGoalThreads), 0, g->stream, d_recs, K, d_robots, T, min_size,
-                       w, min_dist, g->goal_k[0], g->goal_i[0], d_cost, g->p.resolution);
+  const uint32_t* const no_row = nullptr;
+  if (d_cost && d_gain)
+    hipLaunchKernelGGL((k_goal_topk<true, true>), tgrid, dim3(kGoalThreads), 0, g->stream, d_recs, K, d_robots, T,
+                       min_size, w, min_dist, g->goal_k[0], g->goal_i[0], d_cost, g->p.resolution, d_gain, min_gain);
+  else if (d_cost)
+    hipLaunchKernelGGL((k_goal_topk<true, false>), tgrid, dim3(kGoalThreads), 0, g->stream, d_recs, K, d_robots, T,
+                       min_size, w, min_dist, g->goal_k[0], g->goal_i[0], d_cost, g->p.resolution, no_row,
+                       (int64_t)0);
   else
-    hipLaunchKernelGGL(k_goal_topk<false>, tgrid, dim3(kGoalThreads), 0, g->stream, d_recs, K, d_robots, T,
-                       min_size, w, min_dist, g->goal_k[0], g->goal_i[0], (const uint32_t*)nullptr, 0.0);
+    hipLaunchKernelGGL((k_goal_topk<false, false>), tgrid, dim3(kGoalThreads), 0, g->stream, d_recs, K, d_robots, T,
+                       min_size, w, min_dist, g->goal_k[0], g->goal_i[0], no_row, 0.0, no_row, (int64_t)0);
   DM_HIP(hipGetLastError());
   int64_t nl = std::max<int64_t>(nch, 1);
   const int32_t per = kGoalN / T;  // lists one merge workgroup takes (>= 16)
@@ -370,6 +386,43 @@ int dm_match_launch_scans(dm_grid* g, int32_t S, int32_t N, int32_t A, int32_t k
   }
   dm_timer_begin(g, "match_best", &t);
   hipLaunchKernelGGL(k_match_best, dim3((unsigned)S), dim3(kThreads), 0, s, g->match_vol, A, half, k0, g->match_out);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  return DM_OK;
+}
+
+// ---- information gain (dm_gain.h) ---------------------------------------------
+
+int dm_gain_launch_cells(dm_grid* g, int64_t n) {
+  if (n <= 0) return DM_OK;
+  hipLaunchKernelGGL(dm_gain::k_gain_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g->stream, g->gain_xy, n,
+                     g->W, g->H, g->p.origin_x, g->p.origin_y, g->p.resolution, g->gain_cell);
+  DM_HIP(hipGetLastError());
+  return DM_OK;
+}
+
+int dm_gain_launch_skip(dm_grid* g, const dm_cluster* d_recs, const uint32_t* d_cost, int64_t K, int64_t min_size) {
+  if (K <= 0) return DM_OK;
+  hipLaunchKernelGGL(dm_gain::k_gain_skip, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, g->stream, d_recs, d_cost,
+                     K, min_size, g->gain_skip);
+  DM_HIP(hipGetLastError());
+  return DM_OK;
+}
+
+int dm_gain_launch_views(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R, bool memo) {
+  using namespace dm_gain;
+  if (n <= 0) return DM_OK;
+  const size_t bytes = sizeof(uint32_t) * (size_t)bitmap_words(R);
+  int64_t* const mc = memo ? g->gain_memo_cell : nullptr;
+  uint32_t* const mg = memo ? g->gain_memo_gain : nullptr;
+  KernelTimer t;
+  dm_timer_begin(g, "gain_views", &t);
+  if (bytes <= (size_t)kDynBytes)
+    hipLaunchKernelGGL(k_gain_views<false>, dim3((unsigned)n), dim3(kThreads), bytes, g->stream, g->state,
+                       (int32_t)g->W, (int32_t)g->H, d_cell, d_skip, R, mc, mg, g->gain_out);
+  else
+    hipLaunchKernelGGL(k_gain_views<true>, dim3((unsigned)n), dim3(kThreads), 0, g->stream, g->state, (int32_t)g->W,
+                       (int32_t)g->H, d_cell, d_skip, R, mc, mg, g->gain_out);
   DM_HIP(hipGetLastError());
   dm_timer_end(g, &t);
   return DM_OK;

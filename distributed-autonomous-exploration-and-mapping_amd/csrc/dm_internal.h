@@ -525,6 +525,16 @@ struct dm_grid {
   int32_t* match_out = nullptr;       // [S][4] k, i, j, score, then [S] used beams
   int64_t match_out_cap = 0;
 
+  // information gain (dm_gain.h; dm_gain_views and dm_assign_goals_gain),
+  // grown on demand
+  double* gain_xy = nullptr;          // [gain_cap][2] view points
+  int64_t* gain_cell = nullptr;       // [gain_cap] view cells
+  uint32_t* gain_out = nullptr;       // [gain_cap] gains (dm_assign_goals_gain: one robot's row)
+  uint8_t* gain_skip = nullptr;       // [gain_cap] views not to cast
+  int64_t* gain_memo_cell = nullptr;  // [gain_cap] per cluster: the cell of its last cast (one call)
+  uint32_t* gain_memo_gain = nullptr; // [gain_cap] and its gain
+  int64_t gain_cap = 0;
+
   // profiling
   bool profile = false;
   std::vector<KernelTimer> pending;
@@ -690,7 +700,17 @@ inline hipStream_t dm_exchange_stream_of(const dm_grid* g) { return g->overlap ?
 // goal selection (dm_goals.hip)
 int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, const double* d_robots, int32_t R,
                         int32_t T, int64_t min_size, double w, double min_dist,
-                        const unsigned long long** d_k, const uint32_t** d_i, const uint32_t* d_cost = nullptr);
+                        const unsigned long long** d_k, const uint32_t** d_i, const uint32_t* d_cost = nullptr,
+                        const uint32_t* d_gain = nullptr, int64_t min_gain = 0);
+// information gain (dm_gain.h, launched from dm_goals.hip); the gain_* arrays
+// of the handle are allocated by the caller (dm_api.cpp: grow_gain)
+// cells of n view points in g->gain_xy into g->gain_cell
+int dm_gain_launch_cells(dm_grid* g, int64_t n);
+// skip flags of K clusters (size < min_size or d_cost unreachable) into g->gain_skip
+int dm_gain_launch_skip(dm_grid* g, const dm_cluster* d_recs, const uint32_t* d_cost, int64_t K, int64_t min_size);
+// gains of n view cells into g->gain_out; d_skip and the memo (g->gain_memo_*) are optional
+int dm_gain_launch_views(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R,
+                         bool memo);
 // path planning (dm_plan.h, launched from dm_goals.hip); the plan_* arrays
 // of the handle are allocated by the caller (dm_api.cpp: ensure_plan)
 int dm_plan_launch_travers(dm_grid* g, int32_t inflate_cells);

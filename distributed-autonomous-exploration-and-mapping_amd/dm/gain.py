@@ -1,0 +1,168 @@
+"""Information gain of a viewpoint on the occupancy grid: host restatement and
+test reference of dm_gain_views and dm_assign_goals_gain (csrc/dm_gain.h), as
+dm/plan.py is for the planner.
+
+The reference explores reactively (server/thymio_project/thymio_project/
+main.py:123-188) and has no next-best-view step, so there is no reference
+behaviour to match; the definitions are this build's SPEC (include/dm.h,
+DESIGN.md §9).  They use integers only, so the results are unique.
+
+Visible-unknown count of a view cell (vx, vy) for radius_cells = R in [1, 511]:
+
+* one ray to each of the 8R offsets (ex, ey) with max(|ex|, |ey|) == R;
+* each ray is the SPEC a5 line of csrc/dm_ray.h: the major axis is x iff
+  |ex| >= |ey|, n = R, adb = min(|ex|, |ey|), and step k (0..R) is at
+  major = k * ia, minor = ib * floor((2 * k * adb + n) / (2 * n));
+* a ray is walked from k = 0 and ends before the first cell that is out of
+  the grid, has dx*dx + dy*dy > R*R, or has state 100; every cell it visits
+  before that whose state is unknown (neither 0 nor 100) is marked;
+* the gain is the number of distinct marked cells.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import plan
+
+MAX_RADIUS = 511
+MAX_VIEWS = 1 << 20
+
+
+def check_radius(R: int) -> int:
+    R = int(R)
+    if not 1 <= R <= MAX_RADIUS:
+        raise ValueError(f"radius_cells must be in [1, {MAX_RADIUS}]")
+    return R
+
+
+def ray_offsets(R: int):
+    """(ex, ey) int64 [8R]: the offsets with max(|ex|, |ey|) == R."""
+    a = np.arange(-R, R + 1, dtype=np.int64)
+    b = np.arange(-R + 1, R, dtype=np.int64)
+    ex = np.concatenate([a, a, np.full(b.shape, -R), np.full(b.shape, R)])
+    ey = np.concatenate([np.full(a.shape, -R), np.full(a.shape, R), b, b])
+    return ex, ey
+
+
+def visible_unknown(state, cell, R: int) -> int:
+    """The visible-unknown count of the view cell (vx, vy): vectorised over
+    the 8R rays, a loop over k with an alive mask."""
+    st = np.asarray(state)
+    H, W = st.shape
+    R = check_radius(R)
+    vx, vy = int(cell[0]), int(cell[1])
+    ex, ey = ray_offsets(R)
+    xmajor = np.abs(ex) >= np.abs(ey)
+    adb = np.minimum(np.abs(ex), np.abs(ey))
+    sx, sy = np.sign(ex), np.sign(ey)
+    alive = np.ones(ex.shape, bool)
+    marked = np.zeros((H, W), bool)
+    for k in range(R + 1):
+        q = (2 * k * adb + R) // (2 * R)
+        dx = np.where(xmajor, k * sx, q * sx)
+        dy = np.where(xmajor, q * sy, k * sy)
+        x, y = vx + dx, vy + dy
+        alive &= (x >= 0) & (x < W) & (y >= 0) & (y < H) & (dx * dx + dy * dy <= R * R)
+        if not alive.any():
+            break
+        xa, ya = x[alive], y[alive]
+        s = st[ya, xa]
+        blocked = s == 100
+        unknown = (s != 100) & (s != 0)
+        marked[ya[unknown], xa[unknown]] = True
+        alive[np.flatnonzero(alive)[blocked]] = False
+    return int(marked.sum())
+
+
+def gain_views(state, views_xy, origin_x: float, origin_y: float, resolution: float, radius_cells: int):
+    """dm_gain_views: (gain uint32 [n], cell int64 [n]); a view outside the
+    grid, or a non-finite one, has cell -1 and gain 0."""
+    st = np.asarray(state)
+    H, W = st.shape
+    R = check_radius(radius_cells)
+    xy = np.asarray(views_xy, np.float64).reshape(-1, 2)
+    if xy.shape[0] > MAX_VIEWS:
+        raise ValueError(f"at most {MAX_VIEWS} views")
+    gain = np.zeros(xy.shape[0], np.uint32)
+    cells = np.full(xy.shape[0], -1, np.int64)
+    memo: dict = {}
+    for i, (x, y) in enumerate(xy):
+        c = plan.cell_of(float(x), float(y), origin_x, origin_y, resolution, W, H)
+        if c is None:
+            continue
+        cells[i] = c[1] * W + c[0]
+        if c not in memo:
+            memo[c] = visible_unknown(st, c, R)
+        gain[i] = memo[c]
+    return gain, cells
+
+
+def default_radius(range_max: float, resolution: float) -> int:
+    """ceil(range_max / resolution), capped at the limit."""
+    return max(1, min(MAX_RADIUS, int(math.ceil(float(range_max) / float(resolution)))))
+
+
+def assign_goals_gain(state, clusters: np.ndarray, robots_xy, origin_x: float, origin_y: float, resolution: float,
+                      min_size: int = 8, min_gain: int = 0, distance_weight: float = 1.0, min_distance: float = 0.0,
+                      inflate_cells: int = 2, max_cost: int = 0, snap_cells: int = 5, radius_cells: int = 240,
+                      cache: dict | None = None):
+    """dm.plan.assign_goals_path with the visible-unknown count of the snapped
+    cell as the numerator of the utility: per robot, in order, (cluster index,
+    (x, y) centre of the snapped cell, snapped cell, gain) or None.  A cluster
+    is eligible iff size >= min_size, it is reached, dist >= min_distance and
+    gain >= min_gain; util = gain / (1 + distance_weight * dist), and a gain of
+    0 is never a goal.  `cache`: as for assign_goals_path (the per-robot
+    fields, keyed by the robot's cell); the gains of the view cells are kept in
+    it too, under ("gain", radius, cell)."""
+    if not float(distance_weight) >= 0.0:
+        raise ValueError("distance_weight must be >= 0 (dm_assign_goals_gain rejects it too)")
+    if int(min_gain) < 0:
+        raise ValueError("min_gain must be >= 0")
+    R = check_radius(radius_cells)
+    st = np.asarray(state)
+    H, W = st.shape
+    robots = [(float(x), float(y)) for x, y in robots_xy]
+    cells = [plan.cell_of(x, y, origin_x, origin_y, resolution, W, H) for x, y in robots]
+    if any(c is None for c in cells):
+        raise ValueError("a robot is outside the grid")
+    if clusters is None or len(clusters) == 0:
+        return [None] * len(robots)
+    trav = plan.traversable(st, inflate_cells)
+    targets = [plan.cell_of(float(c["cx_m"]), float(c["cy_m"]), origin_x, origin_y, resolution, W, H)
+               for c in clusters]
+    gains: dict = cache if cache is not None else {}
+    taken = np.zeros(len(clusters), bool)
+    out = []
+    for rc in cells:
+        f = cache.get(rc) if cache is not None else None
+        if f is None:
+            f = plan.field(st, [rc], inflate_cells, max_cost, trav=trav)
+            if cache is not None:
+                cache[rc] = f
+        snapped = [plan.snap(f, t, snap_cells) for t in targets]
+        cost = np.array([s[0] for s in snapped], np.uint32)
+        dist = cost.astype(np.float64) * float(resolution) / 5.0
+        gain = np.zeros(len(clusters), np.int64)
+        for i, (_, cell) in enumerate(snapped):
+            if cell < 0:
+                continue
+            key = ("gain", R, cell)
+            if key not in gains:
+                gains[key] = visible_unknown(st, (cell % W, cell // W), R)
+            gain[i] = gains[key]
+        ok = ((clusters["size"] >= min_size) & (cost != plan.UNREACHABLE) & (dist >= min_distance)
+              & (gain >= int(min_gain)) & (gain > 0) & ~taken)
+        util = np.where(ok, gain.astype(np.float64) / (1.0 + float(distance_weight) * dist), -np.inf)
+        m = util.max()
+        if not np.isfinite(m):
+            out.append(None)
+            continue
+        best = np.flatnonzero(util == m)
+        i = int(best[np.argmin(clusters["label"][best])])  # ties: the smaller label
+        taken[i] = True
+        cell = snapped[i][1]
+        xy = (origin_x + ((cell % W) + 0.5) * resolution, origin_y + ((cell // W) + 0.5) * resolution)
+        out.append((i, xy, cell, int(gain[i])))
+    return out

@@ -337,6 +337,49 @@ class OccupancyMapper:
         return [(int(i), (float(p[0]), float(p[1])), int(c)) if i >= 0 else None
                 for i, p, c in zip(idx, out, cell)]
 
+    # -- information gain (csrc/dm_gain.h; host restatement: dm/gain.py) ----
+    def default_gain_radius(self) -> int:
+        """ceil(range_max / resolution) cells, capped at the limit of 511."""
+        from .gain import default_radius
+
+        return default_radius(self.params.range_max, self.params.resolution)
+
+    def gain_views(self, views_xy, radius_cells: int | None = None):
+        """The visible-unknown count of view points (metres) on the device
+        (dm_gain_views): (gain uint32 [n], cell int64 [n]); a view outside the
+        grid, or a non-finite one, has cell -1 and gain 0.  `radius_cells`
+        defaults to the sensor's range, default_gain_radius()."""
+        xy = np.ascontiguousarray(np.asarray(views_xy, np.float64).reshape(-1, 2))
+        n = xy.shape[0]
+        R = self.default_gain_radius() if radius_cells is None else int(radius_cells)
+        gain = np.zeros(n, np.uint32)
+        cell = np.full(n, -1, np.int64)
+        with self._lock:
+            check(self._lib.dm_gain_views(self._handle(), _vp(xy), n, R, _vp(gain), _vp(cell)))
+        return gain, cell
+
+    def assign_goals_gain(self, robots_xy, min_size: int = 8, min_gain: int = 0, distance_weight: float = 1.0,
+                          min_distance: float = 0.0, inflate_cells: int = 2, max_cost: int = 0,
+                          snap_cells: int = 5, radius_cells: int | None = None):
+        """assign_goals_path scored by information gain (dm_assign_goals_gain):
+        per robot, in order, (cluster index, (x, y), cell, gain) or None, where
+        gain is the visible-unknown count of the reachable cell the cluster's
+        centroid snaps to.  Same policy as dm.gain.assign_goals_gain."""
+        xy = np.ascontiguousarray(np.asarray(robots_xy, np.float64).reshape(-1, 2))
+        R = xy.shape[0]
+        rad = self.default_gain_radius() if radius_cells is None else int(radius_cells)
+        idx = np.empty(R, np.int64)
+        out = np.empty((R, 2), np.float64)
+        cell = np.empty(R, np.int64)
+        gain = np.empty(R, np.uint32)
+        with self._lock:
+            check(self._lib.dm_assign_goals_gain(self._handle(), _vp(xy), R, int(min_size), int(min_gain),
+                                                 float(distance_weight), float(min_distance), int(inflate_cells),
+                                                 int(max_cost), int(snap_cells), rad, _vp(idx), _vp(out),
+                                                 _vp(cell), _vp(gain)))
+        return [(int(i), (float(p[0]), float(p[1])), int(c), int(gn)) if i >= 0 else None
+                for i, p, c, gn in zip(idx, out, cell, gain)]
+
     # -- scan matching (csrc/dm_match.h; host restatement: dm/match.py) ----
     def match_field(self, smear_cells: int, kern) -> np.ndarray:
         """The matcher's response field (dm_match_field): uint8 [rows, W], per

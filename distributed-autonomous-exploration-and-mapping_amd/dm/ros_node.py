@@ -217,6 +217,12 @@ class SlamParams:
     dm_goal_path_distance: bool = False
     dm_goal_inflate_m: float = 0.10       # obstacle inflation radius (the robot's)
     dm_goal_snap_m: float = 0.25          # how far a goal may move to reach a traversable cell
+    # score goals by what the sensor would see from them, the unknown cells its
+    # rays reach on the current map (dm_assign_goals_gain), in place of the
+    # frontier's size; implies dm_goal_path_distance; off: as before
+    dm_goal_information_gain: bool = False
+    dm_goal_gain_radius_m: float = float("nan")   # NaN: the map's range_max (max_laser_range)
+    dm_goal_min_gain: int = 1
     # correct every accepted scan's pose against the map on the device
     # (dm_match_scans) and keep the correction as map -> odom; off: the pose
     # provider's pose is taken as it is, as before.  Needs use_scan_matching
@@ -250,6 +256,14 @@ class SlamParams:
         inflate = int(math.ceil(float(self.dm_goal_inflate_m) / res))
         snap = int(math.ceil(float(self.dm_goal_snap_m) / res))
         return min(max(inflate, 0), 32), min(max(snap, 0), 16)
+
+    def gain_radius_cells(self) -> int:
+        """dm_goal_gain_radius_m in cells, ceil(x / resolution), clamped to the
+        C-ABI's limits [1, 511]; NaN: the map's range_max."""
+        m = float(self.dm_goal_gain_radius_m)
+        if math.isnan(m):
+            m = float(self.max_laser_range)
+        return min(max(int(math.ceil(m / float(self.resolution))), 1), 511)
 
     def grid_params(self):
         kw = dict(resolution=float(self.resolution), range_max=float(self.max_laser_range))
@@ -401,6 +415,7 @@ class MappingNode:
         self.goal_pub = goal_publisher or ListPublisher("/goal_pose")
         self.plan_pub = plan_publisher or ListPublisher("/plan")
         self.last_plan = None  # the Path of the last goal chosen by path length
+        self.last_gain = None  # the gain of the last goal chosen with dm_goal_information_gain
         self.clock = clock
         self._last_publish = -math.inf
         self._pass_stamp = None  # stamp of the frontier pass in flight (None: none)
@@ -516,7 +531,7 @@ class MappingNode:
         x, y, _ = self.latest_pose
         s = self.slam
         self.last_plan = None
-        if s.dm_goal_path_distance:
+        if s.dm_goal_path_distance or s.dm_goal_information_gain:
             return self._choose_goal_by_path(x, y, self._last_publish if stamp is None else stamp)
         g = self.mapper.assign_goals([(x, y)], min_size=s.dm_goal_min_size,
                                      distance_weight=s.dm_goal_distance_weight,
@@ -534,13 +549,23 @@ class MappingNode:
         """dm_goal_path_distance: the goal is the centre of a reachable cell,
         scored by the path length from the robot (dm_assign_goals_path), and
         the path to it (dm_plan_path over the field that call left) becomes
-        ``last_plan``, a nav_msgs/Path whose poses face along the path."""
+        ``last_plan``, a nav_msgs/Path whose poses face along the path.  With
+        dm_goal_information_gain the score's numerator is the unknown area
+        visible from that cell (dm_assign_goals_gain), kept in ``last_gain``."""
         s = self.slam
         inflate, snap = s.goal_cells()
-        g = self.mapper.assign_goals_path([(x, y)], min_size=s.dm_goal_min_size,
-                                          distance_weight=s.dm_goal_distance_weight,
-                                          min_distance=s.dm_goal_min_distance, inflate_cells=inflate,
-                                          snap_cells=snap)[0]
+        if s.dm_goal_information_gain:
+            g = self.mapper.assign_goals_gain([(x, y)], min_size=s.dm_goal_min_size,
+                                              min_gain=s.dm_goal_min_gain,
+                                              distance_weight=s.dm_goal_distance_weight,
+                                              min_distance=s.dm_goal_min_distance, inflate_cells=inflate,
+                                              snap_cells=snap, radius_cells=s.gain_radius_cells())[0]
+            self.last_gain = None if g is None else int(g[3])
+        else:
+            g = self.mapper.assign_goals_path([(x, y)], min_size=s.dm_goal_min_size,
+                                              distance_weight=s.dm_goal_distance_weight,
+                                              min_distance=s.dm_goal_min_distance, inflate_cells=inflate,
+                                              snap_cells=snap)[0]
         if g is None:
             return None
         gx, gy = g[1]

@@ -251,6 +251,7 @@ int dm_set_overlap(dm_grid* g, int32_t on);
  * blocks below (halos, edge rows / labels, exports, merges, dm_set_stream)
  * return DM_ERR_INVALID_ARG on such a handle, and so do the path planning
  * calls (dm_plan_*, dm_assign_goals_path) and the scan matcher (dm_match_*),
+ * and the information-gain calls (dm_gain_views, dm_assign_goals_gain),
  * which need the whole map in one handle: sharded planning and matching are
  * not implemented.  Replaces: slam_toolbox's
  * single map thread for a map too large (or too many robots) for one GPU;
@@ -468,6 +469,71 @@ int dm_assign_goals_path(dm_grid* g, const double* robots_xy, int32_t n_robots, 
                          double distance_weight, double min_distance, int32_t inflate_cells,
                          uint32_t max_cost, int32_t snap_cells, int64_t* out_index, double* out_xy,
                          int64_t* out_cell);
+
+/* ---- Information gain of a viewpoint on the device-resident map.  The
+ * reference has no next-best-view step: its robots move by the reactive IR /
+ * LiDAR policy of main.py:123-188.  dm_assign_goals and dm_assign_goals_path
+ * score a frontier cluster by its size, a proxy for what exploration is after;
+ * these calls count what the sensor would see from the goal: the unknown cells
+ * its rays reach on the current map before an obstacle.  Both are synchronous,
+ * ordered after everything enqueued on the handle, read the map as it is at
+ * the call (the states dm_get_state returns: 100, 0, anything else unknown),
+ * never write it and do not change the map version (a dm_plan_field result
+ * and the matcher's cached field stay valid; dm_assign_goals_gain itself
+ * leaves its last robot's field).  They need a handle that covers the whole
+ * map: a band handle (band_rows != height) or a dm_create_sharded handle
+ * returns DM_ERR_INVALID_ARG.
+ *
+ * Definition (integers only: every result is unique and bit-exact).
+ *   Visible-unknown count of a view cell (vx, vy), for radius_cells = R in
+ *     [1, 511]:
+ *   Rays: one to each of the 8R offsets (ex, ey) with max(|ex|, |ey|) == R.
+ *   Line: each ray is the integration's line from (vx, vy)
+ *     to (vx + ex, vy + ey): the major axis is x iff |ex| >= |ey|, n = R,
+ *     adb = min(|ex|, |ey|), ia / ib the signs of the major / minor offset;
+ *     step k (0..R) is at major = k * ia,
+ *     minor = ib * floor((2 * k * adb + n) / (2 * n)).
+ *   Walk: a ray is walked from k = 0 and ends before the first cell that is
+ *     out of the grid, has dx*dx + dy*dy > R*R, or has state 100.
+ *   Marking: every cell it visits before that with an unknown state is
+ *     marked.  Rays pass through unknown and free cells alike; k = 0 is the
+ *     view cell itself, so a view on an occupied cell marks nothing.
+ *   gain = the number of distinct marked cells, as uint32.
+ * The limit 511 is the largest radius whose bitmap of marked cells, 1023 rows
+ * of 32 words, fits the 160 KiB of local memory of one compute unit. */
+
+/* The gains of n view points (n in [0, 2^20]; views_xy[2i], [2i+1] metres).
+ * The cell of a point is the planner's, floor((x - origin_x) / resolution),
+ * likewise y; out_cell[i] = its linear index cy*width + cx.  A view outside
+ * the grid, or a non-finite one, gets out_cell[i] = -1 and out_gain[i] = 0.
+ * radius_cells or n out of range, or a NULL pointer with n > 0:
+ * DM_ERR_INVALID_ARG.  Replaces nothing of the reference; it is the
+ * next-best-view score of an exploration stack that takes over from the
+ * reactive policy of main.py:123-188. */
+int dm_gain_views(dm_grid* g, const double* views_xy, int64_t n, int32_t radius_cells, uint32_t* out_gain,
+                  int64_t* out_cell);
+/* dm_assign_goals_path with the information gain as the numerator of the
+ * utility.  The same: the clusters, the availability rule and the errors, the
+ * per-robot field and the snap of every centroid to it,
+ * dist = (double)cost * resolution / 5.0, the greedy robot order, ties to the
+ * smaller label, n_robots <= 256, out_index / out_xy / out_cell, and the
+ * handle's field is left as the last robot's.  What changes: for robot r and
+ * cluster c, gain(r, c) is the visible-unknown count of c's snapped cell under
+ * r's field; a cluster is eligible iff size >= min_size, it is reached,
+ * dist >= min_distance and gain >= min_gain (min_gain >= 0, a negative value:
+ * DM_ERR_INVALID_ARG); and
+ *   util = (double)gain / (1 + distance_weight * dist)
+ * as separately rounded doubles.  A gain of 0 gives util 0, which reads as
+ * "not eligible": a cluster with nothing to see is never a goal, even with
+ * min_gain = 0.  out_gain[r] = the chosen cluster's gain (0: none).  A
+ * cluster taken by an earlier robot does not discount what the others would
+ * see: overlap-aware assignment is not implemented.  Replaces the reactive
+ * policy of main.py:123-188 like dm_assign_goals, with the next-best-view
+ * score in place of the frontier's size. */
+int dm_assign_goals_gain(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size,
+                         int64_t min_gain, double distance_weight, double min_distance, int32_t inflate_cells,
+                         uint32_t max_cost, int32_t snap_cells, int32_t radius_cells, int64_t* out_index,
+                         double* out_xy, int64_t* out_cell, uint32_t* out_gain);
 
 /* ---- Correlative scan matching against the device-resident map.  In the
  * reference the pose of a scan comes from slam_toolbox's correlative scan
