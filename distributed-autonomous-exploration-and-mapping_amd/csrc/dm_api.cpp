@@ -523,6 +523,7 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   if ((rc = dev_alloc(&g->tile_seen, g->NT, "tile seen flags"))) return fail(rc);
   // The run-time switches (read once, here): DM_SPARSE_PIECES (0: no
   // sparse work items), DM_FMASK=on|off (fmask maintenance forced either way),
+  // DM_FRONTIER_CACHE=on|off (the label cache of the workgroup tile kernel),
   // DM_FRONTIER_KERNEL=wave|wg (one frontier tile kernel for every pass),
   // DM_SORT_MIN (cluster count above which the row sort runs) and
   // DM_FAULT_GATE=1 (fault injection: the front-end hand-off never arrives).
@@ -531,6 +532,9 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   if (const char* sp = getenv("DM_SPARSE_PIECES")) g->sparse_pieces = std::max(0, atoi(sp));
   const char* fm = getenv("DM_FMASK");
   g->fmask_mode = fm && !strcmp(fm, "on") ? 1 : (fm && !strcmp(fm, "off") ? 2 : 0);
+  // DM_FRONTIER_CACHE=on|off: the workgroup tile kernel's label cache (default on)
+  const char* fc = getenv("DM_FRONTIER_CACHE");
+  g->fcache_mode = fc && !strcmp(fc, "off") ? 0 : 1;
   const char* fk = getenv("DM_FRONTIER_KERNEL");
   g->frontier_kernel = fk && !strcmp(fk, "wave") ? 1 : (fk && !strcmp(fk, "wg") ? 2 : 0);
   if (const char* sm = getenv("DM_SORT_MIN")) g->sort_min = std::max<int64_t>(0, atoll(sm));
@@ -656,7 +660,7 @@ int dm_destroy(dm_grid* g) {
     dev_free(f.cnt); dev_free(f.fsh); dev_free(f.big_tiles); dev_free(f.fbits);
     dev_free(f.edge_slot); dev_free(f.slot_parent);
   }
-  dev_free(g->fl_n); dev_free(g->bits_flag);
+  dev_free(g->fl_n); dev_free(g->bits_flag); dev_free(g->fcache);
   for (int i = 0; i < 2; ++i) { dev_free(g->flist[i]); dev_free(g->flist_n[i]); }
   for (int b = 0; b < 2; ++b) { dev_free(g->goal_k[b]); dev_free(g->goal_i[b]); }
   dev_free(g->goal_io); dev_free(g->goal_idx);
@@ -877,6 +881,24 @@ int dm_last_stats(dm_grid* g, uint64_t* out, int32_t cap, int32_t* n_out) {
   return DM_OK;
 }
 
+int dm_frontier_cache_stats(dm_grid* g, uint64_t* hits, uint64_t* misses) {
+  if (g && g->sh) return dm_sh_frontier_cache_stats(g, hits, misses);
+  int rc = check_grid(g);
+  if (rc || (rc = use_device(g))) return rc;
+  if (!hits || !misses) return dm_set_error(DM_ERR_INVALID_ARG, "hits or misses is NULL");
+  if (!g->fc_collected) {  // a band's export pass: its shard counters, once it is done
+    DM_HIP(dm_sync_all(g));
+    DM_HIP(hipMemcpy(g->h_sh + kShards * kShardWords, g->fsh, sizeof(unsigned long long) * kShards * kShardWords,
+                     hipMemcpyDeviceToHost));
+    g->fc_hits = dm_shard_sum(g->h_sh + kShards * kShardWords, SH_CHIT);
+    g->fc_misses = dm_shard_sum(g->h_sh + kShards * kShardWords, SH_CMISS);
+    g->fc_collected = true;
+  }
+  *hits = g->fc_hits;
+  *misses = g->fc_misses;
+  return DM_OK;
+}
+
 int dm_get_state(dm_grid* g, int8_t* out) {
   if (g && g->sh) return (out ? dm_sh_get_state(g, out) : dm_set_error(DM_ERR_INVALID_ARG, "out is NULL"));
   int rc = check_grid(g);
@@ -999,6 +1021,7 @@ int dm_frontiers_export_device(dm_grid* g, void* d_export, int64_t rec_cap) {
   hipStream_t es = g->stream;
   if ((rc = dm_enqueue_frontiers(g, false, false, g->overlap, &es))) return rc;
   if ((rc = dm_launch_export(g, es, d_export, rec_cap))) return rc;
+  g->fc_collected = false;  // no readback header: dm_frontier_cache_stats reads the shards
   if (es != g->stream) {
     // the parity set is free again, and the grid stream may use the shared
     // pass arrays, once the pass stream is past this export

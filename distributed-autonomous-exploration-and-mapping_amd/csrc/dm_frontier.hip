@@ -108,6 +108,23 @@ __device__ inline void lds_unite(int32_t* par, int32_t a, int32_t b) {
 
 constexpr int kMaxRuns = 2048;        // <= 32 runs per 64-bit row x 64 rows
 
+// Per-tile label cache: a tile's runs, unions, component
+// ranks and tile-local sums are a pure function of its 64 frontier bit rows,
+// and between two passes those rows change in a few per cent of the tiles.
+// One entry per map tile, kFcWords 64-bit words, validated by content:
+//   [0, 64)   the bit rows the entry was computed from
+//   [64]      valid (bit 0) | components << 8 | runs << 16
+//   [65, 97)  one byte per edge cell (4 sides x 64, the tail's thread order):
+//             the cell's component rank, 0xFF where it is no frontier cell
+//   [97, 159) one word per component in rank order: first cell x (6 bits),
+//             y (6), size (13), tile-local sum of x (18), sum of y (18)
+// Only k_frontier_tile_big reads and writes it, passes label one after the
+// other, and a stale entry (any other bit rows) is a miss: no bulk call has
+// to touch it.
+constexpr int kCacheRoots = 62;
+constexpr int kFcHdr = 64, kFcEdge = 65, kFcComp = 97;
+static_assert(kFcComp + kCacheRoots <= kFcWords && kCacheRoots < 0xFF, "label cache entry layout");
+
 __device__ inline uint64_t upto_mask(int p) {  // bits 0..p inclusive
   return p >= 63 ? ~0ull : ((2ull << p) - 1ull);
 }
@@ -147,6 +164,11 @@ __device__ inline int root_rank(const uint64_t* s_root, const int32_t* pre, int 
 // or only the positions bflag marks (k_frontier_bits: too run-rich for the
 // wave kernel); a workgroup then gathers the flags of its next 64 positions
 // in one load round and works through the marked ones.
+// With the label cache (fcache != nullptr) a tile whose entry holds this
+// pass's bit rows, and which writes no dense or band-edge output, skips 2-4:
+// its slots come from the entry's component words and its edge cells' slots
+// from the entry's bytes; the tail (5) is the same code.  Every other tile
+// with frontier cells runs 2-5 and then stores its entry.
 template <bool EDGE>
 __global__ __launch_bounds__(kFT, DM_FT_OCC) void k_frontier_tile_big(
     FGeom g, const uint64_t* __restrict__ fbits, const int32_t* __restrict__ bflag,
@@ -155,7 +177,7 @@ __global__ __launch_bounds__(kFT, DM_FT_OCC) void k_frontier_tile_big(
     long long* __restrict__ slot_label, int32_t* slot_parent,
     long long* __restrict__ slot_own, long long* __restrict__ slot_acc,
     uint8_t* __restrict__ mask, int32_t* __restrict__ cell_slot, int32_t* __restrict__ edge_slot,
-    unsigned long long* cnt, unsigned long long* fsh, int count_stats) {
+    unsigned long long* cnt, unsigned long long* fsh, int count_stats, uint64_t* fcache) {
   const unsigned long long stamp = cnt[CNT_STAMP];  // this pass's (k_frontier_bits)
   __shared__ uint64_t s_F[DM_TS];          // frontier bit rows
   __shared__ int32_t s_rbase[DM_TS + 1];
@@ -168,10 +190,11 @@ __global__ __launch_bounds__(kFT, DM_FT_OCC) void k_frontier_tile_big(
   __shared__ uint32_t szx[kMaxRoots], ssy[kMaxRoots];
   __shared__ int32_t nroots;
   __shared__ long long sbase;
-  const int tid = threadIdx.x, lane = __lane_id();
+  int tid = threadIdx.x;
   const int64_t nft = (int64_t)*list_n;
   const int64_t G = gridDim.x;
   __shared__ uint64_t s_todo;
+  __shared__ uint32_t s_match;  // != 0: the tile's cache entry holds this pass's bit rows
   DM_PH_INIT();
   for (int64_t kb = blockIdx.x; kb < nft; kb += bflag ? 64 * G : G) {  // one tile per workgroup at C3
   uint64_t todo = 1ull;
@@ -188,12 +211,28 @@ __global__ __launch_bounds__(kFT, DM_FT_OCC) void k_frontier_tile_big(
   while (todo) {
     const int64_t jj = bflag ? kb + (int64_t)(__ffsll((unsigned long long)todo) - 1) * G : kb;
     todo &= todo - 1;
+    // the thread index anew per tile: what is derived from it (masks, LDS
+    // addresses) is recomputed here instead of held in registers, and
+    // spilled, across the whole tile loop
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63;
     const int32_t tile = ftiles[jj];
     const uint64_t F = tid < DM_TS ? fbits[jj * DM_TS + tid] : 0ull;
     const int64_t j = tile;  // border records are indexed by tile
     DM_PH_COUNT(dm_phase_acc_frontier, 16, 1);
     const int32_t tx0 = (tile % g.TX) * DM_TS;
     const int32_t ty0 = (tile / g.TX) * DM_TS;  // band-local
+    // the tile's cache entry: wave 0 loads its header and bit rows in one
+    // round with the tile index known (tiles with band-edge rows never hit
+    // and keep none)
+    const bool dense = g.want_mask || g.want_labels;
+    const bool band_edge = ty0 == 0 || ty0 + DM_TS >= g.R;
+    uint64_t* const ent = fcache && !band_edge ? fcache + (int64_t)tile * kFcWords : nullptr;
+    uint64_t c_hdr = 0, c_F = 0;
+    if (ent && tid < DM_TS) {
+      c_hdr = ent[kFcHdr];
+      c_F = ent[tid];
+    }
     DM_PH(dm_phase_acc_frontier, 0);
     // ---- 2. runs ----------------------------------------------------------------
     int any = 0;
@@ -211,14 +250,60 @@ __global__ __launch_bounds__(kFT, DM_FT_OCC) void k_frontier_tile_big(
       }
       s_rbase[y] = incl - c;
       if (y == 63) s_rbase[DM_TS] = incl;
+      // the header's low word (valid | components << 8 | runs << 16) on a match, else 0
+      const uint64_t same = __ballot(c_F == F);
+      if (y == 0) s_match = (c_hdr & 1ull) && same == ~0ull ? (uint32_t)c_hdr : 0u;
     }
     any = __syncthreads_or(any);
+    const uint32_t c_info = s_match;
+    const bool match = c_info != 0u;
+    const bool hit = match && !dense;
     DM_PH(dm_phase_acc_frontier, 1);
     if (!any) {  // nothing to publish: the neighbours never read this tile's edges
       __syncthreads();
       DM_PH(dm_phase_acc_frontier, 8);
       continue;
     }
+    long long base = 0;
+    uint32_t c_edge = 0xFFu;
+    const long long sh0 = (long long)(blockIdx.x % kShards) * g.slot_per;
+    unsigned long long* const shard = fsh + (blockIdx.x % kShards) * kShardWords;
+    if (hit) {
+    // ---- 2-4 from the entry ----------------------------------------------------
+    // (the component words and edge bytes load while the slot atomic returns)
+    const int nr = (int)((c_info >> 8) & 0xFFu);
+    const uint64_t c_comp = tid < nr ? ent[kFcComp + tid] : 0ull;
+    c_edge = reinterpret_cast<const uint8_t*>(ent + kFcEdge)[tid];
+    if (tid == 0) {
+      sbase = (long long)atomicAdd(&shard[SH_SLOT], (unsigned long long)nr);
+      if (count_stats) {
+        atomicAdd(&shard[SH_RUNS], (unsigned long long)(c_info >> 16));
+        atomicAdd(&shard[SH_FTF], 1ull);
+      }
+      atomicAdd(&shard[SH_CHIT], 1ull);
+    }
+    __syncthreads();
+    DM_PH(dm_phase_acc_frontier, 9);
+    DM_PH_COUNT(dm_phase_acc_frontier, 18, 1);
+    DM_PH_COUNT(dm_phase_acc_frontier, 19, 1);
+    base = sbase;
+    if (tid < nr) {
+      if (base + tid >= g.slot_per) {
+        atomicOr(&cnt[CNT_OVERFLOW], kOvSlots);
+      } else {
+        const long long slot = sh0 + base + tid;
+        const long long gy = (long long)g.row0 + ty0 + (long long)((c_comp >> 6) & 63u);
+        const long long gx = (long long)tx0 + (long long)(c_comp & 63u);
+        const long long sz = (long long)((c_comp >> 12) & 0x1FFFu);
+        slot_label[slot] = gy * g.W + gx;
+        const long long sx = sz * tx0 + (long long)((c_comp >> 25) & 0x3FFFFu);
+        const long long sy = sz * ((long long)g.row0 + ty0) + (long long)((c_comp >> 43) & 0x3FFFFu);
+        slot_own[3 * slot + 0] = sz; slot_own[3 * slot + 1] = sx; slot_own[3 * slot + 2] = sy;
+        slot_acc[3 * slot + 0] = sz; slot_acc[3 * slot + 1] = sx; slot_acc[3 * slot + 2] = sy;
+      }
+    }
+    DM_PH(dm_phase_acc_frontier, 10);
+    } else {
     {  // enumerate the runs: four threads per row, each the runs starting in its 16 columns
       const int y = tid >> 2, q = tid & 3;
       const uint64_t st_all = run_starts(s_F[y]);
@@ -237,9 +322,12 @@ __global__ __launch_bounds__(kFT, DM_FT_OCC) void k_frontier_tile_big(
     for (int r = tid; r < kMaxRoots; r += kFT) { szx[r] = 0; ssy[r] = 0; }
     __syncthreads();
     const int nruns = s_rbase[DM_TS];
-    if (count_stats && tid == 0) {
-      atomicAdd(&fsh[(blockIdx.x % kShards) * kShardWords + SH_RUNS], (unsigned long long)nruns);
-      atomicAdd(&fsh[(blockIdx.x % kShards) * kShardWords + SH_FTF], 1ull);
+    if (tid == 0) {
+      if (count_stats) {
+        atomicAdd(&shard[SH_RUNS], (unsigned long long)nruns);
+        atomicAdd(&shard[SH_FTF], 1ull);
+      }
+      if (fcache) atomicAdd(&shard[SH_CMISS], 1ull);
     }
     DM_PH(dm_phase_acc_frontier, 2);
     DM_PH_COUNT(dm_phase_acc_frontier, 17, nruns);
@@ -298,9 +386,7 @@ __global__ __launch_bounds__(kFT, DM_FT_OCC) void k_frontier_tile_big(
     __syncthreads();
     DM_PH(dm_phase_acc_frontier, 5);
     // slots come from this workgroup's shard region [shard*slot_per, +slot_per)
-    if (tid == 0)
-      sbase = (long long)atomicAdd(&fsh[(blockIdx.x % kShards) * kShardWords + SH_SLOT],
-                                   (unsigned long long)nroots);
+    if (tid == 0) sbase = (long long)atomicAdd(&shard[SH_SLOT], (unsigned long long)nroots);
     for (int r = tid; r < nruns; r += kFT) {
       const int c = root_rank(s_root, s_rootpre, r_par[r]);
       const int y = r_y[r];
@@ -310,8 +396,7 @@ __global__ __launch_bounds__(kFT, DM_FT_OCC) void k_frontier_tile_big(
     }
     __syncthreads();
     DM_PH(dm_phase_acc_frontier, 6);
-    const long long base = sbase;
-    const long long sh0 = (long long)(blockIdx.x % kShards) * g.slot_per;
+    base = sbase;
     for (int r = tid; r < nruns; r += kFT) {
       if (r_par[r] != r) continue;
       const int c = root_rank(s_root, s_rootpre, r);
@@ -326,6 +411,7 @@ __global__ __launch_bounds__(kFT, DM_FT_OCC) void k_frontier_tile_big(
       const long long sy = sz * ((long long)g.row0 + ty0) + ssy[c];
       slot_own[3 * slot + 0] = sz; slot_own[3 * slot + 1] = sx; slot_own[3 * slot + 2] = sy;
       slot_acc[3 * slot + 0] = sz; slot_acc[3 * slot + 1] = sx; slot_acc[3 * slot + 2] = sy;
+    }
     }
     // ---- 5. unions across the tile's edges -------------------------------------
     // Wave w owns edge w ([0] first row, [1] last row, [2] first col, [3]
@@ -349,8 +435,14 @@ __global__ __launch_bounds__(kFT, DM_FT_OCC) void k_frontier_tile_big(
       const int y = side == 0 ? 0 : side == 1 ? 63 : pos;
       const int x = side == 0 || side == 1 ? pos : side == 2 ? 0 : 63;
       int32_t sl = -1;
-      if ((s_F[y] >> x) & 1ull) {
-        const long long v = base + root_rank(s_root, s_rootpre, r_par[run_of(s_rbase, s_F, y, x)]);
+      int crank = -1;  // component rank of this thread's edge cell
+      if (hit) {
+        if (c_edge != 0xFFu) crank = (int)c_edge;
+      } else if ((s_F[y] >> x) & 1ull) {
+        crank = root_rank(s_root, s_rootpre, r_par[run_of(s_rbase, s_F, y, x)]);
+      }
+      if (crank >= 0) {
+        const long long v = base + crank;
         sl = v < g.slot_per ? (int32_t)(sh0 + v) : -1;
       }
       const uint64_t fb = __ballot(sl >= 0);
@@ -436,9 +528,8 @@ __global__ __launch_bounds__(kFT, DM_FT_OCC) void k_frontier_tile_big(
       }
       }
     }
-    // band edge rows (cross-band merging) and optional dense outputs
-    const bool dense = g.want_mask || g.want_labels;
-    if (dense || ty0 == 0 || ty0 + DM_TS >= g.R) {
+    // band edge rows (cross-band merging) and optional dense outputs (never a hit)
+    if (dense || band_edge) {
       for (int c = tid; c < DM_TS * DM_TS; c += kFT) {
         const int y = c >> 6, x = c & 63;
         const int32_t gy = ty0 + y, gx = tx0 + x;
@@ -460,8 +551,43 @@ __global__ __launch_bounds__(kFT, DM_FT_OCC) void k_frontier_tile_big(
         }
       }
     }
-    __syncthreads();
-    DM_PH(dm_phase_acc_frontier, 7);
+    // the tile's entry, after the hand-off so that its stores are not part of
+    // what the border publish drains; a tile with more components than an
+    // entry holds only invalidates it.  (A dense-output pass whose rows match
+    // leaves the entry as it is.)
+    if (ent && !match) {
+#ifdef DM_PHASE_TIMING
+      __syncthreads();
+      DM_PH(dm_phase_acc_frontier, 7);
+#endif
+      const int nr = nroots, nruns = s_rbase[DM_TS];
+      if (nr > kCacheRoots) {
+        if (tid == 0) ent[kFcHdr] = 0ull;
+      } else {
+        if (tid < DM_TS) ent[tid] = s_F[tid];
+        {  // the edge cells' component ranks, in the tail's thread order
+          const int side = tid >> 6;
+          const int y = side == 0 ? 0 : side == 1 ? 63 : lane;
+          const int x = side == 0 || side == 1 ? lane : side == 2 ? 0 : 63;
+          uint8_t rk = 0xFFu;
+          if ((s_F[y] >> x) & 1ull) rk = (uint8_t)root_rank(s_root, s_rootpre, r_par[run_of(s_rbase, s_F, y, x)]);
+          reinterpret_cast<uint8_t*>(ent + kFcEdge)[tid] = rk;
+        }
+        for (int r = tid; r < nruns; r += kFT) {
+          if (r_par[r] != r) continue;
+          const int c = root_rank(s_root, s_rootpre, r);
+          const uint64_t zx = szx[c];
+          ent[kFcComp + c] = (uint64_t)r_s[r] | ((uint64_t)r_y[r] << 6) | ((zx >> 18) << 12) |
+                             ((zx & 0x3FFFFull) << 25) | ((uint64_t)ssy[c] << 43);
+        }
+        if (tid == 0) ent[kFcHdr] = 1ull | ((uint64_t)nr << 8) | ((uint64_t)nruns << 16);
+      }
+      __syncthreads();
+      DM_PH(dm_phase_acc_frontier, 11);
+    } else {
+      __syncthreads();
+      DM_PH(dm_phase_acc_frontier, 7);
+    }
   }
   }
   DM_PH_FLUSH(dm_phase_acc_frontier);
@@ -1331,17 +1457,21 @@ __device__ inline void write_rb_header(int64_t K, int64_t cap, unsigned long lon
   unsigned long long* header = dm_rb_header(host_out);
   if (tid < ncnt) header[tid] = tid == sorted_idx ? (K <= cap ? 1ull : 0ull) : cnt[tid];
   if (tid == ncnt && fsh) {
-    unsigned long long most = 0, runs = 0, ftf = 0, big = 0;
+    unsigned long long most = 0, runs = 0, ftf = 0, big = 0, chit = 0, cmiss = 0;
     for (int i = 0; i < kShards; ++i) {
       most = max(most, fsh[i * kShardWords + SH_SLOT]);
       runs += fsh[i * kShardWords + SH_RUNS];
       ftf += fsh[i * kShardWords + SH_FTF];
       big += fsh[i * kShardWords + SH_BIG];
+      chit += fsh[i * kShardWords + SH_CHIT];
+      cmiss += fsh[i * kShardWords + SH_CMISS];
     }
     header[ncnt] = most;
     header[ncnt + 1] = runs;
     header[ncnt + 2] = ftf;
     header[ncnt + 3] = big;
+    header[ncnt + 4] = chit;
+    header[ncnt + 5] = cmiss;
   }
 }
 
@@ -1863,6 +1993,19 @@ int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool spli
   const bool edge = !dense && g->sort_hint <= std::max<int64_t>(g->ftile_hint, 1);
   auto* const big_kernel = edge ? k_frontier_tile_big<true> : k_frontier_tile_big<false>;
   auto* const wave_kernel = edge ? k_frontier_tile<true> : k_frontier_tile<false>;
+  // the label cache, with the first pass that launches the workgroup kernel
+  // (every pass does); without the memory the passes run uncached
+  if (g->fcache_mode == 1 && !g->fcache) {
+    void* p = nullptr;
+    const size_t bytes = sizeof(uint64_t) * kFcWords * (size_t)g->NT;
+    if (hipMalloc(&p, bytes) == hipSuccess && hipMemsetAsync(p, 0, bytes, g->stream) == hipSuccess) {
+      g->fcache = (uint64_t*)p;
+    } else {
+      (void)hipGetLastError();
+      if (p) (void)hipFree(p);
+      g->fcache_mode = 0;
+    }
+  }
   dm_timer_begin(g, "frontier_bits", &t);
   DM_LAUNCH(k_frontier_bits, dim3(bits_grid), dim3(kFW * 64), 0, g->stream, fg, g->state, g->halo, g->fmask,
             g->fedge, g->tile_seen, g->ftiles, g->ftiles_n, list_n, g->fbits, g->cnt, g->fmask_on ? 1 : 0,
@@ -1899,7 +2042,7 @@ int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool spli
     DM_LAUNCH(big_kernel, dim3(big_grid), dim3(kFT), 0, g->big_stream, fg, g->fbits,
               g->big_tiles,
               g->ftiles, list_n, g->border, g->rel, g->slot_label, g->slot_parent, g->slot_own,
-              g->slot_acc, g->mask, g->cell_slot, g->edge_slot, g->cnt, g->fsh, 0);
+              g->slot_acc, g->mask, g->cell_slot, g->edge_slot, g->cnt, g->fsh, 0, g->fcache);
     dm_timer_end(g, &t);
     DM_HIP(hipGetLastError());
     DM_HIP(hipEventRecord(g->ev_big, g->big_stream));
@@ -1922,7 +2065,7 @@ int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool spli
     DM_LAUNCH(big_kernel, dim3(dense_grid), dim3(kFT), 0, ps, fg, g->fbits, nullptr,
               g->ftiles, list_n,
               g->border, g->rel, g->slot_label, g->slot_parent, g->slot_own, g->slot_acc, g->mask,
-              g->cell_slot, g->edge_slot, g->cnt, g->fsh, 1);
+              g->cell_slot, g->edge_slot, g->cnt, g->fsh, 1, g->fcache);
     dm_timer_end(g, &t);
     DM_HIP(hipGetLastError());
   }
@@ -2001,6 +2144,9 @@ int dm_frontiers_readback(dm_grid* g, int64_t* n_clusters, int64_t* copied) {
   g->runs_hint = (int64_t)hdr[CNT_N + 1];
   g->ftf_hint = (int64_t)hdr[CNT_N + 2];
   g->big_hint = (int64_t)hdr[CNT_N + 3];
+  g->fc_hits = hdr[CNT_N + 4];
+  g->fc_misses = hdr[CNT_N + 5];
+  g->fc_collected = true;
   return DM_OK;
 }
 

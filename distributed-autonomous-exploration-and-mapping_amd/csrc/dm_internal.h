@@ -88,8 +88,11 @@ static_assert(kShards * kShardWords == 512, "k_integrate_reset covers 512 shard 
 enum { SH_U = 0, SH_T = 1, SH_TH = 2, SH_ACT = 3 };
 // frontier shard fields: slots allocated, runs and tiles with frontier
 // cells (the next pass picks its tile kernel from their ratio)
-// and tiles too run-rich for a tile-wave (the next pass sizes the big kernel's grid)
-enum { SH_SLOT = 0, SH_RUNS = 1, SH_FTF = 2, SH_BIG = 3 };
+// and tiles too run-rich for a tile-wave (the next pass sizes the big kernel's grid);
+// tiles the workgroup kernel labelled from the label cache / in full
+enum { SH_SLOT = 0, SH_RUNS = 1, SH_FTF = 2, SH_BIG = 3, SH_CHIT = 4, SH_CMISS = 5 };
+// 64-bit words of one tile's label-cache entry (dm_frontier.hip): 1.25 KB
+constexpr int kFcWords = 160;
 
 // dm_last_stats entries (include/dm.h)
 constexpr int kNStats = 11;
@@ -100,10 +103,10 @@ constexpr bool dm_stat_is_frontier(int i) { return i >= 7 && i <= 9; }  // the o
 // frontier counters [CNT_N] and the fullest slot shard [CNT_N], written by
 // k_rank_sort into the mapped host buffer together with the first records.
 // header words: [0, CNT_N) counters, [CNT_N] fullest slot shard, [CNT_N + 1]
-// runs, [CNT_N + 2] tiles with frontier cells, [CNT_N + 3] run-rich tiles
-// (shard sums)
-constexpr int kRbRecords = 6;  // 6 * 48 B = 288 B >= (CNT_N + 3) * 8 B
-static_assert(kRbRecords * sizeof(dm_cluster) >= (CNT_N + 4) * sizeof(unsigned long long), "readback header");
+// runs, [CNT_N + 2] tiles with frontier cells, [CNT_N + 3] run-rich tiles,
+// [CNT_N + 4] label-cache hits, [CNT_N + 5] misses (shard sums)
+constexpr int kRbRecords = 6;  // 6 * 48 B = 288 B >= (CNT_N + 6) * 8 B
+static_assert(kRbRecords * sizeof(dm_cluster) >= (CNT_N + 6) * sizeof(unsigned long long), "readback header");
 // The mapped host readback carries 32-byte records (label, size, sum_x,
 // sum_y): the host computes the centroids with the SPEC's double formula
 // (one division, then add; no FMA), bit-identical to the device's, so a third
@@ -112,7 +115,7 @@ struct dm_raw_record {
   long long label, size, sum_x, sum_y;
 };
 constexpr int kRbHostRecords = 6;  // 6 * 32 B = 192 B of header in front of the host records
-static_assert(kRbHostRecords * sizeof(dm_raw_record) >= (CNT_N + 4) * sizeof(unsigned long long),
+static_assert(kRbHostRecords * sizeof(dm_raw_record) >= (CNT_N + 6) * sizeof(unsigned long long),
               "readback header");
 __host__ __device__ inline unsigned long long* dm_rb_header(dm_raw_record* records) {
   return reinterpret_cast<unsigned long long*>(records - kRbHostRecords);
@@ -254,6 +257,18 @@ struct dm_grid {
   uint8_t* tile_seen = nullptr;
   bool fmask_on = false, fmask_valid = false;
   int fmask_mode = 0;  // DM_FMASK=auto|on|off (read at dm_create; tests / A/B): 0 auto, 1 on, 2 off
+  // Label cache of the workgroup tile kernel: [NT][kFcWords], one entry per
+  // tile, valid exactly when its stored bit rows equal the pass's (nothing
+  // else ever has to touch it: dm_reset, dm_set_state, dm_load and relists
+  // leave it alone).  Allocated zero-filled with the first frontier pass;
+  // fcache_mode: DM_FRONTIER_CACHE=on|off (read at dm_create; tests / A/B),
+  // 1 on, 0 off -- also after a failed allocation, which is no error.
+  uint64_t* fcache = nullptr;
+  int fcache_mode = 1;
+  // hits and misses of the last collected pass (readback header), or of the
+  // last export pass (fc_collected false: read from its shards on demand)
+  unsigned long long fc_hits = 0, fc_misses = 0;
+  bool fc_collected = true;
   unsigned long long* cnt = nullptr;    // CNT_N device counters (frontier fields)
   unsigned long long* h_cnt = nullptr;  // pinned mirror: [CNT_N] frontier counters, [CNT_N] integrate counters
   unsigned long long* fsh = nullptr;    // [kShards][kShardWords] frontier shards
@@ -747,6 +762,7 @@ int dm_sh_integrate_device(dm_grid* g, int32_t S, const double* d_pose4, int32_t
                            float amin, float inc);
 int dm_sh_last_counts(dm_grid* g, uint64_t* U, uint64_t* T);
 int dm_sh_last_stats(dm_grid* g, uint64_t* out, int32_t cap, int32_t* n_out);
+int dm_sh_frontier_cache_stats(dm_grid* g, uint64_t* hits, uint64_t* misses);
 int dm_sh_get_state(dm_grid* g, int8_t* out);
 int dm_sh_get_logodds(dm_grid* g, float* out);
 int dm_sh_set_logodds(dm_grid* g, const float* in);

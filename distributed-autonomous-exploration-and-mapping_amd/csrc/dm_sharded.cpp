@@ -600,6 +600,21 @@ int dm_sh_last_stats(dm_grid* g, uint64_t* out, int32_t cap, int32_t* n_out) {
   return DM_OK;
 }
 
+int dm_sh_frontier_cache_stats(dm_grid* g, uint64_t* hits, uint64_t* misses) {
+  dm_shard_set* s = g->sh;
+  if (!hits || !misses) return dm_set_error(DM_ERR_INVALID_ARG, "hits or misses is NULL");
+  uint64_t h = 0, m = 0;
+  for (int r = 0; r < s->P; ++r) {  // the bands' last passes
+    uint64_t bh = 0, bm = 0;
+    if (int rc = dm_frontier_cache_stats(s->band[(size_t)r], &bh, &bm)) return rc;
+    h += bh;
+    m += bm;
+  }
+  *hits = h;
+  *misses = m;
+  return DM_OK;
+}
+
 int dm_sh_profile_enable(dm_grid* g, int enable) {
   dm_shard_set* s = g->sh;
   for (int r = 0; r < s->P; ++r)

@@ -191,6 +191,15 @@ class OccupancyMapper:
             check(self._lib.dm_last_stats(self._handle(), out, k, ctypes.byref(n)))
         return {k: int(out[i]) for i, k in enumerate(self.STAT_NAMES)}
 
+    def frontier_cache_stats(self) -> tuple[int, int]:
+        """(hits, misses) of the last collected frontier pass's label cache
+        (dm_frontier_cache_stats): tiles labelled from their cached entry /
+        labelled in full by the workgroup tile kernel."""
+        h, m = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        with self._lock:
+            check(self._lib.dm_frontier_cache_stats(self._handle(), ctypes.byref(h), ctypes.byref(m)))
+        return int(h.value), int(m.value)
+
     def ld06_to_scans(self, points, offsets, n_beams: int, laser_scan_dir: bool = True,
                       want_intensities: bool = False):
         """LD06 PointData -> LaserScan ranges on the GPU, as the driver's

@@ -171,6 +171,19 @@ int dm_last_counts(dm_grid* g, uint64_t* updates, uint64_t* touched);
  * cap gets the first cap of them. */
 int dm_last_stats(dm_grid* g, uint64_t* out, int32_t cap, int32_t* n_out);
 
+/* The frontier label cache.  The dense-pass tile kernel keeps, per map tile,
+ * the tile-local labelling (components, their sizes and sums, the component
+ * of every edge cell) together with the 64 frontier bit rows it was computed
+ * from; a pass whose bit rows for a tile equal the stored ones reuses it (a
+ * hit), any other tile with frontier cells is labelled in full (a miss).
+ * Validity is by content only, so no call invalidates it and results are the
+ * same with and without it (DM_FRONTIER_CACHE=off, read at dm_create,
+ * switches it off).  *hits / *misses = the counts of the last collected
+ * frontier pass (on a sharded handle: summed over the bands' last passes).
+ * 1.25 KB of device memory per tile, allocated with the first pass; if that
+ * allocation fails the passes run uncached. */
+int dm_frontier_cache_stats(dm_grid* g, uint64_t* hits, uint64_t* misses);
+
 /* OccupancyGrid.data for the band: int8[band_rows*width] (-1 / 0 / 100). */
 int dm_get_state(dm_grid* g, int8_t* out);
 /* Log-odds for the band: float[band_rows*width]. */

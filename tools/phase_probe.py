@@ -23,7 +23,8 @@ from dm import synth  # noqa: E402
 NAMES = {
     "frontier": {0: "tile index + bit rows", 1: "F+run scan", 2: "enum runs", 3: "unions", 4: "compress",
                  5: "roots", 6: "sums+slot atomic", 7: "slot writes + edge unions + band rows", 8: "empty tile exit",
-                 16: "#tiles", 17: "#runs", 18: "#tiles with F"},
+                 9: "hit: entry loads + slot atomic", 10: "hit: slot writes", 11: "miss: cache entry stores",
+                 16: "#tiles", 17: "#runs (full path)", 18: "#tiles with F", 19: "#label-cache hits"},
     "ftile": {9: "tile index load", 0: "bit rows", 1: "run scan + LDS init", 2: "row unions",
               3: "compress + root ranks", 4: "sums", 5: "slot atomic + slot writes", 6: "border publish + drain",
               7: "pair arrivals", 8: "edge unions", 10: "dense / band-edge writes",
