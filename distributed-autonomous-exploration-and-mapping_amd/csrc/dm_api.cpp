@@ -673,7 +673,7 @@ int dm_destroy(dm_grid* g) {
   dev_free(g->match_trig); dev_free(g->match_ranges); dev_free(g->match_q); dev_free(g->match_vol);
   dev_free(g->match_out);
   dev_free(g->gain_xy); dev_free(g->gain_cell); dev_free(g->gain_out); dev_free(g->gain_skip);
-  dev_free(g->gain_memo_cell); dev_free(g->gain_memo_gain);
+  dev_free(g->gain_memo_cell); dev_free(g->gain_memo_gain); dev_free(g->gain_claimed);
   for (auto& w : g->iw) {
     dev_free(w.pieces); dev_free(w.hitems); dev_free(w.litems); dev_free(w.heavy_list); dev_free(w.slabs);
     dev_free(w.heavy_done); dev_free(w.tile_count); dev_free(w.tile_cur); dev_free(w.cnt); dev_free(w.sh);
@@ -1673,11 +1673,72 @@ int dm_gain_views(dm_grid* g, const double* views_xy, int64_t n, int32_t radius_
   return DM_OK;
 }
 
-int dm_assign_goals_gain(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size, int64_t min_gain,
-                         double distance_weight, double min_distance, int32_t inflate_cells, uint32_t max_cost,
-                         int32_t snap_cells, int32_t radius_cells, int64_t* out_index, double* out_xy,
-                         int64_t* out_cell, uint32_t* out_gain) {
-  int rc = plan_check_handle(g, "dm_assign_goals_gain");
+// The claimed set of the overlap-aware calls: allocated by the first of them.
+static int64_t claimed_words(const dm_grid* g) { return g->H * ((g->W + 31) / 32); }
+
+static int ensure_claimed(dm_grid* g) {
+  if (g->gain_claimed) return DM_OK;
+  return dev_alloc(&g->gain_claimed, claimed_words(g), "claimed set");
+}
+
+// n points (metres) to g->gain_xy and their cells to g->gain_cell.
+static int gain_upload_views(dm_grid* g, const double* xy, int64_t n) {
+  if (n <= 0) return DM_OK;
+  DM_HIP(hipMemcpyAsync(g->gain_xy, xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, g->stream));
+  return dm_gain_launch_cells(g, n);
+}
+
+int dm_gain_views_joint(dm_grid* g, const double* views_xy, int64_t n, int32_t radius_cells, uint32_t* out_marginal,
+                        int64_t* out_cell) {
+  int rc = plan_check_handle(g, "dm_gain_views_joint");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n < 0 || n > 1024) return dm_set_error(DM_ERR_INVALID_ARG, "n must be in [0, 1024] (got %lld)", (long long)n);
+  if (n > 0 && (!views_xy || !out_marginal || !out_cell))
+    return dm_set_error(DM_ERR_INVALID_ARG, "views_xy / out_marginal / out_cell is NULL");
+  if ((rc = gain_check_radius(radius_cells))) return rc;
+  if ((rc = ensure_claimed(g)) || (rc = grow_gain(g, std::max<int64_t>(n, 1)))) return rc;
+  DM_HIP(dm_sync_all(g));  // after everything enqueued on the handle, on every stream of it
+  g->gain_claimed_valid = false;
+  DM_HIP(hipMemsetAsync(g->gain_claimed, 0, sizeof(uint32_t) * (size_t)claimed_words(g), g->stream));
+  if ((rc = gain_upload_views(g, views_xy, n))) return rc;
+  if ((rc = dm_gain_launch_joint(g, g->gain_cell, n, radius_cells, g->gain_out))) return rc;
+  if (n > 0) {
+    DM_HIP(hipMemcpyAsync(out_marginal, g->gain_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+    DM_HIP(hipMemcpyAsync(out_cell, g->gain_cell, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  }
+  DM_HIP(hipStreamSynchronize(g->stream));
+  g->gain_claimed_valid = true;
+  return DM_OK;
+}
+
+int dm_gain_claimed(dm_grid* g, uint8_t* out) {
+  int rc = plan_check_handle(g, "dm_gain_claimed");
+  if (rc || (rc = use_device(g))) return rc;
+  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
+  if (!g->gain_claimed || !g->gain_claimed_valid)
+    return dm_set_error(DM_ERR_STATE, "dm_gain_claimed: no claimed set (call dm_gain_views_joint or "
+                        "dm_assign_goals_coord first)");
+  const int64_t cells = g->W * g->H;
+  uint8_t* d = nullptr;
+  if ((rc = dev_alloc(&d, cells, "claimed image"))) return rc;
+  rc = dm_gain_launch_expand(g, d);
+  hipError_t e = hipSuccess;
+  if (!rc) e = hipMemcpyAsync(out, d, (size_t)cells, hipMemcpyDeviceToHost, g->stream);
+  if (!rc && e == hipSuccess) e = hipStreamSynchronize(g->stream);
+  (void)hipFree(d);
+  if (e != hipSuccess) return dm_hip_check(e, "dm_gain_claimed");
+  return rc;
+}
+
+// dm_assign_goals_gain (held_xy == nullptr, n_held == 0, coord == false) and
+// dm_assign_goals_coord: the same call but for the numerator, which with
+// `coord` is the marginal gain against the claimed set.
+static int assign_goals_gain_impl(dm_grid* g, const char* what, bool coord, const double* robots_xy, int32_t n_robots,
+                                  const double* held_xy, int32_t n_held, int64_t min_size, int64_t min_gain,
+                                  double distance_weight, double min_distance, int32_t inflate_cells,
+                                  uint32_t max_cost, int32_t snap_cells, int32_t radius_cells, int64_t* out_index,
+                                  double* out_xy, int64_t* out_cell, uint32_t* out_gain) {
+  int rc = plan_check_handle(g, what);
   if (rc || (rc = use_device(g))) return rc;
   if (n_robots < 0 || n_robots > 256)
     return dm_set_error(DM_ERR_INVALID_ARG, "n_robots must be in [0, 256] (got %d)", n_robots);
@@ -1688,6 +1749,9 @@ int dm_assign_goals_gain(dm_grid* g, const double* robots_xy, int32_t n_robots, 
   if (distance_weight < 0.0)  // as dm_assign_goals: the device ranks by the util's IEEE bits
     return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight must be >= 0");
   if (min_gain < 0) return dm_set_error(DM_ERR_INVALID_ARG, "min_gain must be >= 0 (got %lld)", (long long)min_gain);
+  if (n_held < 0 || n_held > 1024)
+    return dm_set_error(DM_ERR_INVALID_ARG, "n_held must be in [0, 1024] (got %d)", n_held);
+  if (n_held > 0 && !held_xy) return dm_set_error(DM_ERR_INVALID_ARG, "held_xy is NULL");
   if ((rc = plan_check_inflate(inflate_cells)) || (rc = plan_check_snap(snap_cells)) ||
       (rc = gain_check_radius(radius_cells)))
     return rc;
@@ -1697,7 +1761,7 @@ int dm_assign_goals_gain(dm_grid* g, const double* robots_xy, int32_t n_robots, 
     return dm_set_error(DM_ERR_INVALID_ARG, "no collected frontier result on the device (call dm_frontiers, "
                                             "dm_frontiers_end or dm_merge_bands first; a later pass may have "
                                             "reused its readback slot)");
-  if (n_robots == 0) return DM_OK;
+  if (n_robots == 0 && !coord) return DM_OK;
   for (int32_t r = 0; r < n_robots; ++r) {
     int64_t c;
     if (!plan_cell_of(g, robots_xy[2 * r], robots_xy[2 * r + 1], &c))
@@ -1707,9 +1771,22 @@ int dm_assign_goals_gain(dm_grid* g, const double* robots_xy, int32_t n_robots, 
   const dm_cluster* recs = g->goal_kind == 1 ? g->rb[s].out_clu : g->rb[s].m_out;
   const int64_t K = g->goal_n;
   if ((rc = ensure_plan(g)) || (rc = grow_plan_query(g, std::max<int64_t>(K, 1))) ||
-      (rc = grow_gain(g, std::max<int64_t>(K, 1))))
+      (rc = grow_gain(g, std::max<int64_t>(std::max<int64_t>(K, n_held), 1))))
     return rc;
+  if (coord && (rc = ensure_claimed(g))) return rc;
   DM_HIP(dm_join_pass_stream(g));
+  if (coord) {
+    // C: empty, then the held views, all in one launch (ORs commute)
+    g->gain_claimed_valid = false;
+    DM_HIP(hipMemsetAsync(g->gain_claimed, 0, sizeof(uint32_t) * (size_t)claimed_words(g), g->stream));
+    if ((rc = gain_upload_views(g, held_xy, n_held))) return rc;
+    if ((rc = dm_gain_launch_commit(g, g->gain_cell, n_held, radius_cells))) return rc;
+    if (n_robots == 0) {
+      DM_HIP(hipStreamSynchronize(g->stream));
+      g->gain_claimed_valid = true;
+      return DM_OK;
+    }
+  }
   if ((rc = dm_plan_launch_travers(g, inflate_cells))) return rc;
   // the memo of this call: no cluster has a cast yet (every byte 0xFF: cell -1,
   // which no cast view has)
@@ -1730,7 +1807,9 @@ int dm_assign_goals_gain(dm_grid* g, const double* robots_xy, int32_t n_robots, 
                                    g->plan_qcost, g->plan_qcell)))
       return rc;
     if ((rc = dm_gain_launch_skip(g, recs, g->plan_qcost, K, min_size))) return rc;
-    if ((rc = dm_gain_launch_views(g, g->plan_qcell, g->gain_skip, K, radius_cells, true))) return rc;
+    if ((rc = coord ? dm_gain_launch_marginal(g, g->plan_qcell, g->gain_skip, K, radius_cells, true)
+                    : dm_gain_launch_views(g, g->plan_qcell, g->gain_skip, K, radius_cells, true)))
+      return rc;
     const unsigned long long* dk = nullptr;
     const uint32_t* di = nullptr;
     if ((rc = dm_launch_goal_topk(g, recs, K, nullptr, 1, T, min_size, distance_weight, min_distance, &dk, &di,
@@ -1756,10 +1835,39 @@ int dm_assign_goals_gain(dm_grid* g, const double* robots_xy, int32_t n_robots, 
       out_gain[r] = gain;
       out_xy[2 * r] = g->p.origin_x + ((double)(cell % g->W) + 0.5) * g->p.resolution;
       out_xy[2 * r + 1] = g->p.origin_y + ((double)(cell / g->W) + 0.5) * g->p.resolution;
+      if (coord) {
+        // the goal's view joins C before the next robot is scored; its gain
+        // is > 0, so C changed and no memo entry holds any longer
+        if ((rc = dm_gain_launch_commit(g, g->plan_qcell + idx[(size_t)r], 1, radius_cells))) return rc;
+        DM_HIP(hipMemsetAsync(g->gain_memo_cell, 0xFF, sizeof(int64_t) * (size_t)K, g->stream));
+      }
     }
+  }
+  if (coord) {
+    DM_HIP(hipStreamSynchronize(g->stream));
+    g->gain_claimed_valid = true;
   }
   memcpy(out_index, idx.data(), sizeof(int64_t) * (size_t)R);
   return DM_OK;
+}
+
+int dm_assign_goals_gain(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size, int64_t min_gain,
+                         double distance_weight, double min_distance, int32_t inflate_cells, uint32_t max_cost,
+                         int32_t snap_cells, int32_t radius_cells, int64_t* out_index, double* out_xy,
+                         int64_t* out_cell, uint32_t* out_gain) {
+  return assign_goals_gain_impl(g, "dm_assign_goals_gain", false, robots_xy, n_robots, nullptr, 0, min_size, min_gain,
+                                distance_weight, min_distance, inflate_cells, max_cost, snap_cells, radius_cells,
+                                out_index, out_xy, out_cell, out_gain);
+}
+
+int dm_assign_goals_coord(dm_grid* g, const double* robots_xy, int32_t n_robots, const double* held_xy,
+                          int32_t n_held, int64_t min_size, int64_t min_gain, double distance_weight,
+                          double min_distance, int32_t inflate_cells, uint32_t max_cost, int32_t snap_cells,
+                          int32_t radius_cells, int64_t* out_index, double* out_xy, int64_t* out_cell,
+                          uint32_t* out_gain) {
+  return assign_goals_gain_impl(g, "dm_assign_goals_coord", true, robots_xy, n_robots, held_xy, n_held, min_size,
+                                min_gain, distance_weight, min_distance, inflate_cells, max_cost, snap_cells,
+                                radius_cells, out_index, out_xy, out_cell, out_gain);
 }
 
 // ---- scan matcher (csrc/dm_match.h): response field, score volume, best

@@ -1,5 +1,7 @@
 // dm_gain.h — visible-unknown count of a viewpoint: the device
-// code of dm_gain_views and dm_assign_goals_gain, included by dm_goals.hip.
+// code of dm_gain_views and dm_assign_goals_gain, and of the overlap-aware
+// dm_gain_views_joint, dm_assign_goals_coord and dm_gain_claimed (§9.4),
+// included by dm_goals.hip.
 //
 // Definition (integers only, so every result is unique and bit-exact), for a
 // view cell (vx, vy) and radius_cells = R in [1, kMaxR]:
@@ -52,17 +54,44 @@ __global__ void k_gain_skip(const dm_cluster* __restrict__ recs, const uint32_t*
   skip[c] = (recs[c].size < min_size || cost[c] == DM_PLAN_UNREACHABLE) ? 1 : 0;
 }
 
+// Words of a row of the claimed set (below): bit x & 31 of word
+// y * claimed_wpr(W) + (x >> 5) is cell (x, y).
+__host__ __device__ inline int32_t claimed_wpr(int32_t W) { return (W + 31) >> 5; }
+
+// The claimed word at (row y, word index q); 0 outside the grid.
+__device__ inline uint32_t claimed_load(const uint32_t* claimed, int32_t cwpr, int32_t H, int32_t y, int32_t q) {
+  return (y >= 0 && y < H && q >= 0 && q < cwpr) ? claimed[(int64_t)y * cwpr + q] : 0u;
+}
+
 // cells[v]: the view's linear cell, < 0 for none (gain 0).  skip (may be
 // null): skip[v] != 0 gives gain 0 without a cast.  memo_cell / memo_gain (may
 // be null): the cell and gain of the last cast of view slot v; a view on the
 // same cell takes the gain from there.
-template <bool kStatic>
+//
+// The overlap-aware calls (dm_gain_views_joint, dm_assign_goals_coord; DESIGN
+// §9.4) keep a claimed set C, a global bitmap of H rows of claimed_wpr(W)
+// words.  The LDS word (row, wi) of a view covers map row y = vy + row - R and
+// the columns x0 .. x0 + 31, x0 = vx - R + 32 wi; its claimed bits are the two
+// global words at floor(x0 / 32) and + 1 of row y, shifted down by x0 mod 32
+// (floor division and modulo: x0 < 0 within R of the left edge).
+//   kMask    after the walk the claimed bits are taken out of the LDS bitmap,
+//            so the count is the marginal gain, |V minus C|; a memo is then
+//            only good for the C it was filled under (dm_api.cpp drops it
+//            after every commit)
+//   kCommit  after that every non-zero LDS word is ORed into the one or two
+//            global words it overlaps: C := C u V
+// With both, all reads of C come before a barrier and all ORs after it.
+// Between workgroups nothing waits: a launch that reports marginals has no
+// concurrent writer of C (kMask && kCommit is launched one view at a time,
+// kMask alone only reads, kCommit alone counts nothing and ORs commute).
+template <bool kStatic, bool kMask = false, bool kCommit = false>
 __global__ __launch_bounds__(kThreads) void k_gain_views(const int8_t* __restrict__ state, int32_t W, int32_t H,
                                                          const int64_t* __restrict__ cells,
                                                          const uint8_t* __restrict__ skip, int32_t R,
                                                          int64_t* __restrict__ memo_cell,
                                                          uint32_t* __restrict__ memo_gain,
-                                                         uint32_t* __restrict__ out_gain) {
+                                                         uint32_t* __restrict__ out_gain,
+                                                         uint32_t* claimed) {
   extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
   __shared__ uint32_t s_fix[kStatic ? kMaxWords : 1];
   __shared__ uint32_t s_sum;
@@ -72,8 +101,9 @@ __global__ __launch_bounds__(kThreads) void k_gain_views(const int8_t* __restric
   const int tid = threadIdx.x;
   // every branch up to the cast is uniform over the workgroup
   const int64_t cell = cells[v];
+  constexpr bool kCount = kMask || !kCommit;  // kCommit alone reports nothing: out_gain is not touched
   if (cell < 0 || (skip && skip[v])) {
-    if (tid == 0) out_gain[v] = 0u;
+    if (kCount && tid == 0) out_gain[v] = 0u;
     return;
   }
   if (memo_cell && memo_cell[v] == cell) {
@@ -131,6 +161,34 @@ __global__ __launch_bounds__(kThreads) void k_gain_views(const int8_t* __restric
   }
   __syncthreads();
 
+  if constexpr (kMask || kCommit) {
+    const int32_t cwpr = claimed_wpr(W);
+    if constexpr (kMask) {
+      for (int32_t i = tid; i < nwords; i += kThreads) {
+        const uint32_t m = bits[i];
+        if (!m) continue;
+        const int32_t row = i / wpr, x0 = vx - R + 32 * (i - row * wpr), y = vy + row - R;
+        const int32_t q = x0 >> 5, sh = x0 & 31;  // floor division and modulo
+        const uint32_t lo = claimed_load(claimed, cwpr, H, y, q), hi = claimed_load(claimed, cwpr, H, y, q + 1);
+        bits[i] = m & ~(uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
+      }
+      __syncthreads();  // every read of C is before every OR below
+    }
+    if constexpr (kCommit) {
+      for (int32_t i = tid; i < nwords; i += kThreads) {
+        const uint32_t m = bits[i];
+        if (!m) continue;
+        const int32_t row = i / wpr, x0 = vx - R + 32 * (i - row * wpr), y = vy + row - R;
+        if (y < 0 || y >= H) continue;
+        const int32_t q = x0 >> 5, sh = x0 & 31;
+        const uint32_t lo = m << sh, hi = sh ? m >> (32 - sh) : 0u;
+        if (lo && q >= 0 && q < cwpr) atomicOr(&claimed[(int64_t)y * cwpr + q], lo);
+        if (hi && q + 1 >= 0 && q + 1 < cwpr) atomicOr(&claimed[(int64_t)y * cwpr + q + 1], hi);
+      }
+    }
+  }
+  if constexpr (!kCount) return;
+
   uint32_t c = 0u;
   for (int32_t i = tid; i < nwords; i += kThreads) c += (uint32_t)__popc(bits[i]);
   for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
@@ -154,6 +212,15 @@ __global__ void k_gain_cells(const double* __restrict__ xy, int64_t n, int64_t W
   const double fx = floor((xy[2 * i] - ox) / res), fy = floor((xy[2 * i + 1] - oy) / res);
   const bool in = fx >= 0.0 && fx < (double)W && fy >= 0.0 && fy < (double)H;  // NaN: out of grid
   out_cell[i] = in ? (int64_t)fy * W + (int64_t)fx : -1;
+}
+
+// The claimed set as bytes, 1 / 0 per cell (dm_gain_claimed).
+__global__ void k_gain_expand(const uint32_t* __restrict__ claimed, int32_t W, int32_t H,
+                              uint8_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)W * H) return;
+  const int32_t x = (int32_t)(i % W), y = (int32_t)(i / W);
+  out[i] = (uint8_t)((claimed[(int64_t)y * claimed_wpr(W) + (x >> 5)] >> (x & 31)) & 1u);
 }
 
 }  // namespace dm_gain

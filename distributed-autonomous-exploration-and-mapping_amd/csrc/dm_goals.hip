@@ -409,21 +409,77 @@ int dm_gain_launch_skip(dm_grid* g, const dm_cluster* d_recs, const uint32_t* d_
   return DM_OK;
 }
 
-int dm_gain_launch_views(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R, bool memo) {
+namespace {
+
+// One launch of k_gain_views<., kMask, kCommit> over n views; the bitmap is
+// dynamic LDS up to kDynBytes and the static form above.
+template <bool kMask, bool kCommit>
+void gain_launch(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R, int64_t* mc,
+                 uint32_t* mg, uint32_t* d_out, uint32_t* d_claimed) {
   using namespace dm_gain;
-  if (n <= 0) return DM_OK;
   const size_t bytes = sizeof(uint32_t) * (size_t)bitmap_words(R);
+  if (bytes <= (size_t)kDynBytes)
+    hipLaunchKernelGGL((k_gain_views<false, kMask, kCommit>), dim3((unsigned)n), dim3(kThreads), bytes, g->stream,
+                       g->state, (int32_t)g->W, (int32_t)g->H, d_cell, d_skip, R, mc, mg, d_out, d_claimed);
+  else
+    hipLaunchKernelGGL((k_gain_views<true, kMask, kCommit>), dim3((unsigned)n), dim3(kThreads), 0, g->stream,
+                       g->state, (int32_t)g->W, (int32_t)g->H, d_cell, d_skip, R, mc, mg, d_out, d_claimed);
+}
+
+}  // namespace
+
+int dm_gain_launch_views(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R, bool memo) {
+  if (n <= 0) return DM_OK;
   int64_t* const mc = memo ? g->gain_memo_cell : nullptr;
   uint32_t* const mg = memo ? g->gain_memo_gain : nullptr;
   KernelTimer t;
   dm_timer_begin(g, "gain_views", &t);
-  if (bytes <= (size_t)kDynBytes)
-    hipLaunchKernelGGL(k_gain_views<false>, dim3((unsigned)n), dim3(kThreads), bytes, g->stream, g->state,
-                       (int32_t)g->W, (int32_t)g->H, d_cell, d_skip, R, mc, mg, g->gain_out);
-  else
-    hipLaunchKernelGGL(k_gain_views<true>, dim3((unsigned)n), dim3(kThreads), 0, g->stream, g->state, (int32_t)g->W,
-                       (int32_t)g->H, d_cell, d_skip, R, mc, mg, g->gain_out);
+  gain_launch<false, false>(g, d_cell, d_skip, n, R, mc, mg, g->gain_out, nullptr);
   DM_HIP(hipGetLastError());
   dm_timer_end(g, &t);
+  return DM_OK;
+}
+
+int dm_gain_launch_marginal(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R,
+                            bool memo) {
+  if (n <= 0) return DM_OK;
+  int64_t* const mc = memo ? g->gain_memo_cell : nullptr;
+  uint32_t* const mg = memo ? g->gain_memo_gain : nullptr;
+  KernelTimer t;
+  dm_timer_begin(g, "gain_marginal", &t);
+  gain_launch<true, false>(g, d_cell, d_skip, n, R, mc, mg, g->gain_out, g->gain_claimed);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  return DM_OK;
+}
+
+int dm_gain_launch_commit(dm_grid* g, const int64_t* d_cell, int64_t n, int32_t R) {
+  if (n <= 0) return DM_OK;
+  KernelTimer t;
+  dm_timer_begin(g, "gain_commit", &t);
+  gain_launch<false, true>(g, d_cell, nullptr, n, R, nullptr, nullptr, nullptr, g->gain_claimed);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  return DM_OK;
+}
+
+int dm_gain_launch_joint(dm_grid* g, const int64_t* d_cell, int64_t n, int32_t R, uint32_t* d_out) {
+  if (n <= 0) return DM_OK;
+  KernelTimer t;
+  dm_timer_begin(g, "gain_joint", &t);
+  // one view per launch: view i's marginal is against the views before it
+  for (int64_t i = 0; i < n; ++i) {
+    gain_launch<true, true>(g, d_cell + i, nullptr, 1, R, nullptr, nullptr, d_out + i, g->gain_claimed);
+    DM_HIP(hipGetLastError());
+  }
+  dm_timer_end(g, &t);
+  return DM_OK;
+}
+
+int dm_gain_launch_expand(dm_grid* g, uint8_t* d_out) {
+  const int64_t cells = g->W * g->H;
+  hipLaunchKernelGGL(dm_gain::k_gain_expand, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, g->stream,
+                     g->gain_claimed, (int32_t)g->W, (int32_t)g->H, d_out);
+  DM_HIP(hipGetLastError());
   return DM_OK;
 }

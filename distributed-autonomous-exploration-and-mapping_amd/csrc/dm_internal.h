@@ -549,6 +549,10 @@ struct dm_grid {
   int64_t* gain_memo_cell = nullptr;  // [gain_cap] per cluster: the cell of its last cast (one call)
   uint32_t* gain_memo_gain = nullptr; // [gain_cap] and its gain
   int64_t gain_cap = 0;
+  // the claimed set of dm_gain_views_joint / dm_assign_goals_coord: H rows of
+  // ceil(W / 32) words, allocated by the first of the two calls
+  uint32_t* gain_claimed = nullptr;
+  bool gain_claimed_valid = false;    // one of the two calls has run (dm_gain_claimed)
 
   // profiling
   bool profile = false;
@@ -726,6 +730,17 @@ int dm_gain_launch_skip(dm_grid* g, const dm_cluster* d_recs, const uint32_t* d_
 // gains of n view cells into g->gain_out; d_skip and the memo (g->gain_memo_*) are optional
 int dm_gain_launch_views(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R,
                          bool memo);
+// the overlap-aware forms, over the claimed set g->gain_claimed (allocated by
+// the caller, dm_api.cpp: ensure_claimed):
+// marginal gains of n view cells into g->gain_out, reading the claimed set only
+int dm_gain_launch_marginal(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R,
+                            bool memo);
+// the n views' visible sets into the claimed set, in one launch; reports nothing
+int dm_gain_launch_commit(dm_grid* g, const int64_t* d_cell, int64_t n, int32_t R);
+// view i's marginal gain into d_out[i], then its commit, for i = 0..n-1 in order (one launch each)
+int dm_gain_launch_joint(dm_grid* g, const int64_t* d_cell, int64_t n, int32_t R, uint32_t* d_out);
+// the claimed set as H * W bytes
+int dm_gain_launch_expand(dm_grid* g, uint8_t* d_out);
 // path planning (dm_plan.h, launched from dm_goals.hip); the plan_* arrays
 // of the handle are allocated by the caller (dm_api.cpp: ensure_plan)
 int dm_plan_launch_travers(dm_grid* g, int32_t inflate_cells);

@@ -185,6 +185,10 @@ SIGNATURES = {
     "dm_gain_views": [_vp, _vp, _i64, _i32, _vp, _vp],
     "dm_assign_goals_gain": [_vp, _vp, _i32, _i64, _i64, ctypes.c_double, ctypes.c_double, _i32, ctypes.c_uint32,
                              _i32, _i32, _vp, _vp, _vp, _vp],
+    "dm_gain_views_joint": [_vp, _vp, _i64, _i32, _vp, _vp],
+    "dm_assign_goals_coord": [_vp, _vp, _i32, _vp, _i32, _i64, _i64, ctypes.c_double, ctypes.c_double, _i32,
+                              ctypes.c_uint32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "dm_gain_claimed": [_vp, _vp],
     "dm_match_field": [_vp, _i32, _vp, _vp],
     "dm_match_scans": [_vp, _i32, _vp, _i32, _vp, _f32, _f32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp,
                        _vp, _vp, _vp, _vp, _vp],

@@ -389,6 +389,54 @@ class OccupancyMapper:
         return [(int(i), (float(p[0]), float(p[1])), int(c), int(gn)) if i >= 0 else None
                 for i, p, c, gn in zip(idx, out, cell, gain)]
 
+    def gain_views_joint(self, views_xy, radius_cells: int | None = None):
+        """The marginal gains of view points (metres) taken in order
+        (dm_gain_views_joint): (marginal uint32 [n], cell int64 [n]); view i
+        counts what it sees that the views before it do not.  The claimed set
+        it leaves is gain_claimed().  Same as dm.gain.gain_views_joint."""
+        xy = np.ascontiguousarray(np.asarray(views_xy, np.float64).reshape(-1, 2))
+        n = xy.shape[0]
+        R = self.default_gain_radius() if radius_cells is None else int(radius_cells)
+        marginal = np.zeros(n, np.uint32)
+        cell = np.full(n, -1, np.int64)
+        with self._lock:
+            check(self._lib.dm_gain_views_joint(self._handle(), _vp(xy), n, R, _vp(marginal), _vp(cell)))
+        return marginal, cell
+
+    def assign_goals_coord(self, robots_xy, held_xy=(), min_size: int = 8, min_gain: int = 0,
+                           distance_weight: float = 1.0, min_distance: float = 0.0, inflate_cells: int = 2,
+                           max_cost: int = 0, snap_cells: int = 5, radius_cells: int | None = None):
+        """assign_goals_gain scored by the marginal gain (dm_assign_goals_coord):
+        what a goal sees that neither the held views `held_xy` (the goals the
+        teammates already hold, metres) nor the goals of the robots before it
+        in this call see.  Per robot, in order, (cluster index, (x, y), cell,
+        marginal gain) or None; the claimed set it leaves is gain_claimed().
+        Same policy as dm.gain.assign_goals_coord."""
+        xy = np.ascontiguousarray(np.asarray(robots_xy, np.float64).reshape(-1, 2))
+        held = np.ascontiguousarray(np.asarray(held_xy, np.float64).reshape(-1, 2))
+        R = xy.shape[0]
+        rad = self.default_gain_radius() if radius_cells is None else int(radius_cells)
+        idx = np.empty(R, np.int64)
+        out = np.empty((R, 2), np.float64)
+        cell = np.empty(R, np.int64)
+        gain = np.empty(R, np.uint32)
+        with self._lock:
+            check(self._lib.dm_assign_goals_coord(self._handle(), _vp(xy), R, _vp(held) if held.shape[0] else None,
+                                                  held.shape[0], int(min_size), int(min_gain),
+                                                  float(distance_weight), float(min_distance), int(inflate_cells),
+                                                  int(max_cost), int(snap_cells), rad, _vp(idx), _vp(out),
+                                                  _vp(cell), _vp(gain)))
+        return [(int(i), (float(p[0]), float(p[1])), int(c), int(gn)) if i >= 0 else None
+                for i, p, c, gn in zip(idx, out, cell, gain)]
+
+    def gain_claimed(self) -> np.ndarray:
+        """The claimed set left by the last gain_views_joint or
+        assign_goals_coord (dm_gain_claimed): bool [rows, W]."""
+        out = np.empty((self.rows, self.width), np.uint8)
+        with self._lock:
+            check(self._lib.dm_gain_claimed(self._handle(), _vp(out)))
+        return out.astype(bool)
+
     # -- scan matching (csrc/dm_match.h; host restatement: dm/match.py) ----
     def match_field(self, smear_cells: int, kern) -> np.ndarray:
         """The matcher's response field (dm_match_field): uint8 [rows, W], per

@@ -37,6 +37,10 @@ callback signatures:
   slam_toolbox's, slam_config.yaml:35,50-53,64-66) before integrating it; the
   correction is kept as ``map_to_odom`` and, under ROS, broadcast as
   ``map -> odom``: the part of the TF chain slam_toolbox published;
+* with ``dm_goal_coordinate`` (default off), subscribes ``dm_peer_goals_topic``
+  (``geometry_msgs/PoseArray``: the goals the other robots hold) and scores its
+  own goal by what it would see that those goals do not
+  (``dm_assign_goals_coord``);
 * with ``dm_devices`` naming several GPUs, the map is one sharded handle
   (``dm_create_sharded``: row bands over those devices, the exchange inside
   libdm) behind the same calls.
@@ -105,6 +109,13 @@ class PoseStamped:
 @dataclass
 class Path:
     """nav_msgs/Path: the poses of a plan, start first."""
+    header: Header = field(default_factory=Header)
+    poses: list = field(default_factory=list)
+
+
+@dataclass
+class PoseArray:
+    """geometry_msgs/PoseArray: the goals the peers hold (dm_peer_goals_topic)."""
     header: Header = field(default_factory=Header)
     poses: list = field(default_factory=list)
 
@@ -223,6 +234,12 @@ class SlamParams:
     dm_goal_information_gain: bool = False
     dm_goal_gain_radius_m: float = float("nan")   # NaN: the map's range_max (max_laser_range)
     dm_goal_min_gain: int = 1
+    # discount a goal's gain by what the goals the peers already hold will see
+    # (dm_assign_goals_coord; the peers' goals arrive on dm_peer_goals_topic as
+    # a geometry_msgs/PoseArray in the map frame); implies
+    # dm_goal_information_gain; off: as before
+    dm_goal_coordinate: bool = False
+    dm_peer_goals_topic: str = "/peer_goals"
     # correct every accepted scan's pose against the map on the device
     # (dm_match_scans) and keep the correction as map -> odom; off: the pose
     # provider's pose is taken as it is, as before.  Needs use_scan_matching
@@ -416,6 +433,7 @@ class MappingNode:
         self.plan_pub = plan_publisher or ListPublisher("/plan")
         self.last_plan = None  # the Path of the last goal chosen by path length
         self.last_gain = None  # the gain of the last goal chosen with dm_goal_information_gain
+        self.peer_goals = []   # (x, y) of the goals the peers hold (dm_goal_coordinate)
         self.clock = clock
         self._last_publish = -math.inf
         self._pass_stamp = None  # stamp of the frontier pass in flight (None: none)
@@ -457,6 +475,11 @@ class MappingNode:
         self.last_integrated_pose = tuple(float(v) for v in pose)
         self.updates += u
         self.scans_integrated += 1
+
+    def peer_goals_cb(self, msg):
+        """dm_peer_goals_topic: the goals the other robots hold now; the next
+        choose_goal with dm_goal_coordinate discounts what they will see."""
+        self.peer_goals = [(float(p.position.x), float(p.position.y)) for p in msg.poses]
 
     def _match(self, msg, odom, prior):
         """Correct an accepted scan's prior against the map (the device's
@@ -531,7 +554,7 @@ class MappingNode:
         x, y, _ = self.latest_pose
         s = self.slam
         self.last_plan = None
-        if s.dm_goal_path_distance or s.dm_goal_information_gain:
+        if s.dm_goal_path_distance or s.dm_goal_information_gain or s.dm_goal_coordinate:
             return self._choose_goal_by_path(x, y, self._last_publish if stamp is None else stamp)
         g = self.mapper.assign_goals([(x, y)], min_size=s.dm_goal_min_size,
                                      distance_weight=s.dm_goal_distance_weight,
@@ -551,10 +574,19 @@ class MappingNode:
         the path to it (dm_plan_path over the field that call left) becomes
         ``last_plan``, a nav_msgs/Path whose poses face along the path.  With
         dm_goal_information_gain the score's numerator is the unknown area
-        visible from that cell (dm_assign_goals_gain), kept in ``last_gain``."""
+        visible from that cell (dm_assign_goals_gain), kept in ``last_gain``;
+        with dm_goal_coordinate it is what of that the peers' goals do not
+        already see (dm_assign_goals_coord with ``peer_goals`` held)."""
         s = self.slam
         inflate, snap = s.goal_cells()
-        if s.dm_goal_information_gain:
+        if s.dm_goal_coordinate:
+            g = self.mapper.assign_goals_coord([(x, y)], held_xy=self.peer_goals, min_size=s.dm_goal_min_size,
+                                               min_gain=s.dm_goal_min_gain,
+                                               distance_weight=s.dm_goal_distance_weight,
+                                               min_distance=s.dm_goal_min_distance, inflate_cells=inflate,
+                                               snap_cells=snap, radius_cells=s.gain_radius_cells())[0]
+            self.last_gain = None if g is None else int(g[3])
+        elif s.dm_goal_information_gain:
             g = self.mapper.assign_goals_gain([(x, y)], min_size=s.dm_goal_min_size,
                                               min_gain=s.dm_goal_min_gain,
                                               distance_weight=s.dm_goal_distance_weight,
@@ -648,7 +680,7 @@ def main(args=None):  # pragma: no cover - needs ROS 2
     from rclpy.node import Node
     from sensor_msgs.msg import LaserScan as RosLaserScan
     from nav_msgs.msg import OccupancyGrid as RosGrid, Path as RosPath
-    from geometry_msgs.msg import PoseArray, Pose as RosPose, PoseStamped as RosPoseStamped
+    from geometry_msgs.msg import PoseArray as RosPoseArray, Pose as RosPose, PoseStamped as RosPoseStamped
     import tf2_ros
 
     rclpy.init(args=args)
@@ -674,12 +706,12 @@ def main(args=None):  # pragma: no cover - needs ROS 2
         return (tr.translation.x, tr.translation.y, yaw_from_quaternion(tr.rotation))
 
     map_pub = node.create_publisher(RosGrid, "/map", 10)
-    fr_pub = node.create_publisher(PoseArray, "/frontiers", 10)
+    fr_pub = node.create_publisher(RosPoseArray, "/frontiers", 10)
     goal_pub = node.create_publisher(RosPoseStamped, "/goal_pose", 10)
 
     class _FrontierAdapter:
         def publish(self, clusters):
-            pa = PoseArray()
+            pa = RosPoseArray()
             pa.header.frame_id = sp.map_frame
             pa.header.stamp = node.get_clock().now().to_msg()
             for c in clusters:
@@ -716,6 +748,8 @@ def main(args=None):  # pragma: no cover - needs ROS 2
     mn = MappingNode(sp, pose_provider=lookup, map_publisher=map_pub, frontier_publisher=_FrontierAdapter(),
                      goal_publisher=_GoalAdapter(), plan_publisher=_PlanAdapter(), clock=lambda: node.get_clock().now().nanoseconds * 1e-9)
     node.create_subscription(RosLaserScan, sp.scan_topic, mn.scan_cb, 10)
+    if sp.dm_goal_coordinate:
+        node.create_subscription(RosPoseArray, sp.dm_peer_goals_topic, mn.peer_goals_cb, 10)
     # slam_toolbox publishes the map on its own period, not per scan
     node.create_timer(sp.map_update_interval, mn.timer_cb)
     node.create_timer(0.01, mn.poll_frontiers)  # frontiers go out as soon as the GPU pass is done

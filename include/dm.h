@@ -540,13 +540,70 @@ int dm_gain_views(dm_grid* g, const double* views_xy, int64_t n, int32_t radius_
  * "not eligible": a cluster with nothing to see is never a goal, even with
  * min_gain = 0.  out_gain[r] = the chosen cluster's gain (0: none).  A
  * cluster taken by an earlier robot does not discount what the others would
- * see: overlap-aware assignment is not implemented.  Replaces the reactive
+ * see: that is dm_assign_goals_coord, below.  Replaces the reactive
  * policy of main.py:123-188 like dm_assign_goals, with the next-best-view
  * score in place of the frontier's size. */
 int dm_assign_goals_gain(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size,
                          int64_t min_gain, double distance_weight, double min_distance, int32_t inflate_cells,
                          uint32_t max_cost, int32_t snap_cells, int32_t radius_cells, int64_t* out_index,
                          double* out_xy, int64_t* out_cell, uint32_t* out_gain);
+
+/* ---- Overlap-aware information gain.  Two frontier clusters that open onto
+ * the same unmapped hall both score the whole hall under dm_assign_goals_gain,
+ * and two robots are sent to look at the same cells.  These calls discount a
+ * view by what the views before it already see: the greedy coordinated
+ * assignment of multi-robot exploration.  The reference has no counterpart
+ * (its robots do not share goals; main.py:123-188).  All three are
+ * synchronous, ordered after everything enqueued on the handle, read the map
+ * and never write it, and do not change the map version (a dm_plan_field
+ * result and the matcher's cached field stay valid; dm_assign_goals_coord
+ * leaves its last robot's field, as dm_assign_goals_gain does).  They need a
+ * handle that covers the whole map: a band handle or a dm_create_sharded
+ * handle returns DM_ERR_INVALID_ARG.
+ *
+ * Definitions (integers only: every result is unique and bit-exact).
+ *   Visible set V(cell, R): the set of marked cells of the visible-unknown
+ *     count above; |V| is dm_gain_views' gain.
+ *   Claimed set C: a set of map cells, kept in the handle.
+ *   Marginal gain of a view: |V(cell, R) \ C|.
+ *   Commit of a view: C := C u V(cell, R).
+ * C is allocated by the first of the calls (height * ceil(width / 32) words;
+ * DM_ERR_OOM if that fails) and freed by dm_destroy. */
+
+/* The marginal gains of n views taken in order (n in [0, 1024]; radius_cells
+ * in [1, 511]).  The cell of a view is dm_gain_views'; a view outside the
+ * grid, or a non-finite one, gets out_cell[i] = -1 and out_marginal[i] = 0 and
+ * commits nothing.  C starts empty; for i = 0 .. n-1 in order
+ * out_marginal[i] = |V_i \ C|, then V_i is committed.  The sum of out_marginal
+ * is the number of distinct unknown cells the n views see together.  n or
+ * radius_cells out of range, or a NULL pointer with n > 0: DM_ERR_INVALID_ARG. */
+int dm_gain_views_joint(dm_grid* g, const double* views_xy, int64_t n, int32_t radius_cells,
+                        uint32_t* out_marginal, int64_t* out_cell);
+/* dm_assign_goals_gain with the marginal gain as the numerator.  The same:
+ * the clusters of the last collected result, the errors, the per-robot field
+ * and snap, dist, the eligibility tests ("gain 0 is never a goal" included),
+ * the greedy robot order, ties to the smaller label, the taken-cluster rule,
+ * n_robots <= 256, and the field left behind is the last robot's.  What
+ * changes: C starts as the union of V over the n_held held views (n_held in
+ * [0, 1024]; held_xy may be NULL when it is 0; a held view outside the grid or
+ * non-finite adds nothing) - the goals that teammates who are not replanning
+ * in this call already hold; a caller may also pass robot poses.  For robot r,
+ *   gain(r, c) = |V(snapped cell of c under r's field, R) \ C|
+ * with C as it stands when r chooses; when r gets a goal its view is committed
+ * before robot r + 1 is scored, and out_gain[r] is that marginal gain.  With
+ * n_held = 0, robot 0's result equals dm_assign_goals_gain's for the same
+ * inputs, bit for bit.  n_held out of range, or held_xy NULL with n_held > 0:
+ * DM_ERR_INVALID_ARG. */
+int dm_assign_goals_coord(dm_grid* g, const double* robots_xy, int32_t n_robots, const double* held_xy,
+                          int32_t n_held, int64_t min_size, int64_t min_gain, double distance_weight,
+                          double min_distance, int32_t inflate_cells, uint32_t max_cost, int32_t snap_cells,
+                          int32_t radius_cells, int64_t* out_index, double* out_xy, int64_t* out_cell,
+                          uint32_t* out_gain);
+/* The claimed set left by the last dm_gain_views_joint or
+ * dm_assign_goals_coord on the handle: out[height * width] = 1 / 0, row-major.
+ * A diagnostic and test entry, like dm_plan_traversable and dm_match_field.
+ * DM_ERR_STATE if neither call has run yet (or the last one failed). */
+int dm_gain_claimed(dm_grid* g, uint8_t* out);
 
 /* ---- Correlative scan matching against the device-resident map.  In the
  * reference the pose of a scan comes from slam_toolbox's correlative scan

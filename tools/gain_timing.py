@@ -8,9 +8,15 @@ lines:
   (dm_profile_read) and the host restatement's time per view for context;
 * dm_assign_goals_gain against dm_assign_goals_path on the same clusters and
   robots (1 and 16), so that the added cost of the gain is the difference of
-  two measured times.
+  two measured times;
+* dm_gain_views_joint for 1, 16 and 256 views at R = 240 (one launch per
+  view, so the wall time grows with the views), with the distinct cells the
+  views see together;
+* dm_assign_goals_coord against dm_assign_goals_gain on the same clusters and
+  robots (1 and 16): the cost of coordination is the difference of the two
+  wall times, the commit launches plus the recasts the dropped memo causes.
 
-    python tools/gain_timing.py [--out profiles/gain_timing.jsonl]
+    python tools/gain_timing.py [--out profiles/gain_timing.jsonl] [--calls views,goals,joint,coord]
 """
 import argparse
 import json
@@ -51,7 +57,7 @@ def free_points(st, p, n, rng):
     return np.stack([p.origin_x + (xs[pick] + 0.5) * p.resolution, p.origin_y + (ys[pick] + 0.5) * p.resolution], axis=1)
 
 
-def measure(G, reps, host_views):
+def measure(G, reps, host_views, calls=("views", "goals", "joint", "coord")):
     res = 0.05
     half = G * res / 2
     world = synth.make_world(0, -half, -half, half, half)
@@ -62,7 +68,7 @@ def measure(G, reps, host_views):
     lines = []
     with dm.OccupancyMapper(p) as m:
         m.set_state(st)
-        for n in (1, 64, 2048):
+        for n in (1, 64, 2048) if "views" in calls else ():
             views = free_points(st, p, n, rng)
             m.profile(True)
             m.profile_reset()
@@ -83,7 +89,7 @@ def measure(G, reps, host_views):
                 line["equal_to_host"] = bool(np.array_equal(hg, g[:k]))
             lines.append(line)
         cl = m.frontiers().clusters
-        for R in (1, 16):
+        for R in (1, 16) if "goals" in calls else ():
             robots = free_points(st, p, R, rng)
             kw = dict(min_size=8, inflate_cells=2, snap_cells=5)
             _, path_med, path_min = timed(lambda: m.assign_goals_path(robots, **kw), max(3, reps // 4), warmup=1)
@@ -103,6 +109,50 @@ def measure(G, reps, host_views):
                           "gain_views_kernel_ms_per_call": prof["gain_views"][1],
                           "gain_views_launches_per_call": prof["gain_views"][0],
                           "goals_found": sum(x is not None for x in got)})
+        rng = np.random.default_rng(6)  # the overlap-aware calls: their own points, whatever ran above
+        for n in (1, 16, 256) if "joint" in calls else ():
+            views = free_points(st, p, n, rng)
+            (mg, _), med, mn = timed(lambda: m.gain_views_joint(views, RADIUS), max(3, reps // 4), warmup=1)
+            (g, _), plain_med, _ = timed(lambda: m.gain_views(views, RADIUS), max(3, reps // 4), warmup=1)
+            m.profile(True)
+            m.profile_reset()
+            m.gain_views_joint(views, RADIUS)
+            prof = m.profile_read()
+            m.profile(False)
+            line = {"map": name, "call": "dm_gain_views_joint", "views": n, "radius_cells": RADIUS,
+                    "wall_ms_median": med, "wall_ms_min": mn, "dm_gain_views_wall_ms_median": plain_med,
+                    "gain_joint_kernels_ms_per_call": prof["gain_joint"][1],
+                    "distinct_cells_seen": int(mg.sum()), "sum_of_gains": int(g.sum())}
+            k = min(n, host_views)
+            if k:
+                hm, _, _ = gain.gain_views_joint(st, views[:k], p.origin_x, p.origin_y, p.resolution, RADIUS)
+                line["equal_to_host"] = bool(np.array_equal(hm, mg[:k]))
+            lines.append(line)
+        for R in (1, 16) if "coord" in calls else ():
+            robots = free_points(st, p, R, rng)
+            kw = dict(min_size=8, inflate_cells=2, snap_cells=5, radius_cells=RADIUS)
+            unc, gain_med, gain_min = timed(lambda: m.assign_goals_gain(robots, **kw), max(3, reps // 4), warmup=1)
+            got, coord_med, coord_min = timed(lambda: m.assign_goals_coord(robots, **kw), max(3, reps // 4), warmup=1)
+            m.profile(True)
+            m.profile_reset()
+            m.assign_goals_coord(robots, **kw)
+            prof = m.profile_read()
+            m.profile(False)
+            zero = (0, 0.0)
+            lines.append({"map": name, "call": "dm_assign_goals_coord vs dm_assign_goals_gain", "robots": R,
+                          "clusters": int(len(cl)), "clusters_of_min_size": int((cl["size"] >= 8).sum()),
+                          "radius_cells": RADIUS,
+                          "assign_goals_gain_wall_ms_median": gain_med, "assign_goals_gain_wall_ms_min": gain_min,
+                          "assign_goals_coord_wall_ms_median": coord_med, "assign_goals_coord_wall_ms_min": coord_min,
+                          "added_ms_median": coord_med - gain_med,
+                          "gain_marginal_kernel_ms_per_call": prof.get("gain_marginal", zero)[1],
+                          "gain_marginal_launches_per_call": prof.get("gain_marginal", zero)[0],
+                          "gain_commit_kernel_ms_per_call": prof.get("gain_commit", zero)[1],
+                          "gain_commit_launches_per_call": prof.get("gain_commit", zero)[0],
+                          "goals_found": sum(x is not None for x in got),
+                          "goals_that_differ": sum(a != b for a, b in zip(unc, got)),
+                          "cells_claimed": int(m.gain_claimed().sum()),
+                          "sum_of_uncoordinated_gains": sum(x[3] for x in unc if x is not None)})
     return lines
 
 
@@ -112,9 +162,10 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--host-views", type=int, default=8, help="views the host restatement is timed on (0: none)")
     ap.add_argument("--sizes", default="400,4096")
+    ap.add_argument("--calls", default="views,goals,joint,coord", help="which groups of lines to measure")
     args = ap.parse_args()
     for G in (int(s) for s in args.sizes.split(",")):
-        for line in measure(G, args.reps, args.host_views):
+        for line in measure(G, args.reps, args.host_views, tuple(args.calls.split(","))):
             ln = json.dumps(line)
             print(ln, flush=True)
             if args.out:
