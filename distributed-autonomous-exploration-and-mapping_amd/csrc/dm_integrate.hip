@@ -69,6 +69,28 @@ __device__ inline BeamChunk beam_chunk(const Geom& g, int64_t v) {
 
 __device__ inline int lane_id() { return __lane_id(); }
 
+// A wave's maximum / sum of v (every lane active; the result is uniform, in
+// a scalar register).  Within a 16-lane row by DPP (lane ^ 1, lane ^ 2, then
+// the half-row and row mirrors, which pair groups that are already uniform),
+// across the four rows by reading one lane of each.  A __shfl_xor butterfly
+// keeps six ds_bpermute byte addresses (one VGPR per step) live wherever it
+// is inlined; k_tile_accum held them across its whole item loop.
+template <class Op>
+__device__ inline int32_t wave_reduce(int32_t v, Op op) {
+  v = op(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
+  v = op(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
+  v = op(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));  // row_half_mirror
+  v = op(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));  // row_mirror
+  return op(op(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+            op(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+__device__ inline int32_t wave_max(int32_t v) {
+  return wave_reduce(v, [](int32_t a, int32_t b) { return max(a, b); });
+}
+__device__ inline int32_t wave_sum(int32_t v) {
+  return wave_reduce(v, [](int32_t a, int32_t b) { return a + b; });
+}
+
 // Per-block tile histogram in LDS (open addressing).  The 256 beams of a block
 // are consecutive beams of one scan, so their pieces fall in a few tens of
 // tiles: one global atomic per (block, tile) instead of one per piece, and no
@@ -651,8 +673,7 @@ struct CellRows {
 // cells at every step instead of piling a wave's atomics onto one LDS word.
 // The wave's trip count is its longest piece.
 __device__ inline int32_t walk_tp(uint32_t* tl, const TilePiece& tp, int32_t len, int lane) {
-  int32_t wl = len;
-  for (int o = 32; o > 0; o >>= 1) wl = max(wl, __shfl_xor(wl, o));
+  const int32_t wl = wave_max(len);
   const int32_t s0 = len > 0 ? lane % len : 0;
   PieceCursor cur;
   cur.init(tp);
@@ -693,8 +714,7 @@ __device__ inline int32_t walk_piece(uint32_t* tl, const PackedPiece& mine, bool
 __device__ inline int32_t walk_tp_split(uint32_t* tl, const TilePiece& tp, int32_t len, int32_t f, int32_t part,
                                         float rf, int lane) {
   const SplitPart sp = dm_split_part(len, f, part, rf);
-  int32_t wl = sp.n;
-  for (int o = 32; o > 0; o >>= 1) wl = max(wl, __shfl_xor(wl, o));
+  const int32_t wl = wave_max(sp.n);
   const int32_t spare = kTileWords + lane;
   PieceCursor cur;
   if (f == 1) cur.init(tp);
@@ -729,8 +749,7 @@ __device__ inline int32_t walk_piece_bytes(uint32_t* tq, const PackedPiece& mine
   TilePiece tp = dm_unpack_piece(mine.x, mine.y, mine.z, mine.w);
   const int32_t len = valid ? tp.len : 0;
   const SplitPart sp = dm_split_part(len, f, part, rf);
-  int32_t wl = sp.n;
-  for (int o = 32; o > 0; o >>= 1) wl = max(wl, __shfl_xor(wl, o));
+  const int32_t wl = wave_max(sp.n);
   tp.addr0 = to_pitch64(tp.addr0);
   tp.da = to_pitch64(tp.da);
   tp.db = to_pitch64(tp.db);
@@ -859,11 +878,22 @@ __device__ inline void heavy_quarter(const Geom& g, const ApplyArgs& p, int64_t 
 // The next item's pieces are loaded right after this item's apply, its
 // cells (unconditional loads: a fixed count, so the walk waits for the pieces
 // alone with vmcnt(N)) at the top of its iteration, in flight during its
-// walk.  7 workgroups per CU (72 VGPRs, no spills): C3's ~3.8k items in ~2
-// rounds of the chip's slots (41 us vs 43.5 us at 6).  The per-item statistics stay in thread 0's registers (one flush per
+// walk.  The per-item statistics stay in thread 0's registers (one flush per
 // workgroup) and a light tile's free count is a plain read-modify-write (one
 // workgroup owns the tile), so no memory-side atomic sits in front of the
 // next item's loads in the wave's in-order vmcnt queue.
+//
+// Registers (the compiler's resource summary with the Makefile's flags,
+// pinned by tests/test_kernel_resources.py): 64 VGPRs, no scratch, no
+// spilled VGPR, 21 SGPRs spilled into lanes of one VGPR, 19 024 B of LDS.
+// The launch bounds ask for 7 workgroups per CU (a budget of 72 VGPRs); at
+// 64 VGPRs and 19 KB of LDS a CU holds 8, and that eighth workgroup is what
+// the step gains (bounds of 8 measure the same, 7 resident
+// workgroups forced by LDS measure slower).  What keeps it at 64: wave_max /
+// wave_sum instead of shuffle butterflies, and the thread index made opaque
+// once per item, so that nothing derived from it lives across the item loop.
+// Until both were in, this kernel ran with 72 VGPRs, 13 more spilled and 44 B
+// of scratch per lane, 7 per CU.
 #ifndef DM_ACCUM_OCC
 #define DM_ACCUM_OCC 7
 #endif
@@ -878,7 +908,7 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
   __shared__ uint32_t tl[kTileWords + 64];  // + one spare word per lane (walk_tp_split)
   __shared__ int32_t s_T, s_free, s_last;
   __shared__ uint32_t s_U;
-  const int tid = threadIdx.x, lane = lane_id();
+  int tid = threadIdx.x;  // (one-dimensional workgroups of whole waves: the lane is tid % 64)
   DM_TL_BEGIN();
   // The halt word and the item counts in one round of loads (a workgroup
   // runs about one item at C3, so its first item's dependent loads -- counts,
@@ -921,7 +951,6 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
     d.z = (int64_t)d.y + d.z <= g.seg_cap ? d.z : 0;
     return d;
   };
-  const int cx = (tid & 15) * 4;
   __shared__ unsigned long long s_accT, s_accU;  // this workgroup's light-tile totals
   // the first item's loads
   int4 info = item_of(blockIdx.x);
@@ -959,6 +988,13 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
   [[maybe_unused]] unsigned long long tl_word = 0;  // timeline (phase build): dense items | sparse << 16 | finisher ticks << 32
   for (int64_t it = blockIdx.x; it < n_items; it += G) {
     tl_word += 1;
+    // The thread index anew per item (as k_frontier_tile_big): what is
+    // derived from it -- the lane, cx, LDS and slab addresses, and the sparse
+    // loop's wave index, which the compiler hoists up here too -- is
+    // recomputed where it is used instead of held, and spilled, across the
+    // item loop.
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, cx = (tid & 15) * 4;
     // the descriptor is workgroup-uniform: scalar registers, scalar branches
     const int32_t tile = __builtin_amdgcn_readfirstlane(info.x);
     const int32_t c0 = __builtin_amdgcn_readfirstlane(info.y);
@@ -1056,7 +1092,7 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
       }
       const bool inside = tx0 + DM_TS <= g.r.W && ty0 + DM_TS <= g.r.R;  // workgroup-uniform
       if (inside) {
-        for (int o = 32; o > 0; o >>= 1) u += __shfl_xor(u, o);
+        u = wave_sum(u);
         if (lane == 0) atomicAdd(&s_U, (uint32_t)u);
       }
       mine_n = load_pieces(next);
@@ -1102,16 +1138,22 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
   // four waves' tiles share the LDS of one dense count tile.  A wave walks,
   // applies and clears its own tile with no workgroup barrier (LDS operations
   // of one wave complete in order; the wavefront fences keep the compiler
-  // from moving them), so a CU keeps 4 x 7 = 28 sparse tiles in flight.
+  // from moving them), so a CU keeps 4 x 8 = 32 sparse tiles in flight.
   __shared__ int32_t s_wT[kQuarter / 64], s_wfree[kQuarter / 64];
   __shared__ uint32_t s_wU[kQuarter / 64];
   __shared__ uint16_t s_list[kQuarter / 64][kSparseList];  // touched 4-cell groups of each wave's tile
-  const int wv = tid >> 6;
-  uint32_t* tq = tl + wv * (DM_TS * DM_TS / 4);
-  const int hcx = (lane & 15) * 4;
-  if (lane == 0) { s_wT[wv] = 0; s_wfree[wv] = 0; s_wU[wv] = 0u; }
+  // (the thread index anew, as above: nothing of this loop is computed before
+  // the dense items, and each item recomputes its lane's LDS addresses.  The
+  // wave index as a scalar: the item, its descriptor and what is derived
+  // from it -- tile origin, split factor -- then sit in scalar registers.)
+  asm volatile("" : "+v"(tid));
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if ((tid & 63) == 0) { s_wT[wv] = 0; s_wfree[wv] = 0; s_wU[wv] = 0u; }
   const int nw = kQuarter / 64;
   for (int64_t it = sp_rank * nw + wv; it < SI; it += (int64_t)G * nw) {
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, hcx = (tid & 15) * 4;
+    uint32_t* tq = tl + wv * (DM_TS * DM_TS / 4);
     int4 d = list_b[(int64_t)g.act_cap - 1 - it];
     d.z = (int64_t)d.y + d.z <= g.seg_cap ? d.z : 0;  // never past the piece array
     const int32_t tile = d.x, c0 = d.y, c = d.z;
@@ -1127,7 +1169,7 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
     const bool inside = tx0 + DM_TS <= g.r.W && ty0 + DM_TS <= g.r.R;  // uniform in the wave
     uint32_t wU = 0u;
     if (inside) {
-      for (int o = 32; o > 0; o >>= 1) u += __shfl_xor(u, o);
+      u = wave_sum(u);
       wU = (uint32_t)u;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
