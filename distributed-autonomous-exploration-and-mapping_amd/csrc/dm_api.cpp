@@ -542,6 +542,10 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   // and DM_PLAN_MAX_ROUNDS: the distance field's round bound (dm_plan_field's
   // DM_ERR_INCOMPLETE path; a complete field is the same under any bound)
   if (const char* pr = getenv("DM_PLAN_MAX_ROUNDS")) g->plan_max_rounds = std::max<int64_t>(0, atoll(pr));
+  // and DM_MATCH_GLOBAL_BATCH: the most blocks one round of dm_match_global
+  // refines (its result is the same under any value)
+  if (const char* mb = getenv("DM_MATCH_GLOBAL_BATCH"))
+    g->mg_batch = std::min<int64_t>(std::max<int64_t>(1, atoll(mb)), dm_grid::kMgExhaustiveBatch);
   for (auto& f : g->fw) {
     e = hipEventCreateWithFlags(&f.ev_split, hipEventDisableTiming | hipEventDisableSystemFence);
     if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
@@ -672,6 +676,9 @@ int dm_destroy(dm_grid* g) {
   dev_free(g->match_V); dev_free(g->match_kern); dev_free(g->match_tiles); dev_free(g->match_pose4);
   dev_free(g->match_trig); dev_free(g->match_ranges); dev_free(g->match_q); dev_free(g->match_vol);
   dev_free(g->match_out);
+  dev_free(g->mg_pool); dev_free(g->mg_ptiles); dev_free(g->mg_bound); dev_free(g->mg_hist); dev_free(g->mg_ctl);
+  dev_free(g->mg_list); dev_free(g->mg_nused); dev_free(g->mg_cand); dev_free(g->mg_best);
+  if (g->h_mg) (void)hipHostFree(g->h_mg);
   dev_free(g->gain_xy); dev_free(g->gain_cell); dev_free(g->gain_out); dev_free(g->gain_skip);
   dev_free(g->gain_memo_cell); dev_free(g->gain_memo_gain); dev_free(g->gain_claimed);
   for (auto& w : g->iw) {
@@ -1896,6 +1903,7 @@ static int match_set_table(dm_grid* g, int32_t r, const uint8_t* kern) {
     return DM_OK;
   g->match_r = -1;
   g->match_built.assign((size_t)g->NT, 0);
+  ++g->match_epoch;
   g->match_kern_h.assign(kern, kern + n);
   // pageable source: the copy is staged before the call returns
   DM_HIP(hipMemcpyAsync(g->match_kern, g->match_kern_h.data(), n, hipMemcpyHostToDevice, g->stream));
@@ -2025,6 +2033,190 @@ int dm_match_scans(dm_grid* g, int32_t S, const double* poses, int32_t N, const 
     out_pose[3 * s] = poses[3 * s] + (double)(i * stride) * step;
     out_pose[3 * s + 1] = poses[3 * s + 1] + (double)(j * stride) * step;
     out_pose[3 * s + 2] = poses[3 * s + 2] + yaw_offsets[k];
+  }
+  return DM_OK;
+}
+
+// ---- whole-window relocalisation (csrc/dm_match_global.h) -----------------------
+
+static int ensure_match_global(dm_grid* g) {
+  int rc = DM_OK;
+  if (!g->h_mg) {
+    hipError_t e = hipHostMalloc((void**)&g->h_mg, sizeof(uint32_t) * 8, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess) {
+      g->h_mg = nullptr;
+      return dm_hip_check(e, "hipHostMalloc(relocalisation rounds)");
+    }
+    memset(g->h_mg, 0, sizeof(uint32_t) * 8);
+    DM_HIP(hipHostGetDevicePointer((void**)&g->h_mg_dev, g->h_mg, 0));
+  }
+  if (g->mg_best) return DM_OK;  // allocated last
+  if ((rc = dev_alloc(&g->mg_hist, 2048, "bound histogram"))) return rc;
+  if ((rc = dev_alloc(&g->mg_ctl, 4, "round control words"))) return rc;
+  if ((rc = dev_alloc(&g->mg_list, dm_grid::kMgExhaustiveBatch, "round block list"))) return rc;
+  if ((rc = dev_alloc(&g->mg_cand, dm_grid::kMgExhaustiveBatch, "round candidates"))) return rc;
+  if ((rc = dev_alloc(&g->mg_nused, 1, "used beams"))) return rc;
+  return dev_alloc(&g->mg_best, 1, "best candidate");
+}
+
+int dm_match_global(dm_grid* g, int32_t S, const double* poses, int32_t N, const float* ranges, float angle_min,
+                    float angle_increment, int32_t A, const double* yaw_offsets, int32_t k0, int32_t half_x,
+                    int32_t half_y, int32_t block, int32_t exhaustive, int32_t smear_cells, const uint8_t* kern,
+                    int32_t* out_best, uint32_t* out_score, int32_t* out_n_used, double* out_pose,
+                    uint64_t* out_stats) {
+  int rc = plan_check_handle(g, "dm_match_global");
+  if (rc || (rc = use_device(g))) return rc;
+  if ((rc = check_integrate_args(S, N, poses, ranges))) return rc;
+  if (A < 1 || A > 1024) return dm_set_error(DM_ERR_INVALID_ARG, "A must be in [1, 1024] (got %d)", A);
+  if (k0 < 0 || k0 >= A) return dm_set_error(DM_ERR_INVALID_ARG, "k0 must be in [0, A) (got %d, A = %d)", k0, A);
+  if (half_x < 0 || half_x > 4096 || half_y < 0 || half_y > 4096)
+    return dm_set_error(DM_ERR_INVALID_ARG, "half_x and half_y must be in [0, 4096] (got %d, %d)", half_x, half_y);
+  if (block != 4 && block != 8 && block != 16 && block != 32)
+    return dm_set_error(DM_ERR_INVALID_ARG, "block must be 4, 8, 16 or 32 (got %d)", block);
+  if (exhaustive != 0 && exhaustive != 1)
+    return dm_set_error(DM_ERR_INVALID_ARG, "exhaustive must be 0 or 1 (got %d)", exhaustive);
+  if ((rc = match_check_table(smear_cells, kern))) return rc;
+  if (!yaw_offsets) return dm_set_error(DM_ERR_INVALID_ARG, "yaw_offsets is NULL");
+  if (S > 0 && (!poses || !out_best || !out_score || !out_n_used || !out_pose))
+    return dm_set_error(DM_ERR_INVALID_ARG, "poses / out_best / out_score / out_n_used / out_pose is NULL");
+  if ((int64_t)A * std::max(N, 1) > (1ll << 31) - 1) return dm_set_error(DM_ERR_SHAPE, "A*N must be < 2^31");
+  if (g->W > (1ll << 20) || g->H > (1ll << 20))
+    return dm_set_error(DM_ERR_SHAPE, "dm_match_global needs a map of at most 2^20 cells a side");
+  MgShape sh;
+  sh.N = N;
+  sh.A = A;
+  sh.k0 = k0;
+  sh.half_x = half_x;
+  sh.half_y = half_y;
+  sh.lb = block == 4 ? 2 : block == 8 ? 3 : block == 16 ? 4 : 5;
+  sh.nbx = (2 * half_x + 1 + block - 1) / block;
+  sh.nby = (2 * half_y + 1 + block - 1) / block;
+  sh.exhaustive = exhaustive;
+  const int64_t blocks = (int64_t)A * sh.nbx * sh.nby;
+  if (blocks > (1ll << 26))
+    return dm_set_error(DM_ERR_CAPACITY, "%lld blocks per scan, the limit is 2^26: use a larger block (got %d)",
+                        (long long)blocks, block);
+  // the pooled field's extended coordinates e = c + block - 1, padded to whole blocks
+  const int64_t EWB = (g->W + block - 1 + block - 1) / block, EHB = (g->H + block - 1 + block - 1) / block;
+  if ((int64_t)block * block * EWB * EHB > (1ll << 31) - 1)
+    return dm_set_error(DM_ERR_SHAPE, "dm_match_global: the pooled field of this map needs 2^31 bytes or more");
+  sh.EWB = (int32_t)EWB;
+  sh.EHB = (int32_t)EHB;
+  const int64_t PTX = (EWB * block + 63) / 64, PTY = (EHB * block + 63) / 64;
+  if (S == 0) return DM_OK;
+  DM_HIP(dm_sync_all(g));  // after everything enqueued on the handle, on every stream of it
+  if ((rc = match_set_table(g, smear_cells, kern))) return rc;
+  if ((rc = ensure_match_global(g))) return rc;
+
+  const int64_t SA = (int64_t)S * A, nbm = (int64_t)S * N;
+  if ((rc = dev_grow(&g->match_pose4, &g->match_pose_cap, 4 * SA, "candidate poses")) ||
+      (rc = dev_grow(&g->match_trig, &g->match_trig_cap, 2 * (int64_t)N, "beam angle table")) ||
+      (rc = dev_grow(&g->match_ranges, &g->match_ranges_cap, nbm, "ranges")) ||
+      (rc = dev_grow(&g->match_q, &g->match_q_cap, (int64_t)A * N, "fine coordinates")))
+    return rc;
+  if (!exhaustive) {
+    if ((rc = dev_grow(&g->mg_bound, &g->mg_bound_cap, blocks, "block bounds")) ||
+        (rc = dev_grow(&g->mg_pool, &g->mg_pool_cap, (int64_t)block * block * EWB * EHB, "pooled response field")) ||
+        (rc = dev_grow(&g->mg_ptiles, &g->mg_ptiles_cap, PTX * PTY, "pool tile list")))
+      return rc;
+    if (g->mg_pool_block != block || g->mg_pool_epoch != g->match_epoch ||
+        g->mg_pool_built.size() != (size_t)(PTX * PTY)) {
+      g->mg_pool_built.assign((size_t)(PTX * PTY), 0);
+      g->mg_pool_block = block;
+      g->mg_pool_epoch = g->match_epoch;
+    }
+  }
+
+  const double res = g->p.resolution;
+  std::vector<double> trig(2 * (size_t)N), pose4(4 * (size_t)SA);
+  for (int32_t i = 0; i < N; ++i) {
+    const double phi = (double)angle_min + (double)i * (double)angle_increment;
+    trig[2 * (size_t)i] = cos(phi);
+    trig[2 * (size_t)i + 1] = sin(phi);
+  }
+  for (int32_t s = 0; s < S; ++s)
+    for (int32_t k = 0; k < A; ++k) {
+      const double yk = poses[3 * s + 2] + yaw_offsets[k];
+      double* p4 = &pose4[4 * ((size_t)s * A + k)];
+      p4[0] = poses[3 * s];
+      p4[1] = poses[3 * s + 1];
+      p4[2] = cos(yk);
+      p4[3] = sin(yk);
+    }
+  hipStream_t st = g->stream;
+  DM_HIP(hipMemcpyAsync(g->match_pose4, pose4.data(), sizeof(double) * pose4.size(), hipMemcpyHostToDevice, st));
+  if (N > 0) {
+    DM_HIP(hipMemcpyAsync(g->match_trig, trig.data(), sizeof(double) * trig.size(), hipMemcpyHostToDevice, st));
+    DM_HIP(hipMemcpyAsync(g->match_ranges, ranges, sizeof(float) * (size_t)nbm, hipMemcpyHostToDevice, st));
+  }
+  DM_HIP(hipStreamSynchronize(st));  // pose4 and trig are locals
+
+  for (int32_t s = 0; s < S; ++s) {
+    const double x = poses[3 * s], y = poses[3 * s + 1];
+    int32_t r5[5] = {k0, 0, 0, 0, 0};
+    uint64_t stats[4] = {(uint64_t)blocks, 0, 0, 0};
+    if (N > 0 && isfinite(x) && isfinite(y)) {
+      // the cells the window reaches: every used beam ends within range_max of
+      // the pose and a translation moves it by at most half cells; two cells
+      // of slack cover the rounding of the endpoint arithmetic
+      const double reach_x = (double)g->p.range_max + (double)(half_x + 1) * res + 2.0 * res;
+      const double reach_y = (double)g->p.range_max + (double)(half_y + 1) * res + 2.0 * res;
+      const double fx0 = floor((x - reach_x - g->p.origin_x) / res) - 1.0;
+      const double fx1 = floor((x + reach_x - g->p.origin_x) / res) + 1.0;
+      const double fy0 = floor((y - reach_y - g->p.origin_y) / res) - 1.0;
+      const double fy1 = floor((y + reach_y - g->p.origin_y) / res) + 1.0;
+      std::vector<uint8_t> want((size_t)g->NT, 0);
+      std::vector<int32_t> plist;
+      if (exhaustive) {
+        if (fx1 >= 0.0 && fy1 >= 0.0 && fx0 < (double)g->W && fy0 < (double)g->H) {
+          const int64_t tx0 = (int64_t)std::max(fx0, 0.0) / DM_TILE, ty0 = (int64_t)std::max(fy0, 0.0) / DM_TILE;
+          const int64_t tx1 = (int64_t)std::min(fx1, (double)(g->W - 1)) / DM_TILE;
+          const int64_t ty1 = (int64_t)std::min(fy1, (double)(g->H - 1)) / DM_TILE;
+          for (int64_t ty = ty0; ty <= ty1; ++ty)
+            for (int64_t tx = tx0; tx <= tx1; ++tx) want[(size_t)(ty * g->TX + tx)] = 1;
+        }
+      } else {
+        // M_B is read at the cells c in [f0, f1] with c >= -(block - 1): the
+        // pool tiles that hold them, and for each the field tiles its patch
+        // [64 p - (block - 1), 64 p + 63] meets
+        const double lo = -(double)(block - 1);
+        if (fx1 >= lo && fy1 >= lo && fx0 < (double)g->W && fy0 < (double)g->H) {
+          const int64_t px0 = ((int64_t)std::max(fx0, lo) + block - 1) / 64;
+          const int64_t py0 = ((int64_t)std::max(fy0, lo) + block - 1) / 64;
+          const int64_t px1 = ((int64_t)std::min(fx1, (double)(g->W - 1)) + block - 1) / 64;
+          const int64_t py1 = ((int64_t)std::min(fy1, (double)(g->H - 1)) + block - 1) / 64;
+          for (int64_t py = py0; py <= py1; ++py)
+            for (int64_t px = px0; px <= px1; ++px) {
+              if (!g->mg_pool_built[(size_t)(py * PTX + px)]) plist.push_back((int32_t)(py * PTX + px));
+              const int64_t tx0 = std::max<int64_t>(64 * px - (block - 1), 0) / DM_TILE;
+              const int64_t ty0 = std::max<int64_t>(64 * py - (block - 1), 0) / DM_TILE;
+              const int64_t tx1 = std::min<int64_t>(px, g->TX - 1), ty1 = std::min<int64_t>(py, g->NT / g->TX - 1);
+              for (int64_t ty = ty0; ty <= ty1; ++ty)
+                for (int64_t tx = tx0; tx <= tx1; ++tx) want[(size_t)(ty * g->TX + tx)] = 1;
+            }
+        }
+      }
+      if ((rc = match_build_tiles(g, want))) return rc;
+      if (!plist.empty()) {
+        DM_HIP(hipMemcpyAsync(g->mg_ptiles, plist.data(), sizeof(int32_t) * plist.size(), hipMemcpyHostToDevice, st));
+        DM_HIP(hipStreamSynchronize(st));  // `plist` is a local
+        if ((rc = dm_mg_launch_pool(g, (int32_t)plist.size(), sh.lb, sh.EWB, sh.EHB, (int32_t)PTX))) return rc;
+        for (int32_t t : plist) g->mg_pool_built[(size_t)t] = 1;
+      }
+      if ((rc = dm_mg_run_scan(g, sh, g->match_pose4 + 4 * (size_t)s * A, g->match_ranges + (size_t)s * N, r5, stats)))
+        return rc;
+    }
+    const int32_t k = r5[0], i = r5[1], j = r5[2];
+    out_best[3 * s] = k;
+    out_best[3 * s + 1] = i;
+    out_best[3 * s + 2] = j;
+    out_score[s] = (uint32_t)r5[3];
+    out_n_used[s] = r5[4];
+    out_pose[3 * s] = poses[3 * s] + (double)i * res;
+    out_pose[3 * s + 1] = poses[3 * s + 1] + (double)j * res;
+    out_pose[3 * s + 2] = poses[3 * s + 2] + yaw_offsets[k];
+    if (out_stats)
+      for (int m = 0; m < 4; ++m) out_stats[4 * s + m] = stats[m];
   }
   return DM_OK;
 }

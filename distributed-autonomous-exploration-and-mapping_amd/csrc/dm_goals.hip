@@ -20,6 +20,7 @@
 #include "dm_gain.h"
 #include "dm_internal.h"
 #include "dm_match.h"
+#include "dm_match_global.h"
 #include "dm_plan.h"
 
 namespace {
@@ -388,6 +389,119 @@ int dm_match_launch_scans(dm_grid* g, int32_t S, int32_t N, int32_t A, int32_t k
   hipLaunchKernelGGL(k_match_best, dim3((unsigned)S), dim3(kThreads), 0, s, g->match_vol, A, half, k0, g->match_out);
   DM_HIP(hipGetLastError());
   dm_timer_end(g, &t);
+  return DM_OK;
+}
+
+// ---- whole-window relocalisation (dm_match_global.h) ---------------------------
+
+int dm_mg_launch_pool(dm_grid* g, int32_t n_tiles, int32_t lb, int32_t EWB, int32_t EHB, int32_t PTX) {
+  if (n_tiles <= 0) return DM_OK;
+  KernelTimer t;
+  dm_timer_begin(g, "mg_pool", &t);
+  hipLaunchKernelGGL(dm_mg::k_mg_pool, dim3((unsigned)n_tiles), dim3(dm_mg::kThreads), 0, g->stream, g->match_V, g->W,
+                     g->H, lb, EWB, EHB, PTX, g->mg_ptiles, g->mg_pool);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  return DM_OK;
+}
+
+int dm_mg_run_scan(dm_grid* g, const MgShape& sh, const double* d_pose4, const float* d_ranges, int32_t* res,
+                   uint64_t* stats) {
+  using namespace dm_mg;
+  hipStream_t s = g->stream;
+  Cand* best = (Cand*)g->mg_best;
+  Cand* cand = (Cand*)g->mg_cand;
+  const int32_t N = sh.N, A = sh.A, nb = sh.nbx * sh.nby;
+  const int64_t blocks = (int64_t)A * nb;
+  KernelTimer t;
+  hipLaunchKernelGGL(k_mg_init, dim3(1), dim3(64), 0, s, best, sh.k0, g->mg_nused);
+  DM_HIP(hipGetLastError());
+  {
+    MatchArgs a;
+    a.N = N;
+    a.ox = g->p.origin_x;
+    a.oy = g->p.origin_y;
+    a.step = g->p.resolution;  // sub = 1
+    a.range_min = g->p.range_min;
+    a.range_max = g->p.range_max;
+    dm_timer_begin(g, "match_prep", &t);
+    hipLaunchKernelGGL(dm_match::k_match_prep, dim3((unsigned)A, (unsigned)((N + kThreads - 1) / kThreads)),
+                       dim3(dm_match::kThreads), 0, s, a, d_pose4, d_ranges, g->match_trig, A, sh.k0, g->match_q,
+                       g->mg_nused);
+    DM_HIP(hipGetLastError());
+    dm_timer_end(g, &t);
+  }
+  uint64_t refined = 0, rounds = 0;
+  if (sh.exhaustive) {
+    for (int64_t base = 0; base < blocks; base += dm_grid::kMgExhaustiveBatch) {
+      const int32_t n = (int32_t)std::min<int64_t>(dm_grid::kMgExhaustiveBatch, blocks - base);
+      dm_timer_begin(g, "mg_refine", &t);
+      hipLaunchKernelGGL(k_mg_refine, dim3((unsigned)n), dim3(kThreads), 0, s, g->match_q, N, g->match_V, g->W, g->H,
+                         sh.lb, sh.half_x, sh.half_y, sh.nbx, nb, sh.k0, (const int32_t*)nullptr, (int32_t)base,
+                         (const uint32_t*)nullptr, n, cand);
+      DM_HIP(hipGetLastError());
+      dm_timer_end(g, &t);
+      dm_timer_begin(g, "mg_fold", &t);
+      hipLaunchKernelGGL(k_mg_fold, dim3(1), dim3(kThreads), 0, s, cand, (const uint32_t*)nullptr, n, sh.k0, best,
+                         g->mg_nused, g->h_mg_dev);
+      DM_HIP(hipGetLastError());
+      dm_timer_end(g, &t);
+      refined += (uint64_t)n;
+      ++rounds;
+    }
+    DM_HIP(hipStreamSynchronize(s));
+  } else {
+    dm_timer_begin(g, "mg_bound", &t);
+    hipLaunchKernelGGL(k_mg_bound, dim3((unsigned)((nb + kThreads - 1) / kThreads), (unsigned)A), dim3(kThreads), 0, s,
+                       g->match_q, N, g->mg_pool, sh.lb, sh.EWB, sh.EHB, sh.half_x, sh.half_y, sh.nbx, nb,
+                       g->mg_bound);
+    DM_HIP(hipGetLastError());
+    dm_timer_end(g, &t);
+    // rounds: the blocks whose bound reaches the best exact score so far (and
+    // 1), the highest bounds first; few in the first round, when nothing is
+    // known yet, then up to mg_batch
+    const uint32_t hi = 255u * (uint32_t)N;
+    const unsigned scan_grid = (unsigned)std::min<int64_t>((blocks + kThreads - 1) / kThreads, 2048);
+    uint32_t s_best = 0;
+    uint32_t cap = (uint32_t)std::min<int64_t>(g->mg_batch, 8);
+    for (;;) {
+      const uint32_t lo = std::max(s_best, 1u);
+      DM_HIP(hipMemsetAsync(g->mg_hist, 0, sizeof(uint32_t) * kBins, s));
+      dm_timer_begin(g, "mg_select", &t);
+      hipLaunchKernelGGL(k_mg_hist, dim3(scan_grid), dim3(kThreads), 0, s, g->mg_bound, blocks, lo, hi, g->mg_hist);
+      hipLaunchKernelGGL(k_mg_pick, dim3(1), dim3(kThreads), 0, s, g->mg_hist, cap, g->mg_ctl);
+      hipLaunchKernelGGL(k_mg_compact, dim3(scan_grid), dim3(kThreads), 0, s, g->mg_bound, blocks, lo, hi, g->mg_ctl,
+                         g->mg_list);
+      DM_HIP(hipGetLastError());
+      dm_timer_end(g, &t);
+      dm_timer_begin(g, "mg_refine", &t);
+      hipLaunchKernelGGL(k_mg_refine, dim3(cap), dim3(kThreads), 0, s, g->match_q, N, g->match_V, g->W, g->H, sh.lb,
+                         sh.half_x, sh.half_y, sh.nbx, nb, sh.k0, g->mg_list, 0, g->mg_ctl, 0, cand);
+      DM_HIP(hipGetLastError());
+      dm_timer_end(g, &t);
+      dm_timer_begin(g, "mg_fold", &t);
+      hipLaunchKernelGGL(k_mg_fold, dim3(1), dim3(kThreads), 0, s, cand, g->mg_ctl, 0, sh.k0, best, g->mg_nused,
+                         g->h_mg_dev);
+      DM_HIP(hipGetLastError());
+      dm_timer_end(g, &t);
+      DM_HIP(hipStreamSynchronize(s));
+      const uint32_t n = g->h_mg[4];
+      if (n == 0) break;  // no unrefined block can reach the best score: it is exact
+      refined += n;
+      ++rounds;
+      s_best = g->h_mg[0];
+      cap = (uint32_t)std::min<int64_t>(g->mg_batch, (int64_t)cap * 4);
+    }
+  }
+  res[0] = (int32_t)g->h_mg[1];
+  res[1] = (int32_t)g->h_mg[2];
+  res[2] = (int32_t)g->h_mg[3];
+  res[3] = (int32_t)g->h_mg[0];
+  res[4] = (int32_t)g->h_mg[5];
+  stats[0] = (uint64_t)blocks;
+  stats[1] = sh.exhaustive ? 0 : (uint64_t)blocks;
+  stats[2] = refined;
+  stats[3] = rounds;
   return DM_OK;
 }
 

@@ -539,6 +539,34 @@ struct dm_grid {
   int64_t match_vol_cap = 0;
   int32_t* match_out = nullptr;       // [S][4] k, i, j, score, then [S] used beams
   int64_t match_out_cap = 0;
+  uint64_t match_epoch = 0;           // bumped whenever match_built is dropped (new table or map version)
+
+  // whole-window relocalisation (dm_match_global.h; dm_match_global), allocated
+  // on first use.  mg_pool is the max-pooled field M_B of match_V for block
+  // size mg_pool_block, decimated by phase, built for the 64 x 64 tiles of
+  // extended coordinates flagged in mg_pool_built; it is dropped with the
+  // field (mg_pool_epoch != match_epoch) and on another block size.
+  uint8_t* mg_pool = nullptr;         // [B][B][EHB][EWB]
+  int64_t mg_pool_cap = 0;
+  int32_t* mg_ptiles = nullptr;       // pool tiles to build
+  int64_t mg_ptiles_cap = 0;
+  std::vector<uint8_t> mg_pool_built; // [PTY][PTX] host flags
+  int32_t mg_pool_block = 0;
+  uint64_t mg_pool_epoch = 0;
+  uint32_t* mg_bound = nullptr;       // [A][nby][nbx] bounds of one scan; 0 once refined
+  int64_t mg_bound_cap = 0;
+  uint32_t* mg_hist = nullptr;        // [kBins]
+  uint32_t* mg_ctl = nullptr;         // [C_WORDS] the round's count, bin and cap
+  int32_t* mg_list = nullptr;         // [mg_batch] the round's blocks
+  int4* mg_cand = nullptr;            // [kMgExhaustiveBatch >= mg_batch] dm_mg::Cand (16 bytes)
+  int4* mg_best = nullptr;            // dm_mg::Cand, the running best
+  int32_t* mg_nused = nullptr;        // the scan's used beams
+  uint32_t* h_mg = nullptr;           // mapped [8]: score, k, i, j, blocks of the round, used beams
+  uint32_t* h_mg_dev = nullptr;       // its device address
+  // DM_MATCH_GLOBAL_BATCH (read at dm_create): the most blocks one round
+  // refines; any value gives the same result
+  int64_t mg_batch = 4096;
+  static constexpr int32_t kMgExhaustiveBatch = 65536;
 
   // information gain (dm_gain.h; dm_gain_views and dm_assign_goals_gain),
   // grown on demand
@@ -763,6 +791,20 @@ int dm_match_launch_field(dm_grid* g, int32_t n_tiles, int32_t r, bool mono);
 // volume (g->match_vol) and the best candidates (g->match_out) of S scans
 int dm_match_launch_scans(dm_grid* g, int32_t S, int32_t N, int32_t A, int32_t k0, int32_t sub, int32_t half,
                           int32_t stride);
+// whole-window relocalisation (dm_match_global.h, launched from dm_goals.hip);
+// the mg_* arrays of the handle are allocated by the caller (dm_api.cpp)
+struct MgShape {
+  int32_t N, A, k0, half_x, half_y, lb;  // block = 1 << lb
+  int32_t nbx, nby;                      // blocks per yaw along x and y
+  int32_t EWB, EHB;                      // the pooled field's planes: [EHB][EWB]
+  int32_t exhaustive;
+};
+// M_B of the first n_tiles tiles of g->mg_ptiles (PTX tiles per row) into g->mg_pool
+int dm_mg_launch_pool(dm_grid* g, int32_t n_tiles, int32_t lb, int32_t EWB, int32_t EHB, int32_t PTX);
+// One scan: candidate poses d_pose4 [A][4], ranges d_ranges [N], g->match_trig.
+// Synchronous.  res = k, i, j, score, used beams; stats [4] as dm_match_global's.
+int dm_mg_run_scan(dm_grid* g, const MgShape& sh, const double* d_pose4, const float* d_ranges, int32_t* res,
+                   uint64_t* stats);
 int dm_launch_ld06(dm_grid* g, int32_t S, const dm_ld06_point* d_pts, const int64_t* d_offsets,
                    int32_t N, int dir, float* d_ranges, float* d_intensities);
 

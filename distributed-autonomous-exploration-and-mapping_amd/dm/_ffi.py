@@ -192,6 +192,8 @@ SIGNATURES = {
     "dm_match_field": [_vp, _i32, _vp, _vp],
     "dm_match_scans": [_vp, _i32, _vp, _i32, _vp, _f32, _f32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp,
                        _vp, _vp, _vp, _vp, _vp],
+    "dm_match_global": [_vp, _i32, _vp, _i32, _vp, _f32, _f32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
+                        _vp, _vp, _vp, _vp, _vp],
 }
 # functions returning const char*
 STRING_FUNCS = ("dm_last_error", "dm_version")

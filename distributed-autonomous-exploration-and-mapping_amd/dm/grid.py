@@ -505,6 +505,61 @@ class OccupancyMapper:
         with self._lock:  # both stages against one map
             return match.two_stage_with(match_one, pose, slam, float(self.params.resolution))
 
+    def match_global(self, poses, ranges, angle_min, angle_increment, yaw_offsets, k0: int, half_x: int,
+                     half_y: int, smear_cells: int, kern, block: int = 16, exhaustive: bool = False) -> dict:
+        """The best pose of S scans over a whole window on the device
+        (dm_match_global): dm_match_scans' candidates at sub = 1, stride = 1
+        for i in [-half_x, half_x], j in [-half_y, half_y] (up to 4096 each) and
+        up to 1024 yaws, found exactly by block bounds (`block` in {4, 8, 16,
+        32}) or, with `exhaustive`, by scoring everything.  Returns best int32
+        [S, 3] = (k, i, j), score uint32 [S], n_used int32 [S], pose float64
+        [S, 3] and stats uint64 [S, 4] = blocks, blocks bounded, blocks
+        refined, rounds.  Same results as dm.match.match_global, bit for bit."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        ranges = np.ascontiguousarray(ranges, dtype=np.float32)
+        if ranges.ndim != 2:
+            ranges = ranges.reshape(poses.shape[0], -1)
+        S, N = ranges.shape
+        off = np.ascontiguousarray(yaw_offsets, dtype=np.float64).reshape(-1)
+        kern = None if kern is None else np.ascontiguousarray(kern, dtype=np.uint8).reshape(-1)
+        if kern is not None and 0 <= int(smear_cells) <= 16 and kern.shape[0] < int(smear_cells) ** 2 + 1:
+            raise DmError(_ffi.DM_ERR_INVALID_ARG, "kern needs smear_cells**2 + 1 entries")
+        best = np.zeros((S, 3), np.int32)
+        score = np.zeros(S, np.uint32)
+        n_used = np.zeros(S, np.int32)
+        pose = np.zeros((S, 3), np.float64)
+        stats = np.zeros((S, 4), np.uint64)
+        with self._lock:
+            check(self._lib.dm_match_global(self._handle(), S, _vp(poses), N, _vp(ranges), float(angle_min),
+                                            float(angle_increment), off.shape[0], _vp(off), int(k0), int(half_x),
+                                            int(half_y), int(block), int(exhaustive), int(smear_cells), _vp(kern),
+                                            _vp(best), _vp(score), _vp(n_used), _vp(pose), _vp(stats)))
+        return {"best": best, "score": score, "n_used": n_used, "pose": pose, "stats": stats}
+
+    def relocalize(self, scan, prior=None, slam=None) -> dict:
+        """Find the pose of one LaserScan-like message in the map without a good
+        prior: the global stage (dm_match_global with dm.match.global_params'
+        reading of slam_toolbox's wide search; the whole map from its centre
+        when `prior` is None, +-loop_search_space_dimension / 2 around it
+        otherwise), then match_scan's two-stage search from its pose.  Returns
+        dm.match.relocalize's dict: pose, global_response and response (score
+        / (255 * n_used) of the global and the fine stage), accepted (both reach
+        loop_match_minimum_response_coarse / _fine), global, fine, stats."""
+        from . import match
+
+        ranges = np.asarray(scan.ranges, dtype=np.float32)[None, :]
+        amin, inc = np.float32(scan.angle_min), np.float32(scan.angle_increment)
+
+        def global_one(p, **kw):
+            res = self.match_global([p], ranges, amin, inc, **kw)
+            one = match.first_scan(res)
+            one["stats"] = tuple(int(v) for v in res["stats"][0])
+            return one
+
+        with self._lock:  # all stages against one map
+            return match.relocalize_with(global_one, lambda p: self.match_scan(scan, p, slam), self.params, prior,
+                                         slam)
+
     # -- frontiers --------------------------------------------------------
     def frontiers(self, want_mask=False, want_labels=False, cap=None) -> Frontiers:
         """Frontier mask / labels (optional dense copies) and the cluster

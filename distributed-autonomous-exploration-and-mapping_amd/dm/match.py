@@ -24,6 +24,12 @@ The trigonometry is ``math.cos`` / ``math.sin`` per value (the C library, as
 rounds every operation separately like the device code compiled without FMA
 contraction.
 
+``match_global`` restates dm_match_global (csrc/dm_match_global.h): the same
+score at sub = 1, stride = 1 over a window of up to 8193 x 8193 translations
+and 1024 yaws, as the exhaustive search that defines its result;
+``global_params`` and ``relocalize`` are this build's reading of
+slam_toolbox's wide search (slam_config.yaml:47-48, 56-58).
+
 ``two_stage`` is the coarse-then-fine search this build derives from the
 reference's slam_config.yaml; the wrapper (``OccupancyMapper.match_scan``)
 runs the same driver over the device calls.
@@ -232,6 +238,150 @@ def match_scans(state, params, poses, ranges, angle_min, angle_increment, yaw_of
                        poses[s, 2] + off[k])
     return {"best": out_best, "score": out_score, "n_used": used[:, int(k0), :].sum(axis=1).astype(np.int32),
             "pose": out_pose, "volume": vol}
+
+
+# -- whole-window relocalisation (dm_match_global) ---------------------------------
+MAX_GLOBAL_ANGLES = 1024
+MAX_GLOBAL_HALF = 4096
+
+# slam_config.yaml's wide-search settings (line numbers there)
+GLOBAL_DEFAULTS = {
+    "loop_search_space_dimension": 8.0,            # :56
+    "loop_search_space_smear_deviation": 0.03,     # :58
+    "loop_match_minimum_response_coarse": 0.35,    # :47
+    "loop_match_minimum_response_fine": 0.45,      # :48
+    "coarse_angle_resolution": 0.0349,             # :66
+}
+
+
+def match_global(state, params, poses, ranges, angle_min, angle_increment, yaw_offsets, k0: int, half_x: int,
+                 half_y: int, smear_cells: int, kern, field=None) -> dict:
+    """dm_match_global restated as the exhaustive search: dm_match_scans'
+    definition at sub = 1, stride = 1 over i in [-half_x, half_x], j in
+    [-half_y, half_y].  best int32 [S, 3] = (k, i, j), score uint32 [S], n_used
+    int32 [S], pose float64 [S, 3].  Per yaw and used beam the window
+    V[qy - half_y : qy + half_y + 1, qx - half_x : qx + half_x + 1] (0 out of the
+    grid) is added to the yaw's score plane; no volume is kept."""
+    off = np.asarray(yaw_offsets, np.float64).reshape(-1)
+    A = off.shape[0]
+    k0, hx, hy = int(k0), int(half_x), int(half_y)
+    if not 1 <= A <= MAX_GLOBAL_ANGLES:
+        raise ValueError("A must be in [1, 1024]")
+    if not 0 <= k0 < A:
+        raise ValueError("k0 must be in [0, A)")
+    if not (0 <= hx <= MAX_GLOBAL_HALF and 0 <= hy <= MAX_GLOBAL_HALF):
+        raise ValueError("half_x and half_y must be in [0, 4096]")
+    V = response_field(state, smear_cells, kern) if field is None else np.asarray(field, np.uint8)
+    H, W = V.shape
+    poses = np.asarray(poses, np.float64).reshape(-1, 3)
+    S = poses.shape[0]
+    qx, qy, used = fine_coords(params, poses, ranges, angle_min, angle_increment, off, 1)
+    res = float(params.resolution)
+    jj, ii = np.mgrid[-hy:hy + 1, -hx:hx + 1].astype(np.int64)
+    # the tie tuple's (i*i + j*j, j, i) of one yaw as one integer
+    key = ((ii * ii + jj * jj) << 28) | ((jj + hy) << 14) | (ii + hx)
+    far = np.int64(2 ** 62)
+    out_best = np.zeros((S, 3), np.int32)
+    out_score = np.zeros(S, np.uint32)
+    out_pose = np.zeros((S, 3), np.float64)
+    empty = not V.any()
+    for s in range(S):
+        top = (0, (0, 0, k0, 0, 0))  # score, tie tuple: stands when nothing scores above 0
+        for k in range(A if not empty else 0):
+            u = used[s, k]
+            if not u.any():
+                continue
+            acc = np.zeros((2 * hy + 1, 2 * hx + 1), np.uint32)
+            for x, y in zip(qx[s, k][u].tolist(), qy[s, k][u].tolist()):
+                x0, x1 = max(x - hx, 0), min(x + hx + 1, W)
+                y0, y1 = max(y - hy, 0), min(y + hy + 1, H)
+                if x0 < x1 and y0 < y1:
+                    acc[y0 - (y - hy):y1 - (y - hy), x0 - (x - hx):x1 - (x - hx)] += V[y0:y1, x0:x1]
+            mx = int(acc.max())
+            if mx == 0 or mx < top[0]:
+                continue
+            kk = int(np.where(acc == mx, key, far).min())
+            i, j = (kk & 0x3FFF) - hx, ((kk >> 14) & 0x3FFF) - hy
+            cand = (i * i + j * j, abs(k - k0), k, j, i)
+            if mx > top[0] or cand < top[1]:
+                top = (mx, cand)
+        sc, (_, _, k, j, i) = top
+        out_best[s] = (k, i, j)
+        out_score[s] = sc
+        out_pose[s] = (poses[s, 0] + float(i) * res, poses[s, 1] + float(j) * res, poses[s, 2] + off[k])
+    return {"best": out_best, "score": out_score, "n_used": used[:, k0, :].sum(axis=1).astype(np.int32),
+            "pose": out_pose}
+
+
+def global_params(slam, resolution: float, width: int, height: int, prior=None) -> dict:
+    """This build's reading of slam_toolbox's wide search (`slam` as for
+    search_params; missing names take the yaml's values):
+
+    * yaw candidates over the full circle in steps of coarse_angle_resolution:
+      n = floor(2 pi / step) of them (the 1e-9 tolerance of _symmetric_offsets
+      on the count; 180 at 0.0349), offsets (m - n // 2) * step, k0 = n // 2 the
+      zero offset; at most 1024;
+    * sigma = loop_search_space_smear_deviation, smear_cells = min(16,
+      ceil(2 sigma / resolution));
+    * without a prior the window is the whole map from its centre: half_x =
+      ceil(width / 2), half_y = ceil(height / 2); with one it is
+      +-loop_search_space_dimension / 2 in cells;
+    * block 16."""
+    g = {k: float(getattr(slam, k, v)) for k, v in GLOBAL_DEFAULTS.items()}
+    res = float(resolution)
+    step = g["coarse_angle_resolution"]
+    n = int(math.floor(2.0 * math.pi / step + 1e-9)) if step > 0.0 else 1
+    n = min(max(n, 1), MAX_GLOBAL_ANGLES)
+    k0 = n // 2
+    sigma = g["loop_search_space_smear_deviation"]
+    r = min(MAX_SMEAR, max(0, int(math.ceil(2.0 * sigma / res))))
+    if prior is None:
+        hx, hy = (int(width) + 1) // 2, (int(height) + 1) // 2
+    else:
+        hx = hy = int(math.ceil(g["loop_search_space_dimension"] / 2.0 / res - 1e-9))
+    return {"yaw_offsets": np.array([(m - k0) * step for m in range(n)], np.float64), "k0": k0,
+            "half_x": min(max(hx, 0), MAX_GLOBAL_HALF), "half_y": min(max(hy, 0), MAX_GLOBAL_HALF),
+            "smear_cells": r, "kern": kernel_table(sigma, res, r) if sigma > 0.0 else np.array([255], np.uint8),
+            "block": 16}
+
+
+def relocalize_with(global_one, fine_two_stage, params, prior, slam) -> dict:
+    """The relocalisation driver over any global matcher and two-stage matcher:
+    global_one(pose, **global search) -> one scan's {"best", "score", "n_used",
+    "pose"[, "stats"]}; fine_two_stage(pose) -> two_stage's dict.  The global
+    stage runs from `prior` (None: the map's centre, yaw 0, the whole map),
+    the two-stage search from its pose.  accepted: the global response >=
+    loop_match_minimum_response_coarse and the fine one >=
+    loop_match_minimum_response_fine."""
+    gp = global_params(slam, float(params.resolution), int(params.width), int(params.height), prior)
+    if prior is None:
+        res = float(params.resolution)
+        start = (float(params.origin_x) + 0.5 * float(int(params.width)) * res,
+                 float(params.origin_y) + 0.5 * float(int(params.height)) * res, 0.0)
+    else:
+        start = tuple(float(v) for v in prior)
+    glob = global_one(start, **gp)
+    n, score = int(glob["n_used"]), int(glob["score"])
+    g_resp = score / (255.0 * n) if n > 0 else 0.0
+    fine = fine_two_stage(tuple(float(v) for v in glob["pose"]))
+    lo_c = float(getattr(slam, "loop_match_minimum_response_coarse", GLOBAL_DEFAULTS["loop_match_minimum_response_coarse"]))
+    lo_f = float(getattr(slam, "loop_match_minimum_response_fine", GLOBAL_DEFAULTS["loop_match_minimum_response_fine"]))
+    return {"pose": tuple(float(v) for v in fine["pose"]), "global_response": g_resp,
+            "response": float(fine["response"]), "accepted": bool(g_resp >= lo_c and fine["response"] >= lo_f),
+            "global": glob, "fine": fine, "stats": glob.get("stats")}
+
+
+def relocalize(state, params, ranges, angle_min, angle_increment, prior=None, slam=None) -> dict:
+    """relocalize_with over the host restatement (OccupancyMapper.relocalize's
+    reference)."""
+    r1 = np.asarray(ranges, np.float32).reshape(1, -1)
+
+    def global_one(p, yaw_offsets, k0, half_x, half_y, smear_cells, kern, block):
+        return first_scan(match_global(state, params, [p], r1, angle_min, angle_increment, yaw_offsets, k0, half_x,
+                                       half_y, smear_cells, kern))
+
+    return relocalize_with(global_one, lambda p: two_stage(state, params, r1[0], angle_min, angle_increment, p, slam),
+                           params, prior, slam)
 
 
 # -- the two-stage search of this build --------------------------------------------

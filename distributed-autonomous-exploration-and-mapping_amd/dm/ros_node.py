@@ -37,6 +37,11 @@ callback signatures:
   slam_toolbox's, slam_config.yaml:35,50-53,64-66) before integrating it; the
   correction is kept as ``map_to_odom`` and, under ROS, broadcast as
   ``map -> odom``: the part of the TF chain slam_toolbox published;
+* with ``dm_map_file`` loads a ``dm_save`` checkpoint at start, and with
+  ``dm_relocalize`` (default off; needs ``dm_scan_matching``) integrates no
+  scan into it until one has been found in the map (``dm_match_global`` over
+  the whole map, then the matcher; slam_toolbox's localization mode,
+  slam_config.yaml:20, 47-48, 56-58); the pose found becomes ``map_to_odom``;
 * with ``dm_goal_coordinate`` (default off), subscribes ``dm_peer_goals_topic``
   (``geometry_msgs/PoseArray``: the goals the other robots hold) and scores its
   own goal by what it would see that those goals do not
@@ -212,6 +217,11 @@ class SlamParams:
     fine_search_angle_offset: float = 0.00349               # :64
     coarse_search_angle_offset: float = 0.349               # :65
     coarse_angle_resolution: float = 0.0349                 # :66
+    # its wide search's settings (used with dm_relocalize)
+    loop_match_minimum_response_coarse: float = 0.35        # :47
+    loop_match_minimum_response_fine: float = 0.45          # :48
+    loop_search_space_dimension: float = 8.0                # :56
+    loop_search_space_smear_deviation: float = 0.03         # :58
     # this build (not slam_toolbox parameters)
     dm_width: int = 4096                  # cells; a 204.8 m square at 5 cm
     dm_height: int = 4096
@@ -245,6 +255,13 @@ class SlamParams:
     # provider's pose is taken as it is, as before.  Needs use_scan_matching
     # too (the reference's own switch, true in its yaml).
     dm_scan_matching: bool = False
+    # a dm_save checkpoint loaded into the mapper at start ("": none), the
+    # reference's "localization to use a existing map" (slam_config.yaml:20)
+    dm_map_file: str = ""
+    # with a loaded map: integrate nothing until a scan has been found in it
+    # (OccupancyMapper.relocalize over the whole map, dm_match_global); the
+    # pose found becomes map -> odom.  Needs dm_scan_matching.
+    dm_relocalize: bool = False
 
     @classmethod
     def from_dict(cls, d: dict) -> "SlamParams":
@@ -416,7 +433,7 @@ class MappingNode:
         self.params = p.grid_params()
         if mapper is None:
             devices = parse_devices(p.dm_devices)
-            if len(devices) > 1 and p.dm_scan_matching and p.use_scan_matching:
+            if len(devices) > 1 and ((p.dm_scan_matching and p.use_scan_matching) or p.dm_relocalize):
                 raise ValueError("dm_scan_matching needs the whole map in one handle: it is not available "
                                  "with a map sharded over dm_devices")
             if len(devices) > 1:
@@ -452,6 +469,15 @@ class MappingNode:
         self.scans_rejected = 0
         self.last_match = None             # mapper.match_scan's result for the last matched scan
         self.last_integrated_pose = None   # the pose the last scan was integrated at
+        # dm_map_file / dm_relocalize: while `relocalizing`, no scan is integrated
+        if p.dm_relocalize and not self.matching:
+            raise ValueError("dm_relocalize needs dm_scan_matching (and use_scan_matching)")
+        self.map_loaded = bool(p.dm_map_file)
+        if self.map_loaded:
+            self.mapper.load(str(p.dm_map_file))
+        self.relocalizing = bool(p.dm_relocalize) and self.map_loaded
+        self.relocalize_rejected = 0
+        self.last_relocalize = None        # mapper.relocalize's result of the last attempt
 
     # main.py:77-78 keeps the signature scan_cb(self, msg)
     def scan_cb(self, msg):
@@ -468,7 +494,12 @@ class MappingNode:
         stamp = stamp_seconds(msg.header.stamp)
         if self.gate is not None and not self.gate.accept(stamp, pose):
             return
-        if self.matching and self.scans_integrated > 0:
+        if self.relocalizing:
+            pose = self._relocalize(msg, odom)
+            if pose is None:
+                return
+            self.latest_pose = pose
+        elif self.matching and (self.scans_integrated > 0 or self.map_loaded):
             pose = self._match(msg, odom, pose)
             self.latest_pose = pose
         u, _ = self.mapper.integrate_scan(msg, pose)
@@ -497,6 +528,23 @@ class MappingNode:
             return matched
         self.scans_rejected += 1
         return tuple(float(v) for v in prior)
+
+    def _relocalize(self, msg, odom):
+        """Find an accepted scan in the loaded map (OccupancyMapper.relocalize:
+        the whole map, every yaw; what slam_toolbox's localization mode does
+        for the reference, slam_config.yaml:20, :47-48, :56-58).  Accepted:
+        map_to_odom becomes matched o odom^-1 and the scan is integrated at
+        the matched pose; the node then goes on matching.  Rejected: counted,
+        and nothing is integrated (None)."""
+        res = self.mapper.relocalize(msg, None, self.slam)
+        self.last_relocalize = res
+        if not res["accepted"]:
+            self.relocalize_rejected += 1
+            return None
+        matched = tuple(float(v) for v in res["pose"])
+        self.map_to_odom = se2_compose(matched, se2_inverse(odom))
+        self.relocalizing = False
+        return matched
 
     def timer_cb(self):
         """The map_update_interval timer: publish /map and start a frontier

@@ -673,6 +673,54 @@ int dm_match_scans(dm_grid* g, int32_t S, const double* poses, int32_t N, const 
                    int32_t half, int32_t stride, int32_t smear_cells, const uint8_t* kern, int32_t* out_best,
                    uint32_t* out_score, int32_t* out_n_used, double* out_pose, uint32_t* out_volume);
 
+/* Whole-window relocalisation: the best candidate of dm_match_scans'
+ * definition at sub = 1, stride = 1 over a window far larger than its volume
+ * could hold, found exactly by bounds from a max-pooled response field
+ * (DESIGN.md §8.5).  It takes over slam_toolbox's localisation start on a
+ * saved map (slam_config.yaml:20) and its wide loop search (:56-58).
+ *
+ *   The response field V, the used beams, n_used and the endpoint cells
+ *     qx = floor((ex - origin_x) / resolution), qy likewise, are those of
+ *     dm_match_scans at sub = 1; the candidate yaw is yaw + yaw_offsets[k].
+ *   score[s][k][j][i] = sum over used beams of V[qx + i, qy + j], cells out of
+ *     the grid adding 0, for i in [-half_x, half_x], j in [-half_y, half_y].
+ *   Best: the maximal score over all A * (2 half_x + 1) * (2 half_y + 1)
+ *     candidates, ties to the lexicographically least
+ *     (i*i + j*j, |k - k0|, k, j, i); an empty or unknown map gives
+ *     (k0, 0, 0) with score 0.
+ *   Output pose: x + (double)i * resolution, y + (double)j * resolution,
+ *     yaw + yaw_offsets[k].
+ *   Limits: half_x, half_y in [0, 4096]; A in [1, 1024]; k0 in [0, A); block in
+ *     {4, 8, 16, 32}; exhaustive in {0, 1}; S, N, smear_cells, kern as for
+ *     dm_match_scans.  Anything else is DM_ERR_INVALID_ARG, and so is a band
+ *     handle or a dm_create_sharded handle.  More than 2^26 blocks per scan,
+ *     A * ceil((2 half_x + 1) / block) * ceil((2 half_y + 1) / block), is
+ *     DM_ERR_CAPACITY (take a larger block); a failed allocation DM_ERR_OOM.
+ * The result is defined by the exhaustive search alone: block and exhaustive
+ * change how it is found and what out_stats says, never a result bit.  With
+ * half_x == half_y <= 32 and A <= 64 the four outputs equal
+ * dm_match_scans(sub = 1, stride = 1, half).
+ *   exhaustive = 0: M_B[c] = max of V over [cx, cx + block) x [cy, cy + block)
+ *     bounds every score of a block of block x block translations of one yaw
+ *     by sum over used beams of M_B[qx + i0, qy + j0]; blocks are scored
+ *     exactly in rounds, the highest bounds first, until no unscored block's
+ *     bound reaches the best exact score (ties included: exact).
+ *   exhaustive = 1: every block is scored; the device's own brute force.
+ * out_best: int32[S][3] = (k, i, j); out_score: uint32[S]; out_n_used:
+ * int32[S]; out_pose: double[S][3]; out_stats (may be NULL): uint64[S][4] =
+ * blocks in the search, blocks whose bound was computed (0 when exhaustive),
+ * blocks scored exactly, rounds.  Synchronous, ordered after everything
+ * enqueued on the handle; reads the map and never writes it, the map version
+ * is unchanged.  The scans of one call are processed one after another.  The
+ * pooled field is kept in the handle per (map version, smear_cells, kern,
+ * block), like the field.  DM_MATCH_GLOBAL_BATCH (read at dm_create) sets the
+ * most blocks one round scores (default 4096); it changes no result. */
+int dm_match_global(dm_grid* g, int32_t S, const double* poses, int32_t N, const float* ranges, float angle_min,
+                    float angle_increment, int32_t A, const double* yaw_offsets, int32_t k0, int32_t half_x,
+                    int32_t half_y, int32_t block, int32_t exhaustive, int32_t smear_cells, const uint8_t* kern,
+                    int32_t* out_best /*[S][3] k,i,j*/, uint32_t* out_score, int32_t* out_n_used,
+                    double* out_pose /*[S][3]*/, uint64_t* out_stats /*[S][4], may be NULL*/);
+
 /* Measured uncontended atomic throughput of HIP device `device` (the
  * north star's "atomic throughput against MI355X peak": no vendor figure
  * exists for integer atomics, so the peak is measured in-harness,
