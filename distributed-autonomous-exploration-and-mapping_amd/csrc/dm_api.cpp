@@ -1,5 +1,7 @@
 // dm_api.cpp — the C-ABI of libdm.so (include/dm.h): handle lifetime,
 // validation, error codes, host<->device staging, checkpoints, profiling.
+// The goal, planner and gain calls are in dm_goals.hip and the scan matchers
+// in dm_match.hip, each next to its kernels' launchers.
 //
 // Contract from SURVEY.md §8(b): device memory is owned by the handle; host
 // pointers are borrowed for the call; synchronous functions return after
@@ -51,36 +53,6 @@ bool dm_env_on(const char* name) {  // opt-in A/B switches: NAME=1
 struct HostCluster {
   long long label, size, sum_x, sum_y;
 };
-
-template <class T>
-int dev_alloc(T** p, int64_t count, const char* what) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  if (count <= 0) count = 1;
-  hipError_t e = hipMalloc((void**)p, sizeof(T) * (size_t)count);
-  if (e != hipSuccess) {
-    *p = nullptr;
-    return dm_set_error(e == hipErrorOutOfMemory ? DM_ERR_OOM : DM_ERR_HIP,
-                        "hipMalloc(%s, %lld bytes): %s", what,
-                        (long long)(sizeof(T) * (size_t)count), hipGetErrorString(e));
-  }
-  return DM_OK;
-}
-
-template <class T>
-void dev_free(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-// grow-on-demand scratch: (re)allocate *p to n elements when *cap is smaller
-template <class T>
-int dev_grow(T** p, int64_t* cap, int64_t n, const char* what) {
-  if (n <= *cap) return DM_OK;
-  *cap = 0;
-  const int rc = dev_alloc(p, n, what);
-  if (!rc) *cap = n;
-  return rc;
-}
 
 int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
@@ -351,17 +323,10 @@ int grow_merge(dm_grid* g, int64_t n) {
   return DM_OK;
 }
 
+}  // namespace
+
 int check_grid(const dm_grid* g) {
   if (!g) return dm_set_error(DM_ERR_INVALID_ARG, "grid handle is NULL");
-  return DM_OK;
-}
-
-// The building blocks of the multi-process exchange are not calls of a
-// sharded parent: it runs that exchange itself (dm_sharded.cpp).
-int not_on_sharded(const dm_grid* g, const char* what) {
-  if (g && g->sh)
-    return dm_set_error(DM_ERR_INVALID_ARG, "%s is not available on a sharded handle (dm_create_sharded runs "
-                                            "the band exchange itself)", what);
   return DM_OK;
 }
 
@@ -376,6 +341,30 @@ int check_integrate_args(int32_t S, int32_t N, const void* poses, const void* ra
   if (N > 65535) return dm_set_error(DM_ERR_SHAPE, "N must be <= 65535");
   if ((int64_t)S * N > 0 && (!poses || !ranges))
     return dm_set_error(DM_ERR_INVALID_ARG, "poses/ranges is NULL");
+  return DM_OK;
+}
+
+int dm_check_whole_map(const dm_grid* g, const char* what) {
+  if (g && g->sh)
+    return dm_set_error(DM_ERR_INVALID_ARG, "%s needs one handle that covers the whole map: it is not available "
+                        "on a sharded handle (dm_create_sharded)", what);
+  int rc = check_grid(g);
+  if (rc) return rc;
+  if (g->R != g->H)
+    return dm_set_error(DM_ERR_INVALID_ARG, "%s needs a handle that covers the whole map; this one is the band "
+                        "of rows [%lld, %lld) of %lld", what, (long long)g->row0, (long long)(g->row0 + g->R),
+                        (long long)g->H);
+  return DM_OK;
+}
+
+namespace {
+
+// The building blocks of the multi-process exchange are not calls of a
+// sharded parent: it runs that exchange itself (dm_sharded.cpp).
+int not_on_sharded(const dm_grid* g, const char* what) {
+  if (g && g->sh)
+    return dm_set_error(DM_ERR_INVALID_ARG, "%s is not available on a sharded handle (dm_create_sharded runs "
+                                            "the band exchange itself)", what);
   return DM_OK;
 }
 
@@ -1287,937 +1276,6 @@ int dm_frontiers_poll(dm_grid* g, int32_t* ready) {
   }
   if (e == hipErrorNotReady) return DM_OK;
   DM_HIP(e);
-  return DM_OK;
-}
-
-int dm_assign_goals(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size,
-                    double distance_weight, double min_distance, int64_t* out_index, double* out_xy) {
-  if (g && g->sh) return dm_sh_assign_goals(g, robots_xy, n_robots, min_size, distance_weight, min_distance, out_index, out_xy);
-  int rc = check_grid(g);
-  if (rc || (rc = use_device(g))) return rc;
-  if (n_robots < 0 || n_robots > 256)
-    return dm_set_error(DM_ERR_INVALID_ARG, "n_robots must be in [0, 256] (got %d)", n_robots);
-  if (n_robots > 0 && (!robots_xy || !out_index || !out_xy))
-    return dm_set_error(DM_ERR_INVALID_ARG, "robots_xy / out_index / out_xy is NULL");
-  if (!isfinite(distance_weight) || !isfinite(min_distance))
-    return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight / min_distance must be finite");
-  // the device ranks by the util's IEEE bits, an order that holds for util > 0
-  // only: w >= 0 keeps util = size / (1 + w*dist) positive and finite
-  if (distance_weight < 0.0)
-    return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight must be >= 0");
-  const int s = g->goal_slot;
-  if (s < 0 || g->goal_gen != g->rb_gen ||
-      (g->goal_kind == 1 ? g->rb[s].wepoch : g->rb[s].mepoch) != g->goal_epoch)
-    return dm_set_error(DM_ERR_INVALID_ARG, "no collected frontier result on the device (call dm_frontiers, "
-                                            "dm_frontiers_end or dm_merge_bands first; a later pass may have "
-                                            "reused its readback slot)");
-  if (n_robots == 0) return DM_OK;
-  const dm_cluster* recs = g->goal_kind == 1 ? g->rb[s].out_clu : g->rb[s].m_out;
-  const int64_t K = g->goal_n;
-  if (!g->goal_io) {
-    DM_HIP(hipMalloc((void**)&g->goal_io, sizeof(double) * 4 * 256));
-    DM_HIP(hipMalloc((void**)&g->goal_idx, sizeof(int64_t) * 256));
-  }
-  DM_HIP(dm_join_pass_stream(g));
-  const int32_t R = n_robots, T = n_robots;
-  DM_HIP(hipMemcpyAsync(g->goal_io, robots_xy, sizeof(double) * 2 * (size_t)R, hipMemcpyHostToDevice,
-                        g->stream));
-  std::vector<int64_t> idx((size_t)R, -1);
-  if (K > 0) {
-    const unsigned long long* dk = nullptr;
-    const uint32_t* di = nullptr;
-    if ((rc = dm_launch_goal_topk(g, recs, K, g->goal_io, R, T, min_size, distance_weight, min_distance, &dk,
-                                  &di)))
-      return rc;
-    std::vector<unsigned long long> hk((size_t)R * T);
-    std::vector<uint32_t> hi((size_t)R * T);
-    DM_HIP(hipMemcpyAsync(hk.data(), dk, sizeof(unsigned long long) * hk.size(), hipMemcpyDeviceToHost,
-                          g->stream));
-    DM_HIP(hipMemcpyAsync(hi.data(), di, sizeof(uint32_t) * hi.size(), hipMemcpyDeviceToHost, g->stream));
-    DM_HIP(hipStreamSynchronize(g->stream));
-    // greedy in robot order over each robot's best-first list (its choice is
-    // within its first r + 1 entries: r clusters are taken before its turn)
-    for (int32_t r = 0; r < R; ++r) {
-      for (int32_t t = 0; t < T; ++t) {
-        if (hk[(size_t)r * T + t] == 0ull) break;  // no eligible cluster left in the list
-        const int64_t c = hi[(size_t)r * T + t];
-        if (std::find(idx.begin(), idx.begin() + r, c) != idx.begin() + r) continue;
-        idx[(size_t)r] = c;
-        break;
-      }
-    }
-  }
-  DM_HIP(hipMemcpyAsync(g->goal_idx, idx.data(), sizeof(int64_t) * (size_t)R, hipMemcpyHostToDevice,
-                        g->stream));
-  if ((rc = dm_launch_goal_gather(g, recs, g->goal_idx, R, g->goal_io + 2 * 256))) return rc;
-  DM_HIP(hipMemcpyAsync(out_xy, g->goal_io + 2 * 256, sizeof(double) * 2 * (size_t)R, hipMemcpyDeviceToHost,
-                        g->stream));
-  DM_HIP(hipStreamSynchronize(g->stream));
-  memcpy(out_index, idx.data(), sizeof(int64_t) * (size_t)R);
-  return DM_OK;
-}
-
-// ---- path planning (csrc/dm_plan.h): traversability, distance field, snapped
-// queries, paths, path-length goals ---------------------------------------------
-
-// The planner needs the whole map in one handle.
-static int plan_check_handle(const dm_grid* g, const char* what) {
-  if (g && g->sh)
-    return dm_set_error(DM_ERR_INVALID_ARG, "%s needs one handle that covers the whole map: it is not available "
-                        "on a sharded handle (dm_create_sharded)", what);
-  int rc = check_grid(g);
-  if (rc) return rc;
-  if (g->R != g->H)
-    return dm_set_error(DM_ERR_INVALID_ARG, "%s needs a handle that covers the whole map; this one is the band "
-                        "of rows [%lld, %lld) of %lld", what, (long long)g->row0, (long long)(g->row0 + g->R),
-                        (long long)g->H);
-  return DM_OK;
-}
-
-static int ensure_plan(dm_grid* g) {
-  if (g->plan_cost) return DM_OK;  // allocated last: everything else is there too
-  int rc = DM_OK;
-  if (!g->h_plan) {
-    hipError_t e = hipHostMalloc((void**)&g->h_plan, sizeof(unsigned long long) * 16,
-                                 hipHostMallocMapped | hipHostMallocCoherent);
-    if (e != hipSuccess) {
-      g->h_plan = nullptr;
-      return dm_hip_check(e, "hipHostMalloc(plan rounds)");
-    }
-    memset(g->h_plan, 0, sizeof(unsigned long long) * 16);
-    DM_HIP(hipHostGetDevicePointer((void**)&g->h_plan_dev, g->h_plan, 0));
-  }
-  const int64_t rows = g->NT * DM_TILE;
-  if ((rc = dev_alloc(&g->plan_trav, rows, "traversable bit rows"))) return rc;
-  if ((rc = dev_alloc(&g->plan_travs, rows, "traversable bit rows with sources"))) return rc;
-  if ((rc = dev_alloc(&g->plan_list[0], g->NT, "plan tile list"))) return rc;
-  if ((rc = dev_alloc(&g->plan_list[1], g->NT, "plan tile list"))) return rc;
-  if ((rc = dev_alloc(&g->plan_stamp, g->NT, "plan tile stamps"))) return rc;
-  if ((rc = dev_alloc(&g->plan_len, 4, "plan list lengths"))) return rc;
-  if ((rc = dev_alloc(&g->plan_stat, 8, "plan statistics"))) return rc;
-  DM_HIP(hipMemset(g->plan_stat, 0, sizeof(unsigned long long) * 8));
-  if ((rc = dev_alloc(&g->plan_src, 256, "plan sources"))) return rc;
-  return dev_alloc(&g->plan_cost, g->W * g->H, "distance field");
-}
-
-static int grow_plan_query(dm_grid* g, int64_t n) {
-  if (n <= g->plan_qcap) return DM_OK;
-  g->plan_qcap = 0;
-  int rc = dev_alloc(&g->plan_qxy, 2 * n, "plan query targets");
-  if (!rc) rc = dev_alloc(&g->plan_qcost, n, "plan query costs");
-  if (!rc) rc = dev_alloc(&g->plan_qcell, n, "plan query cells");
-  if (!rc) g->plan_qcap = n;
-  return rc;
-}
-
-// SPEC a4's cell of a point: floor((x - origin) / resolution) per axis
-static bool plan_cell_of(const dm_grid* g, double x, double y, int64_t* cell) {
-  const double fx = floor((x - g->p.origin_x) / g->p.resolution);
-  const double fy = floor((y - g->p.origin_y) / g->p.resolution);
-  if (!(fx >= 0.0 && fx < (double)g->W && fy >= 0.0 && fy < (double)g->H)) return false;  // NaN too
-  *cell = (int64_t)fy * g->W + (int64_t)fx;
-  return true;
-}
-
-static uint64_t plan_map_version(const dm_grid* g) { return g->integrate_seq + g->reset_seq; }
-
-static int plan_need_field(const dm_grid* g, const char* what) {
-  if (!g->plan_cost || !g->plan_valid)
-    return dm_set_error(DM_ERR_STATE, "%s: no distance field (call dm_plan_field first)", what);
-  if (g->plan_version != plan_map_version(g))
-    return dm_set_error(DM_ERR_STATE, "%s: the map changed since the distance field was computed (call "
-                        "dm_plan_field again)", what);
-  return DM_OK;
-}
-
-// The field from n sources (metres) over g->plan_trav, which the caller computed.
-static int plan_field_from(dm_grid* g, const double* sources_xy, int32_t n, uint32_t max_cost, uint64_t* stats) {
-  std::vector<int64_t> cells((size_t)n);
-  std::vector<int32_t> tiles;
-  for (int32_t i = 0; i < n; ++i) {
-    if (!plan_cell_of(g, sources_xy[2 * i], sources_xy[2 * i + 1], &cells[(size_t)i]))
-      return dm_set_error(DM_ERR_INVALID_ARG, "source %d (%g, %g) is outside the grid", i, sources_xy[2 * i],
-                          sources_xy[2 * i + 1]);
-    const int64_t x = cells[(size_t)i] % g->W, y = cells[(size_t)i] / g->W;
-    const int32_t t = (int32_t)((y / DM_TILE) * g->TX + x / DM_TILE);
-    if (std::find(tiles.begin(), tiles.end(), t) == tiles.end()) tiles.push_back(t);
-  }
-  if (max_cost == 0u || max_cost > 0xFFFFFFEFu) max_cost = 0xFFFFFFEFu;
-  g->plan_valid = false;
-  int rc = dm_plan_run_field(g, cells.data(), n, tiles.data(), (int32_t)tiles.size(), max_cost, stats);
-  if (rc) return rc;
-  g->plan_valid = true;
-  g->plan_version = plan_map_version(g);
-  return DM_OK;
-}
-
-static int plan_check_inflate(int32_t inflate_cells) {
-  if (inflate_cells < 0 || inflate_cells > 32)
-    return dm_set_error(DM_ERR_INVALID_ARG, "inflate_cells must be in [0, 32] (got %d)", inflate_cells);
-  return DM_OK;
-}
-
-static int plan_check_snap(int32_t snap_cells) {
-  if (snap_cells < 0 || snap_cells > 16)
-    return dm_set_error(DM_ERR_INVALID_ARG, "snap_cells must be in [0, 16] (got %d)", snap_cells);
-  return DM_OK;
-}
-
-int dm_plan_traversable(dm_grid* g, int32_t inflate_cells, uint8_t* out) {
-  int rc = plan_check_handle(g, "dm_plan_traversable");
-  if (rc || (rc = use_device(g))) return rc;
-  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
-  if ((rc = plan_check_inflate(inflate_cells)) || (rc = ensure_plan(g))) return rc;
-  DM_HIP(dm_join_pass_stream(g));
-  const int64_t cells = g->W * g->H;
-  uint8_t* d = nullptr;
-  if ((rc = dev_alloc(&d, cells, "traversable image"))) return rc;
-  rc = dm_plan_launch_travers(g, inflate_cells);
-  if (!rc) rc = dm_plan_launch_expand(g, d);
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(out, d, (size_t)cells, hipMemcpyDeviceToHost, g->stream);
-  if (!rc && e == hipSuccess) e = hipStreamSynchronize(g->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess) return dm_hip_check(e, "dm_plan_traversable");
-  return rc;
-}
-
-int dm_plan_field(dm_grid* g, const double* sources_xy, int32_t n_sources, int32_t inflate_cells,
-                  uint32_t max_cost, uint64_t* out_stats) {
-  int rc = plan_check_handle(g, "dm_plan_field");
-  if (rc || (rc = use_device(g))) return rc;
-  if (n_sources < 1 || n_sources > 256)
-    return dm_set_error(DM_ERR_INVALID_ARG, "n_sources must be in [1, 256] (got %d)", n_sources);
-  if (!sources_xy) return dm_set_error(DM_ERR_INVALID_ARG, "sources_xy is NULL");
-  if ((rc = plan_check_inflate(inflate_cells)) || (rc = ensure_plan(g))) return rc;
-  DM_HIP(dm_join_pass_stream(g));
-  if ((rc = dm_plan_launch_travers(g, inflate_cells))) return rc;
-  return plan_field_from(g, sources_xy, n_sources, max_cost, out_stats);
-}
-
-int dm_plan_get_field(dm_grid* g, uint32_t* out) {
-  int rc = plan_check_handle(g, "dm_plan_get_field");
-  if (rc || (rc = use_device(g))) return rc;
-  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
-  if ((rc = plan_need_field(g, "dm_plan_get_field"))) return rc;
-  DM_HIP(hipMemcpyAsync(out, g->plan_cost, sizeof(uint32_t) * (size_t)(g->W * g->H), hipMemcpyDeviceToHost,
-                        g->stream));
-  DM_HIP(hipStreamSynchronize(g->stream));
-  return DM_OK;
-}
-
-int dm_plan_query(dm_grid* g, const double* targets_xy, int64_t n, int32_t snap_cells, uint32_t* out_cost,
-                  int64_t* out_cell) {
-  int rc = plan_check_handle(g, "dm_plan_query");
-  if (rc || (rc = use_device(g))) return rc;
-  if (n < 0) return dm_set_error(DM_ERR_INVALID_ARG, "n must be >= 0");
-  if (n > 0 && (!targets_xy || !out_cost || !out_cell))
-    return dm_set_error(DM_ERR_INVALID_ARG, "targets_xy / out_cost / out_cell is NULL");
-  if ((rc = plan_check_snap(snap_cells)) || (rc = plan_need_field(g, "dm_plan_query"))) return rc;
-  if (n == 0) return DM_OK;
-  if ((rc = grow_plan_query(g, n))) return rc;
-  DM_HIP(hipMemcpyAsync(g->plan_qxy, targets_xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, g->stream));
-  if ((rc = dm_plan_launch_query(g, g->plan_qxy, 2, n, snap_cells, g->plan_qcost, g->plan_qcell))) return rc;
-  DM_HIP(hipMemcpyAsync(out_cost, g->plan_qcost, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-  DM_HIP(hipMemcpyAsync(out_cell, g->plan_qcell, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-  DM_HIP(hipStreamSynchronize(g->stream));
-  return DM_OK;
-}
-
-int dm_plan_path(dm_grid* g, double tx, double ty, int32_t snap_cells, int64_t* out_cells, int64_t cap,
-                 int64_t* n_out) {
-  int rc = plan_check_handle(g, "dm_plan_path");
-  if (rc || (rc = use_device(g))) return rc;
-  if (!n_out) return dm_set_error(DM_ERR_INVALID_ARG, "n_out is NULL");
-  *n_out = 0;
-  if (cap < 0 || (cap > 0 && !out_cells)) return dm_set_error(DM_ERR_INVALID_ARG, "cap < 0 or out_cells is NULL");
-  if ((rc = plan_check_snap(snap_cells)) || (rc = plan_need_field(g, "dm_plan_path"))) return rc;
-  if ((rc = grow_plan_query(g, 1))) return rc;
-  // a path visits no cell twice: H * W entries hold any
-  const int64_t dcap = std::max<int64_t>(1, std::min<int64_t>(cap, g->W * g->H));
-  if (dcap > g->plan_pathcap) {
-    g->plan_pathcap = 0;
-    if ((rc = dev_alloc(&g->plan_path, dcap, "path cells"))) return rc;
-    g->plan_pathcap = dcap;
-  }
-  const double txy[2] = {tx, ty};
-  DM_HIP(hipMemcpyAsync(g->plan_qxy, txy, sizeof txy, hipMemcpyHostToDevice, g->stream));
-  if ((rc = dm_plan_launch_query(g, g->plan_qxy, 2, 1, snap_cells, g->plan_qcost, g->plan_qcell))) return rc;
-  if ((rc = dm_plan_launch_path(g, g->plan_qcell, std::min(cap, dcap)))) return rc;
-  unsigned long long st[2] = {0ull, 0ull};
-  DM_HIP(hipMemcpyAsync(st, g->plan_stat + 4, sizeof st, hipMemcpyDeviceToHost, g->stream));
-  DM_HIP(hipStreamSynchronize(g->stream));
-  if (st[1])
-    return dm_set_error(DM_ERR_INCOMPLETE, "dm_plan_path: the walk found no predecessor after %llu cells (the "
-                        "field is not a fixpoint)", st[0]);
-  const int64_t n = (int64_t)st[0];
-  *n_out = n;
-  if (n > cap)
-    return dm_set_error(DM_ERR_CAPACITY, "the path has %lld cells, cap is %lld", (long long)n, (long long)cap);
-  if (n > 0) {
-    std::vector<int64_t> rev((size_t)n);
-    DM_HIP(hipMemcpy(rev.data(), g->plan_path, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n; ++i) out_cells[i] = rev[(size_t)(n - 1 - i)];  // source first
-  }
-  return DM_OK;
-}
-
-int dm_assign_goals_path(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size,
-                         double distance_weight, double min_distance, int32_t inflate_cells, uint32_t max_cost,
-                         int32_t snap_cells, int64_t* out_index, double* out_xy, int64_t* out_cell) {
-  int rc = plan_check_handle(g, "dm_assign_goals_path");
-  if (rc || (rc = use_device(g))) return rc;
-  if (n_robots < 0 || n_robots > 256)
-    return dm_set_error(DM_ERR_INVALID_ARG, "n_robots must be in [0, 256] (got %d)", n_robots);
-  if (n_robots > 0 && (!robots_xy || !out_index || !out_xy || !out_cell))
-    return dm_set_error(DM_ERR_INVALID_ARG, "robots_xy / out_index / out_xy / out_cell is NULL");
-  if (!isfinite(distance_weight) || !isfinite(min_distance))
-    return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight / min_distance must be finite");
-  if (distance_weight < 0.0)  // as dm_assign_goals: the device ranks by the util's IEEE bits
-    return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight must be >= 0");
-  if ((rc = plan_check_inflate(inflate_cells)) || (rc = plan_check_snap(snap_cells))) return rc;
-  const int s = g->goal_slot;
-  if (s < 0 || g->goal_gen != g->rb_gen ||
-      (g->goal_kind == 1 ? g->rb[s].wepoch : g->rb[s].mepoch) != g->goal_epoch)
-    return dm_set_error(DM_ERR_INVALID_ARG, "no collected frontier result on the device (call dm_frontiers, "
-                                            "dm_frontiers_end or dm_merge_bands first; a later pass may have "
-                                            "reused its readback slot)");
-  if (n_robots == 0) return DM_OK;
-  for (int32_t r = 0; r < n_robots; ++r) {
-    int64_t c;
-    if (!plan_cell_of(g, robots_xy[2 * r], robots_xy[2 * r + 1], &c))
-      return dm_set_error(DM_ERR_INVALID_ARG, "robot %d (%g, %g) is outside the grid", r, robots_xy[2 * r],
-                          robots_xy[2 * r + 1]);
-  }
-  const dm_cluster* recs = g->goal_kind == 1 ? g->rb[s].out_clu : g->rb[s].m_out;
-  const int64_t K = g->goal_n;
-  if ((rc = ensure_plan(g)) || (rc = grow_plan_query(g, std::max<int64_t>(K, 1)))) return rc;
-  DM_HIP(dm_join_pass_stream(g));
-  if ((rc = dm_plan_launch_travers(g, inflate_cells))) return rc;
-  const int32_t R = n_robots, T = n_robots;
-  std::vector<int64_t> idx((size_t)R, -1);
-  std::vector<unsigned long long> hk((size_t)T);
-  std::vector<uint32_t> hi((size_t)T);
-  for (int32_t r = 0; r < R; ++r) {
-    // robot r's field, then its path cost to every cluster's snapped centroid
-    if ((rc = plan_field_from(g, robots_xy + 2 * r, 1, max_cost, nullptr))) return rc;
-    out_cell[r] = -1;
-    out_xy[2 * r] = out_xy[2 * r + 1] = NAN;
-    if (K == 0) continue;
-    if ((rc = dm_plan_launch_query(g, &recs[0].cx_m, (int64_t)(sizeof(dm_cluster) / sizeof(double)), K, snap_cells,
-                                   g->plan_qcost, g->plan_qcell)))
-      return rc;
-    const unsigned long long* dk = nullptr;
-    const uint32_t* di = nullptr;
-    if ((rc = dm_launch_goal_topk(g, recs, K, nullptr, 1, T, min_size, distance_weight, min_distance, &dk, &di,
-                                  g->plan_qcost)))
-      return rc;
-    DM_HIP(hipMemcpyAsync(hk.data(), dk, sizeof(unsigned long long) * (size_t)T, hipMemcpyDeviceToHost, g->stream));
-    DM_HIP(hipMemcpyAsync(hi.data(), di, sizeof(uint32_t) * (size_t)T, hipMemcpyDeviceToHost, g->stream));
-    DM_HIP(hipStreamSynchronize(g->stream));
-    // greedy in robot order, as dm_assign_goals: the robot's choice is within
-    // the first r + 1 entries of its best-first list
-    for (int32_t t = 0; t < T; ++t) {
-      if (hk[(size_t)t] == 0ull) break;
-      const int64_t c = hi[(size_t)t];
-      if (std::find(idx.begin(), idx.begin() + r, c) != idx.begin() + r) continue;
-      idx[(size_t)r] = c;
-      break;
-    }
-    if (idx[(size_t)r] >= 0) {
-      int64_t cell = -1;
-      DM_HIP(hipMemcpy(&cell, g->plan_qcell + idx[(size_t)r], sizeof cell, hipMemcpyDeviceToHost));
-      out_cell[r] = cell;
-      // the centre of the snapped cell: a reachable goal, not the centroid
-      out_xy[2 * r] = g->p.origin_x + ((double)(cell % g->W) + 0.5) * g->p.resolution;
-      out_xy[2 * r + 1] = g->p.origin_y + ((double)(cell / g->W) + 0.5) * g->p.resolution;
-    }
-  }
-  memcpy(out_index, idx.data(), sizeof(int64_t) * (size_t)R);
-  return DM_OK;
-}
-
-// ---- information gain (csrc/dm_gain.h): visible-unknown counts of view
-// points, gain-scored goals ---------------------------------------------------------
-
-static int grow_gain(dm_grid* g, int64_t n) {
-  if (n <= g->gain_cap) return DM_OK;
-  g->gain_cap = 0;
-  int rc = dev_alloc(&g->gain_xy, 2 * n, "view points");
-  if (!rc) rc = dev_alloc(&g->gain_cell, n, "view cells");
-  if (!rc) rc = dev_alloc(&g->gain_out, n, "view gains");
-  if (!rc) rc = dev_alloc(&g->gain_skip, n, "view skip flags");
-  if (!rc) rc = dev_alloc(&g->gain_memo_cell, n, "gain memo cells");
-  if (!rc) rc = dev_alloc(&g->gain_memo_gain, n, "gain memo gains");
-  if (!rc) g->gain_cap = n;
-  return rc;
-}
-
-static int gain_check_radius(int32_t radius_cells) {
-  if (radius_cells < 1 || radius_cells > 511)
-    return dm_set_error(DM_ERR_INVALID_ARG, "radius_cells must be in [1, 511] (got %d)", radius_cells);
-  return DM_OK;
-}
-
-int dm_gain_views(dm_grid* g, const double* views_xy, int64_t n, int32_t radius_cells, uint32_t* out_gain,
-                  int64_t* out_cell) {
-  int rc = plan_check_handle(g, "dm_gain_views");
-  if (rc || (rc = use_device(g))) return rc;
-  if (n < 0 || n > (1ll << 20))
-    return dm_set_error(DM_ERR_INVALID_ARG, "n must be in [0, 2^20] (got %lld)", (long long)n);
-  if (n > 0 && (!views_xy || !out_gain || !out_cell))
-    return dm_set_error(DM_ERR_INVALID_ARG, "views_xy / out_gain / out_cell is NULL");
-  if ((rc = gain_check_radius(radius_cells))) return rc;
-  if (n == 0) return DM_OK;
-  if ((rc = grow_gain(g, n))) return rc;
-  DM_HIP(dm_sync_all(g));  // after everything enqueued on the handle, on every stream of it
-  DM_HIP(hipMemcpyAsync(g->gain_xy, views_xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, g->stream));
-  if ((rc = dm_gain_launch_cells(g, n))) return rc;
-  if ((rc = dm_gain_launch_views(g, g->gain_cell, nullptr, n, radius_cells, false))) return rc;
-  DM_HIP(hipMemcpyAsync(out_gain, g->gain_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-  DM_HIP(hipMemcpyAsync(out_cell, g->gain_cell, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-  DM_HIP(hipStreamSynchronize(g->stream));
-  return DM_OK;
-}
-
-// The claimed set of the overlap-aware calls: allocated by the first of them.
-static int64_t claimed_words(const dm_grid* g) { return g->H * ((g->W + 31) / 32); }
-
-static int ensure_claimed(dm_grid* g) {
-  if (g->gain_claimed) return DM_OK;
-  return dev_alloc(&g->gain_claimed, claimed_words(g), "claimed set");
-}
-
-// n points (metres) to g->gain_xy and their cells to g->gain_cell.
-static int gain_upload_views(dm_grid* g, const double* xy, int64_t n) {
-  if (n <= 0) return DM_OK;
-  DM_HIP(hipMemcpyAsync(g->gain_xy, xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, g->stream));
-  return dm_gain_launch_cells(g, n);
-}
-
-int dm_gain_views_joint(dm_grid* g, const double* views_xy, int64_t n, int32_t radius_cells, uint32_t* out_marginal,
-                        int64_t* out_cell) {
-  int rc = plan_check_handle(g, "dm_gain_views_joint");
-  if (rc || (rc = use_device(g))) return rc;
-  if (n < 0 || n > 1024) return dm_set_error(DM_ERR_INVALID_ARG, "n must be in [0, 1024] (got %lld)", (long long)n);
-  if (n > 0 && (!views_xy || !out_marginal || !out_cell))
-    return dm_set_error(DM_ERR_INVALID_ARG, "views_xy / out_marginal / out_cell is NULL");
-  if ((rc = gain_check_radius(radius_cells))) return rc;
-  if ((rc = ensure_claimed(g)) || (rc = grow_gain(g, std::max<int64_t>(n, 1)))) return rc;
-  DM_HIP(dm_sync_all(g));  // after everything enqueued on the handle, on every stream of it
-  g->gain_claimed_valid = false;
-  DM_HIP(hipMemsetAsync(g->gain_claimed, 0, sizeof(uint32_t) * (size_t)claimed_words(g), g->stream));
-  if ((rc = gain_upload_views(g, views_xy, n))) return rc;
-  if ((rc = dm_gain_launch_joint(g, g->gain_cell, n, radius_cells, g->gain_out))) return rc;
-  if (n > 0) {
-    DM_HIP(hipMemcpyAsync(out_marginal, g->gain_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-    DM_HIP(hipMemcpyAsync(out_cell, g->gain_cell, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
-  }
-  DM_HIP(hipStreamSynchronize(g->stream));
-  g->gain_claimed_valid = true;
-  return DM_OK;
-}
-
-int dm_gain_claimed(dm_grid* g, uint8_t* out) {
-  int rc = plan_check_handle(g, "dm_gain_claimed");
-  if (rc || (rc = use_device(g))) return rc;
-  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
-  if (!g->gain_claimed || !g->gain_claimed_valid)
-    return dm_set_error(DM_ERR_STATE, "dm_gain_claimed: no claimed set (call dm_gain_views_joint or "
-                        "dm_assign_goals_coord first)");
-  const int64_t cells = g->W * g->H;
-  uint8_t* d = nullptr;
-  if ((rc = dev_alloc(&d, cells, "claimed image"))) return rc;
-  rc = dm_gain_launch_expand(g, d);
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(out, d, (size_t)cells, hipMemcpyDeviceToHost, g->stream);
-  if (!rc && e == hipSuccess) e = hipStreamSynchronize(g->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess) return dm_hip_check(e, "dm_gain_claimed");
-  return rc;
-}
-
-// dm_assign_goals_gain (held_xy == nullptr, n_held == 0, coord == false) and
-// dm_assign_goals_coord: the same call but for the numerator, which with
-// `coord` is the marginal gain against the claimed set.
-static int assign_goals_gain_impl(dm_grid* g, const char* what, bool coord, const double* robots_xy, int32_t n_robots,
-                                  const double* held_xy, int32_t n_held, int64_t min_size, int64_t min_gain,
-                                  double distance_weight, double min_distance, int32_t inflate_cells,
-                                  uint32_t max_cost, int32_t snap_cells, int32_t radius_cells, int64_t* out_index,
-                                  double* out_xy, int64_t* out_cell, uint32_t* out_gain) {
-  int rc = plan_check_handle(g, what);
-  if (rc || (rc = use_device(g))) return rc;
-  if (n_robots < 0 || n_robots > 256)
-    return dm_set_error(DM_ERR_INVALID_ARG, "n_robots must be in [0, 256] (got %d)", n_robots);
-  if (n_robots > 0 && (!robots_xy || !out_index || !out_xy || !out_cell || !out_gain))
-    return dm_set_error(DM_ERR_INVALID_ARG, "robots_xy / out_index / out_xy / out_cell / out_gain is NULL");
-  if (!isfinite(distance_weight) || !isfinite(min_distance))
-    return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight / min_distance must be finite");
-  if (distance_weight < 0.0)  // as dm_assign_goals: the device ranks by the util's IEEE bits
-    return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight must be >= 0");
-  if (min_gain < 0) return dm_set_error(DM_ERR_INVALID_ARG, "min_gain must be >= 0 (got %lld)", (long long)min_gain);
-  if (n_held < 0 || n_held > 1024)
-    return dm_set_error(DM_ERR_INVALID_ARG, "n_held must be in [0, 1024] (got %d)", n_held);
-  if (n_held > 0 && !held_xy) return dm_set_error(DM_ERR_INVALID_ARG, "held_xy is NULL");
-  if ((rc = plan_check_inflate(inflate_cells)) || (rc = plan_check_snap(snap_cells)) ||
-      (rc = gain_check_radius(radius_cells)))
-    return rc;
-  const int s = g->goal_slot;
-  if (s < 0 || g->goal_gen != g->rb_gen ||
-      (g->goal_kind == 1 ? g->rb[s].wepoch : g->rb[s].mepoch) != g->goal_epoch)
-    return dm_set_error(DM_ERR_INVALID_ARG, "no collected frontier result on the device (call dm_frontiers, "
-                                            "dm_frontiers_end or dm_merge_bands first; a later pass may have "
-                                            "reused its readback slot)");
-  if (n_robots == 0 && !coord) return DM_OK;
-  for (int32_t r = 0; r < n_robots; ++r) {
-    int64_t c;
-    if (!plan_cell_of(g, robots_xy[2 * r], robots_xy[2 * r + 1], &c))
-      return dm_set_error(DM_ERR_INVALID_ARG, "robot %d (%g, %g) is outside the grid", r, robots_xy[2 * r],
-                          robots_xy[2 * r + 1]);
-  }
-  const dm_cluster* recs = g->goal_kind == 1 ? g->rb[s].out_clu : g->rb[s].m_out;
-  const int64_t K = g->goal_n;
-  if ((rc = ensure_plan(g)) || (rc = grow_plan_query(g, std::max<int64_t>(K, 1))) ||
-      (rc = grow_gain(g, std::max<int64_t>(std::max<int64_t>(K, n_held), 1))))
-    return rc;
-  if (coord && (rc = ensure_claimed(g))) return rc;
-  DM_HIP(dm_join_pass_stream(g));
-  if (coord) {
-    // C: empty, then the held views, all in one launch (ORs commute)
-    g->gain_claimed_valid = false;
-    DM_HIP(hipMemsetAsync(g->gain_claimed, 0, sizeof(uint32_t) * (size_t)claimed_words(g), g->stream));
-    if ((rc = gain_upload_views(g, held_xy, n_held))) return rc;
-    if ((rc = dm_gain_launch_commit(g, g->gain_cell, n_held, radius_cells))) return rc;
-    if (n_robots == 0) {
-      DM_HIP(hipStreamSynchronize(g->stream));
-      g->gain_claimed_valid = true;
-      return DM_OK;
-    }
-  }
-  if ((rc = dm_plan_launch_travers(g, inflate_cells))) return rc;
-  // the memo of this call: no cluster has a cast yet (every byte 0xFF: cell -1,
-  // which no cast view has)
-  if (K > 0) DM_HIP(hipMemsetAsync(g->gain_memo_cell, 0xFF, sizeof(int64_t) * (size_t)K, g->stream));
-  const int32_t R = n_robots, T = n_robots;
-  std::vector<int64_t> idx((size_t)R, -1);
-  std::vector<unsigned long long> hk((size_t)T);
-  std::vector<uint32_t> hi((size_t)T);
-  for (int32_t r = 0; r < R; ++r) {
-    // robot r's field, its path cost to every cluster's snapped centroid, then
-    // the gain of every snapped cell that can still be a goal
-    if ((rc = plan_field_from(g, robots_xy + 2 * r, 1, max_cost, nullptr))) return rc;
-    out_cell[r] = -1;
-    out_gain[r] = 0u;
-    out_xy[2 * r] = out_xy[2 * r + 1] = NAN;
-    if (K == 0) continue;
-    if ((rc = dm_plan_launch_query(g, &recs[0].cx_m, (int64_t)(sizeof(dm_cluster) / sizeof(double)), K, snap_cells,
-                                   g->plan_qcost, g->plan_qcell)))
-      return rc;
-    if ((rc = dm_gain_launch_skip(g, recs, g->plan_qcost, K, min_size))) return rc;
-    if ((rc = coord ? dm_gain_launch_marginal(g, g->plan_qcell, g->gain_skip, K, radius_cells, true)
-                    : dm_gain_launch_views(g, g->plan_qcell, g->gain_skip, K, radius_cells, true)))
-      return rc;
-    const unsigned long long* dk = nullptr;
-    const uint32_t* di = nullptr;
-    if ((rc = dm_launch_goal_topk(g, recs, K, nullptr, 1, T, min_size, distance_weight, min_distance, &dk, &di,
-                                  g->plan_qcost, g->gain_out, min_gain)))
-      return rc;
-    DM_HIP(hipMemcpyAsync(hk.data(), dk, sizeof(unsigned long long) * (size_t)T, hipMemcpyDeviceToHost, g->stream));
-    DM_HIP(hipMemcpyAsync(hi.data(), di, sizeof(uint32_t) * (size_t)T, hipMemcpyDeviceToHost, g->stream));
-    DM_HIP(hipStreamSynchronize(g->stream));
-    // greedy in robot order, as dm_assign_goals_path
-    for (int32_t t = 0; t < T; ++t) {
-      if (hk[(size_t)t] == 0ull) break;
-      const int64_t c = hi[(size_t)t];
-      if (std::find(idx.begin(), idx.begin() + r, c) != idx.begin() + r) continue;
-      idx[(size_t)r] = c;
-      break;
-    }
-    if (idx[(size_t)r] >= 0) {
-      int64_t cell = -1;
-      uint32_t gain = 0u;
-      DM_HIP(hipMemcpy(&cell, g->plan_qcell + idx[(size_t)r], sizeof cell, hipMemcpyDeviceToHost));
-      DM_HIP(hipMemcpy(&gain, g->gain_out + idx[(size_t)r], sizeof gain, hipMemcpyDeviceToHost));
-      out_cell[r] = cell;
-      out_gain[r] = gain;
-      out_xy[2 * r] = g->p.origin_x + ((double)(cell % g->W) + 0.5) * g->p.resolution;
-      out_xy[2 * r + 1] = g->p.origin_y + ((double)(cell / g->W) + 0.5) * g->p.resolution;
-      if (coord) {
-        // the goal's view joins C before the next robot is scored; its gain
-        // is > 0, so C changed and no memo entry holds any longer
-        if ((rc = dm_gain_launch_commit(g, g->plan_qcell + idx[(size_t)r], 1, radius_cells))) return rc;
-        DM_HIP(hipMemsetAsync(g->gain_memo_cell, 0xFF, sizeof(int64_t) * (size_t)K, g->stream));
-      }
-    }
-  }
-  if (coord) {
-    DM_HIP(hipStreamSynchronize(g->stream));
-    g->gain_claimed_valid = true;
-  }
-  memcpy(out_index, idx.data(), sizeof(int64_t) * (size_t)R);
-  return DM_OK;
-}
-
-int dm_assign_goals_gain(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size, int64_t min_gain,
-                         double distance_weight, double min_distance, int32_t inflate_cells, uint32_t max_cost,
-                         int32_t snap_cells, int32_t radius_cells, int64_t* out_index, double* out_xy,
-                         int64_t* out_cell, uint32_t* out_gain) {
-  return assign_goals_gain_impl(g, "dm_assign_goals_gain", false, robots_xy, n_robots, nullptr, 0, min_size, min_gain,
-                                distance_weight, min_distance, inflate_cells, max_cost, snap_cells, radius_cells,
-                                out_index, out_xy, out_cell, out_gain);
-}
-
-int dm_assign_goals_coord(dm_grid* g, const double* robots_xy, int32_t n_robots, const double* held_xy,
-                          int32_t n_held, int64_t min_size, int64_t min_gain, double distance_weight,
-                          double min_distance, int32_t inflate_cells, uint32_t max_cost, int32_t snap_cells,
-                          int32_t radius_cells, int64_t* out_index, double* out_xy, int64_t* out_cell,
-                          uint32_t* out_gain) {
-  return assign_goals_gain_impl(g, "dm_assign_goals_coord", true, robots_xy, n_robots, held_xy, n_held, min_size,
-                                min_gain, distance_weight, min_distance, inflate_cells, max_cost, snap_cells,
-                                radius_cells, out_index, out_xy, out_cell, out_gain);
-}
-
-// ---- scan matcher (csrc/dm_match.h): response field, score volume, best
-// candidate ----------------------------------------------------------------------
-
-static int match_check_table(int32_t smear_cells, const uint8_t* kern) {
-  if (smear_cells < 0 || smear_cells > 16)
-    return dm_set_error(DM_ERR_INVALID_ARG, "smear_cells must be in [0, 16] (got %d)", smear_cells);
-  if (!kern) return dm_set_error(DM_ERR_INVALID_ARG, "kern is NULL");
-  return DM_OK;
-}
-
-// The field's table and map version: a change drops every built tile.
-static int match_set_table(dm_grid* g, int32_t r, const uint8_t* kern) {
-  int rc = DM_OK;
-  if (!g->match_V) {
-    if ((rc = dev_alloc(&g->match_kern, 16 * 16 + 1, "smear table"))) return rc;
-    if ((rc = dev_alloc(&g->match_tiles, g->NT, "match tile list"))) return rc;
-    if ((rc = dev_alloc(&g->match_V, g->W * g->H, "response field"))) return rc;
-    g->match_r = -1;
-  }
-  const size_t n = (size_t)r * r + 1;
-  const uint64_t version = plan_map_version(g);
-  if (g->match_r == r && g->match_version == version && g->match_kern_h.size() == n &&
-      memcmp(g->match_kern_h.data(), kern, n) == 0)
-    return DM_OK;
-  g->match_r = -1;
-  g->match_built.assign((size_t)g->NT, 0);
-  ++g->match_epoch;
-  g->match_kern_h.assign(kern, kern + n);
-  // pageable source: the copy is staged before the call returns
-  DM_HIP(hipMemcpyAsync(g->match_kern, g->match_kern_h.data(), n, hipMemcpyHostToDevice, g->stream));
-  g->match_r = r;
-  g->match_version = version;
-  return DM_OK;
-}
-
-// Build the tiles of `want` (one flag per tile) that the field does not hold yet.
-static int match_build_tiles(dm_grid* g, const std::vector<uint8_t>& want) {
-  std::vector<int32_t> list;
-  for (int64_t t = 0; t < g->NT; ++t)
-    if (want[(size_t)t] && !g->match_built[(size_t)t]) list.push_back((int32_t)t);
-  if (list.empty()) return DM_OK;
-  bool mono = true;  // kern does not increase in d2: the nearest occupied cell decides
-  for (size_t i = 1; i < g->match_kern_h.size(); ++i) mono = mono && g->match_kern_h[i] <= g->match_kern_h[i - 1];
-  DM_HIP(hipMemcpyAsync(g->match_tiles, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, g->stream));
-  DM_HIP(hipStreamSynchronize(g->stream));  // `list` is a local
-  int rc = dm_match_launch_field(g, (int32_t)list.size(), g->match_r, mono);
-  if (rc) return rc;
-  for (int32_t t : list) g->match_built[(size_t)t] = 1;
-  return DM_OK;
-}
-
-int dm_match_field(dm_grid* g, int32_t smear_cells, const uint8_t* kern, uint8_t* out) {
-  int rc = plan_check_handle(g, "dm_match_field");
-  if (rc || (rc = use_device(g))) return rc;
-  if ((rc = match_check_table(smear_cells, kern))) return rc;
-  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
-  DM_HIP(dm_sync_all(g));
-  if ((rc = match_set_table(g, smear_cells, kern))) return rc;
-  if ((rc = match_build_tiles(g, std::vector<uint8_t>((size_t)g->NT, 1)))) return rc;
-  DM_HIP(hipMemcpyAsync(out, g->match_V, (size_t)(g->W * g->H), hipMemcpyDeviceToHost, g->stream));
-  DM_HIP(hipStreamSynchronize(g->stream));
-  return DM_OK;
-}
-
-int dm_match_scans(dm_grid* g, int32_t S, const double* poses, int32_t N, const float* ranges, float angle_min,
-                   float angle_increment, int32_t A, const double* yaw_offsets, int32_t k0, int32_t sub,
-                   int32_t half, int32_t stride, int32_t smear_cells, const uint8_t* kern, int32_t* out_best,
-                   uint32_t* out_score, int32_t* out_n_used, double* out_pose, uint32_t* out_volume) {
-  int rc = plan_check_handle(g, "dm_match_scans");
-  if (rc || (rc = use_device(g))) return rc;
-  if ((rc = check_integrate_args(S, N, poses, ranges))) return rc;
-  if (A < 1 || A > 64) return dm_set_error(DM_ERR_INVALID_ARG, "A must be in [1, 64] (got %d)", A);
-  if (k0 < 0 || k0 >= A) return dm_set_error(DM_ERR_INVALID_ARG, "k0 must be in [0, A) (got %d, A = %d)", k0, A);
-  if (sub < 1 || sub > 16) return dm_set_error(DM_ERR_INVALID_ARG, "sub must be in [1, 16] (got %d)", sub);
-  if (half < 0 || half > 32) return dm_set_error(DM_ERR_INVALID_ARG, "half must be in [0, 32] (got %d)", half);
-  if (stride < 1 || stride > 16)
-    return dm_set_error(DM_ERR_INVALID_ARG, "stride must be in [1, 16] (got %d)", stride);
-  if ((rc = match_check_table(smear_cells, kern))) return rc;
-  if (!yaw_offsets) return dm_set_error(DM_ERR_INVALID_ARG, "yaw_offsets is NULL");
-  if (S > 0 && (!poses || !out_best || !out_score || !out_n_used || !out_pose))
-    return dm_set_error(DM_ERR_INVALID_ARG, "poses / out_best / out_score / out_n_used / out_pose is NULL");
-  if ((int64_t)S * A * std::max(N, 1) > (1ll << 31) - 1)
-    return dm_set_error(DM_ERR_SHAPE, "S*A*N must be < 2^31");
-  if (S == 0) return DM_OK;
-  DM_HIP(dm_sync_all(g));  // after everything enqueued on the handle, on every stream of it
-  if ((rc = match_set_table(g, smear_cells, kern))) return rc;
-
-  const int64_t SA = (int64_t)S * A, T1 = 2 * half + 1, T = T1 * T1, nb = (int64_t)S * N;
-  if ((rc = dev_grow(&g->match_pose4, &g->match_pose_cap, 4 * SA, "candidate poses")) ||
-      (rc = dev_grow(&g->match_trig, &g->match_trig_cap, 2 * (int64_t)N, "beam angle table")) ||
-      (rc = dev_grow(&g->match_ranges, &g->match_ranges_cap, nb, "ranges")) ||
-      (rc = dev_grow(&g->match_q, &g->match_q_cap, SA * N, "fine coordinates")) ||
-      (rc = dev_grow(&g->match_vol, &g->match_vol_cap, SA * T, "score volume")) ||
-      (rc = dev_grow(&g->match_out, &g->match_out_cap, 5 * (int64_t)S, "match results")))
-    return rc;
-
-  // host trigonometry with the C library, as dm_integrate: the beam angle
-  // table and cos / sin of every candidate yaw (one double add each)
-  const double step = g->p.resolution / (double)sub;
-  std::vector<double> trig(2 * (size_t)N), pose4(4 * (size_t)SA);
-  for (int32_t i = 0; i < N; ++i) {
-    const double phi = (double)angle_min + (double)i * (double)angle_increment;
-    trig[2 * (size_t)i] = cos(phi);
-    trig[2 * (size_t)i + 1] = sin(phi);
-  }
-  // the tiles the search windows reach: every used beam ends within range_max
-  // of its pose and a translation moves it by at most half * stride fine
-  // steps; two cells of slack cover the rounding of the endpoint arithmetic
-  std::vector<uint8_t> want((size_t)g->NT, 0);
-  const double reach = (double)g->p.range_max + (double)(half * stride + 1) * step + 2.0 * g->p.resolution;
-  for (int32_t s = 0; s < S; ++s) {
-    const double x = poses[3 * s], y = poses[3 * s + 1], yaw = poses[3 * s + 2];
-    for (int32_t k = 0; k < A; ++k) {
-      const double yk = yaw + yaw_offsets[k];
-      double* p4 = &pose4[4 * ((size_t)s * A + k)];
-      p4[0] = x;
-      p4[1] = y;
-      p4[2] = cos(yk);
-      p4[3] = sin(yk);
-    }
-    if (!(isfinite(x) && isfinite(y)) || N == 0) continue;
-    const double fx0 = floor((x - reach - g->p.origin_x) / g->p.resolution) - 1.0;
-    const double fx1 = floor((x + reach - g->p.origin_x) / g->p.resolution) + 1.0;
-    const double fy0 = floor((y - reach - g->p.origin_y) / g->p.resolution) - 1.0;
-    const double fy1 = floor((y + reach - g->p.origin_y) / g->p.resolution) + 1.0;
-    if (!(fx1 >= 0.0 && fy1 >= 0.0 && fx0 < (double)g->W && fy0 < (double)g->H)) continue;
-    const int64_t tx0 = (int64_t)std::max(fx0, 0.0) / DM_TILE, ty0 = (int64_t)std::max(fy0, 0.0) / DM_TILE;
-    const int64_t tx1 = (int64_t)std::min(fx1, (double)(g->W - 1)) / DM_TILE;
-    const int64_t ty1 = (int64_t)std::min(fy1, (double)(g->H - 1)) / DM_TILE;
-    for (int64_t ty = ty0; ty <= ty1; ++ty)
-      for (int64_t tx = tx0; tx <= tx1; ++tx) want[(size_t)(ty * g->TX + tx)] = 1;
-  }
-  if ((rc = match_build_tiles(g, want))) return rc;
-
-  hipStream_t st = g->stream;
-  DM_HIP(hipMemcpyAsync(g->match_pose4, pose4.data(), sizeof(double) * pose4.size(), hipMemcpyHostToDevice, st));
-  if (N > 0) {
-    DM_HIP(hipMemcpyAsync(g->match_trig, trig.data(), sizeof(double) * trig.size(), hipMemcpyHostToDevice, st));
-    DM_HIP(hipMemcpyAsync(g->match_ranges, ranges, sizeof(float) * (size_t)nb, hipMemcpyHostToDevice, st));
-  }
-  if ((rc = dm_match_launch_scans(g, S, N, A, k0, sub, half, stride))) return rc;
-  std::vector<int32_t> res(5 * (size_t)S);
-  DM_HIP(hipMemcpyAsync(res.data(), g->match_out, sizeof(int32_t) * res.size(), hipMemcpyDeviceToHost, st));
-  if (out_volume)
-    DM_HIP(hipMemcpyAsync(out_volume, g->match_vol, sizeof(uint32_t) * (size_t)(SA * T), hipMemcpyDeviceToHost, st));
-  DM_HIP(hipStreamSynchronize(st));
-  for (int32_t s = 0; s < S; ++s) {
-    const int32_t k = res[4 * (size_t)s], i = res[4 * (size_t)s + 1], j = res[4 * (size_t)s + 2];
-    out_best[3 * s] = k;
-    out_best[3 * s + 1] = i;
-    out_best[3 * s + 2] = j;
-    out_score[s] = (uint32_t)res[4 * (size_t)s + 3];
-    out_n_used[s] = res[4 * (size_t)S + s];
-    out_pose[3 * s] = poses[3 * s] + (double)(i * stride) * step;
-    out_pose[3 * s + 1] = poses[3 * s + 1] + (double)(j * stride) * step;
-    out_pose[3 * s + 2] = poses[3 * s + 2] + yaw_offsets[k];
-  }
-  return DM_OK;
-}
-
-// ---- whole-window relocalisation (csrc/dm_match_global.h) -----------------------
-
-static int ensure_match_global(dm_grid* g) {
-  int rc = DM_OK;
-  if (!g->h_mg) {
-    hipError_t e = hipHostMalloc((void**)&g->h_mg, sizeof(uint32_t) * 8, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e != hipSuccess) {
-      g->h_mg = nullptr;
-      return dm_hip_check(e, "hipHostMalloc(relocalisation rounds)");
-    }
-    memset(g->h_mg, 0, sizeof(uint32_t) * 8);
-    DM_HIP(hipHostGetDevicePointer((void**)&g->h_mg_dev, g->h_mg, 0));
-  }
-  if (g->mg_best) return DM_OK;  // allocated last
-  if ((rc = dev_alloc(&g->mg_hist, 2048, "bound histogram"))) return rc;
-  if ((rc = dev_alloc(&g->mg_ctl, 4, "round control words"))) return rc;
-  if ((rc = dev_alloc(&g->mg_list, dm_grid::kMgExhaustiveBatch, "round block list"))) return rc;
-  if ((rc = dev_alloc(&g->mg_cand, dm_grid::kMgExhaustiveBatch, "round candidates"))) return rc;
-  if ((rc = dev_alloc(&g->mg_nused, 1, "used beams"))) return rc;
-  return dev_alloc(&g->mg_best, 1, "best candidate");
-}
-
-int dm_match_global(dm_grid* g, int32_t S, const double* poses, int32_t N, const float* ranges, float angle_min,
-                    float angle_increment, int32_t A, const double* yaw_offsets, int32_t k0, int32_t half_x,
-                    int32_t half_y, int32_t block, int32_t exhaustive, int32_t smear_cells, const uint8_t* kern,
-                    int32_t* out_best, uint32_t* out_score, int32_t* out_n_used, double* out_pose,
-                    uint64_t* out_stats) {
-  int rc = plan_check_handle(g, "dm_match_global");
-  if (rc || (rc = use_device(g))) return rc;
-  if ((rc = check_integrate_args(S, N, poses, ranges))) return rc;
-  if (A < 1 || A > 1024) return dm_set_error(DM_ERR_INVALID_ARG, "A must be in [1, 1024] (got %d)", A);
-  if (k0 < 0 || k0 >= A) return dm_set_error(DM_ERR_INVALID_ARG, "k0 must be in [0, A) (got %d, A = %d)", k0, A);
-  if (half_x < 0 || half_x > 4096 || half_y < 0 || half_y > 4096)
-    return dm_set_error(DM_ERR_INVALID_ARG, "half_x and half_y must be in [0, 4096] (got %d, %d)", half_x, half_y);
-  if (block != 4 && block != 8 && block != 16 && block != 32)
-    return dm_set_error(DM_ERR_INVALID_ARG, "block must be 4, 8, 16 or 32 (got %d)", block);
-  if (exhaustive != 0 && exhaustive != 1)
-    return dm_set_error(DM_ERR_INVALID_ARG, "exhaustive must be 0 or 1 (got %d)", exhaustive);
-  if ((rc = match_check_table(smear_cells, kern))) return rc;
-  if (!yaw_offsets) return dm_set_error(DM_ERR_INVALID_ARG, "yaw_offsets is NULL");
-  if (S > 0 && (!poses || !out_best || !out_score || !out_n_used || !out_pose))
-    return dm_set_error(DM_ERR_INVALID_ARG, "poses / out_best / out_score / out_n_used / out_pose is NULL");
-  if ((int64_t)A * std::max(N, 1) > (1ll << 31) - 1) return dm_set_error(DM_ERR_SHAPE, "A*N must be < 2^31");
-  if (g->W > (1ll << 20) || g->H > (1ll << 20))
-    return dm_set_error(DM_ERR_SHAPE, "dm_match_global needs a map of at most 2^20 cells a side");
-  MgShape sh;
-  sh.N = N;
-  sh.A = A;
-  sh.k0 = k0;
-  sh.half_x = half_x;
-  sh.half_y = half_y;
-  sh.lb = block == 4 ? 2 : block == 8 ? 3 : block == 16 ? 4 : 5;
-  sh.nbx = (2 * half_x + 1 + block - 1) / block;
-  sh.nby = (2 * half_y + 1 + block - 1) / block;
-  sh.exhaustive = exhaustive;
-  const int64_t blocks = (int64_t)A * sh.nbx * sh.nby;
-  if (blocks > (1ll << 26))
-    return dm_set_error(DM_ERR_CAPACITY, "%lld blocks per scan, the limit is 2^26: use a larger block (got %d)",
-                        (long long)blocks, block);
-  // the pooled field's extended coordinates e = c + block - 1, padded to whole blocks
-  const int64_t EWB = (g->W + block - 1 + block - 1) / block, EHB = (g->H + block - 1 + block - 1) / block;
-  if ((int64_t)block * block * EWB * EHB > (1ll << 31) - 1)
-    return dm_set_error(DM_ERR_SHAPE, "dm_match_global: the pooled field of this map needs 2^31 bytes or more");
-  sh.EWB = (int32_t)EWB;
-  sh.EHB = (int32_t)EHB;
-  const int64_t PTX = (EWB * block + 63) / 64, PTY = (EHB * block + 63) / 64;
-  if (S == 0) return DM_OK;
-  DM_HIP(dm_sync_all(g));  // after everything enqueued on the handle, on every stream of it
-  if ((rc = match_set_table(g, smear_cells, kern))) return rc;
-  if ((rc = ensure_match_global(g))) return rc;
-
-  const int64_t SA = (int64_t)S * A, nbm = (int64_t)S * N;
-  if ((rc = dev_grow(&g->match_pose4, &g->match_pose_cap, 4 * SA, "candidate poses")) ||
-      (rc = dev_grow(&g->match_trig, &g->match_trig_cap, 2 * (int64_t)N, "beam angle table")) ||
-      (rc = dev_grow(&g->match_ranges, &g->match_ranges_cap, nbm, "ranges")) ||
-      (rc = dev_grow(&g->match_q, &g->match_q_cap, (int64_t)A * N, "fine coordinates")))
-    return rc;
-  if (!exhaustive) {
-    if ((rc = dev_grow(&g->mg_bound, &g->mg_bound_cap, blocks, "block bounds")) ||
-        (rc = dev_grow(&g->mg_pool, &g->mg_pool_cap, (int64_t)block * block * EWB * EHB, "pooled response field")) ||
-        (rc = dev_grow(&g->mg_ptiles, &g->mg_ptiles_cap, PTX * PTY, "pool tile list")))
-      return rc;
-    if (g->mg_pool_block != block || g->mg_pool_epoch != g->match_epoch ||
-        g->mg_pool_built.size() != (size_t)(PTX * PTY)) {
-      g->mg_pool_built.assign((size_t)(PTX * PTY), 0);
-      g->mg_pool_block = block;
-      g->mg_pool_epoch = g->match_epoch;
-    }
-  }
-
-  const double res = g->p.resolution;
-  std::vector<double> trig(2 * (size_t)N), pose4(4 * (size_t)SA);
-  for (int32_t i = 0; i < N; ++i) {
-    const double phi = (double)angle_min + (double)i * (double)angle_increment;
-    trig[2 * (size_t)i] = cos(phi);
-    trig[2 * (size_t)i + 1] = sin(phi);
-  }
-  for (int32_t s = 0; s < S; ++s)
-    for (int32_t k = 0; k < A; ++k) {
-      const double yk = poses[3 * s + 2] + yaw_offsets[k];
-      double* p4 = &pose4[4 * ((size_t)s * A + k)];
-      p4[0] = poses[3 * s];
-      p4[1] = poses[3 * s + 1];
-      p4[2] = cos(yk);
-      p4[3] = sin(yk);
-    }
-  hipStream_t st = g->stream;
-  DM_HIP(hipMemcpyAsync(g->match_pose4, pose4.data(), sizeof(double) * pose4.size(), hipMemcpyHostToDevice, st));
-  if (N > 0) {
-    DM_HIP(hipMemcpyAsync(g->match_trig, trig.data(), sizeof(double) * trig.size(), hipMemcpyHostToDevice, st));
-    DM_HIP(hipMemcpyAsync(g->match_ranges, ranges, sizeof(float) * (size_t)nbm, hipMemcpyHostToDevice, st));
-  }
-  DM_HIP(hipStreamSynchronize(st));  // pose4 and trig are locals
-
-  for (int32_t s = 0; s < S; ++s) {
-    const double x = poses[3 * s], y = poses[3 * s + 1];
-    int32_t r5[5] = {k0, 0, 0, 0, 0};
-    uint64_t stats[4] = {(uint64_t)blocks, 0, 0, 0};
-    if (N > 0 && isfinite(x) && isfinite(y)) {
-      // the cells the window reaches: every used beam ends within range_max of
-      // the pose and a translation moves it by at most half cells; two cells
-      // of slack cover the rounding of the endpoint arithmetic
-      const double reach_x = (double)g->p.range_max + (double)(half_x + 1) * res + 2.0 * res;
-      const double reach_y = (double)g->p.range_max + (double)(half_y + 1) * res + 2.0 * res;
-      const double fx0 = floor((x - reach_x - g->p.origin_x) / res) - 1.0;
-      const double fx1 = floor((x + reach_x - g->p.origin_x) / res) + 1.0;
-      const double fy0 = floor((y - reach_y - g->p.origin_y) / res) - 1.0;
-      const double fy1 = floor((y + reach_y - g->p.origin_y) / res) + 1.0;
-      std::vector<uint8_t> want((size_t)g->NT, 0);
-      std::vector<int32_t> plist;
-      if (exhaustive) {
-        if (fx1 >= 0.0 && fy1 >= 0.0 && fx0 < (double)g->W && fy0 < (double)g->H) {
-          const int64_t tx0 = (int64_t)std::max(fx0, 0.0) / DM_TILE, ty0 = (int64_t)std::max(fy0, 0.0) / DM_TILE;
-          const int64_t tx1 = (int64_t)std::min(fx1, (double)(g->W - 1)) / DM_TILE;
-          const int64_t ty1 = (int64_t)std::min(fy1, (double)(g->H - 1)) / DM_TILE;
-          for (int64_t ty = ty0; ty <= ty1; ++ty)
-            for (int64_t tx = tx0; tx <= tx1; ++tx) want[(size_t)(ty * g->TX + tx)] = 1;
-        }
-      } else {
-        // M_B is read at the cells c in [f0, f1] with c >= -(block - 1): the
-        // pool tiles that hold them, and for each the field tiles its patch
-        // [64 p - (block - 1), 64 p + 63] meets
-        const double lo = -(double)(block - 1);
-        if (fx1 >= lo && fy1 >= lo && fx0 < (double)g->W && fy0 < (double)g->H) {
-          const int64_t px0 = ((int64_t)std::max(fx0, lo) + block - 1) / 64;
-          const int64_t py0 = ((int64_t)std::max(fy0, lo) + block - 1) / 64;
-          const int64_t px1 = ((int64_t)std::min(fx1, (double)(g->W - 1)) + block - 1) / 64;
-          const int64_t py1 = ((int64_t)std::min(fy1, (double)(g->H - 1)) + block - 1) / 64;
-          for (int64_t py = py0; py <= py1; ++py)
-            for (int64_t px = px0; px <= px1; ++px) {
-              if (!g->mg_pool_built[(size_t)(py * PTX + px)]) plist.push_back((int32_t)(py * PTX + px));
-              const int64_t tx0 = std::max<int64_t>(64 * px - (block - 1), 0) / DM_TILE;
-              const int64_t ty0 = std::max<int64_t>(64 * py - (block - 1), 0) / DM_TILE;
-              const int64_t tx1 = std::min<int64_t>(px, g->TX - 1), ty1 = std::min<int64_t>(py, g->NT / g->TX - 1);
-              for (int64_t ty = ty0; ty <= ty1; ++ty)
-                for (int64_t tx = tx0; tx <= tx1; ++tx) want[(size_t)(ty * g->TX + tx)] = 1;
-            }
-        }
-      }
-      if ((rc = match_build_tiles(g, want))) return rc;
-      if (!plist.empty()) {
-        DM_HIP(hipMemcpyAsync(g->mg_ptiles, plist.data(), sizeof(int32_t) * plist.size(), hipMemcpyHostToDevice, st));
-        DM_HIP(hipStreamSynchronize(st));  // `plist` is a local
-        if ((rc = dm_mg_launch_pool(g, (int32_t)plist.size(), sh.lb, sh.EWB, sh.EHB, (int32_t)PTX))) return rc;
-        for (int32_t t : plist) g->mg_pool_built[(size_t)t] = 1;
-      }
-      if ((rc = dm_mg_run_scan(g, sh, g->match_pose4 + 4 * (size_t)s * A, g->match_ranges + (size_t)s * N, r5, stats)))
-        return rc;
-    }
-    const int32_t k = r5[0], i = r5[1], j = r5[2];
-    out_best[3 * s] = k;
-    out_best[3 * s + 1] = i;
-    out_best[3 * s + 2] = j;
-    out_score[s] = (uint32_t)r5[3];
-    out_n_used[s] = r5[4];
-    out_pose[3 * s] = poses[3 * s] + (double)i * res;
-    out_pose[3 * s + 1] = poses[3 * s + 1] + (double)j * res;
-    out_pose[3 * s + 2] = poses[3 * s + 2] + yaw_offsets[k];
-    if (out_stats)
-      for (int m = 0; m < 4; ++m) out_stats[4 * s + m] = stats[m];
-  }
   return DM_OK;
 }
 

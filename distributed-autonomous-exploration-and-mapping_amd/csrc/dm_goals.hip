@@ -15,12 +15,19 @@
 // chunk lists — and the host runs the O(R^2) greedy over those lists.  The
 // records are the label-sorted list of the last collected frontier result, so
 // "smaller label" is "smaller record index".
+//
+// The planner (dm_plan.h) and the information gain (dm_gain.h) live here too,
+// kernels' launchers and entry points: dm_assign_goals_path, _gain and _coord
+// are one loop (assign_goals_field) over a robot's distance field, the snapped
+// cells of the cluster centroids, their gains and the same top-R lists.
+#include <math.h>
+#include <string.h>
+
 #include <algorithm>
+#include <vector>
 
 #include "dm_gain.h"
 #include "dm_internal.h"
-#include "dm_match.h"
-#include "dm_match_global.h"
 #include "dm_plan.h"
 
 namespace {
@@ -151,7 +158,7 @@ __global__ void k_goal_gather(const dm_cluster* __restrict__ recs, const int64_t
 
 }  // namespace
 
-int dm_launch_goal_gather(dm_grid* g, const dm_cluster* d_recs, const int64_t* d_idx, int32_t R, double* d_xy) {
+static int dm_launch_goal_gather(dm_grid* g, const dm_cluster* d_recs, const int64_t* d_idx, int32_t R, double* d_xy) {
   hipLaunchKernelGGL(k_goal_gather, dim3((R + 63) / 64), dim3(64), 0, g->stream, d_recs, d_idx, R, d_xy);
   DM_HIP(hipGetLastError());
   return DM_OK;
@@ -162,10 +169,10 @@ int dm_launch_goal_gather(dm_grid* g, const dm_cluster* d_recs, const int64_t* d
 // d_cost: [R][K] path costs in place of the Euclidean distance (d_robots is
 // then not read), or nullptr.  d_gain (with d_cost, R == 1): [K] gains, the
 // numerator in place of the size, with min_gain; or nullptr.
-int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, const double* d_robots, int32_t R,
-                        int32_t T, int64_t min_size, double w, double min_dist,
-                        const unsigned long long** d_k, const uint32_t** d_i, const uint32_t* d_cost,
-                        const uint32_t* d_gain, int64_t min_gain) {
+static int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, const double* d_robots, int32_t R,
+                               int32_t T, int64_t min_size, double w, double min_dist,
+                               const unsigned long long** d_k, const uint32_t** d_i, const uint32_t* d_cost = nullptr,
+                               const uint32_t* d_gain = nullptr, int64_t min_gain = 0) {
   const int64_t nch = (K + kGoalN - 1) / kGoalN;
   const int64_t need = (int64_t)R * std::max<int64_t>(nch, 1) * T;
   if (need > g->goal_cap) {
@@ -216,7 +223,7 @@ int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, const d
 
 // ---- path planning (dm_plan.h) ----------------------------------------------
 
-int dm_plan_launch_travers(dm_grid* g, int32_t inflate_cells) {
+static int dm_plan_launch_travers(dm_grid* g, int32_t inflate_cells) {
   DM_HIP(hipMemsetAsync(g->plan_stat + dm_plan::ST_TRAV, 0, sizeof(unsigned long long), g->stream));
   KernelTimer t;
   dm_timer_begin(g, "plan_travers", &t);
@@ -227,7 +234,7 @@ int dm_plan_launch_travers(dm_grid* g, int32_t inflate_cells) {
   return DM_OK;
 }
 
-int dm_plan_launch_expand(dm_grid* g, uint8_t* d_out) {
+static int dm_plan_launch_expand(dm_grid* g, uint8_t* d_out) {
   const int64_t cells = g->W * g->H;
   hipLaunchKernelGGL(dm_plan::k_plan_expand, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, g->stream,
                      g->plan_trav, g->W, g->H, g->TX, d_out);
@@ -235,7 +242,9 @@ int dm_plan_launch_expand(dm_grid* g, uint8_t* d_out) {
   return DM_OK;
 }
 
-int dm_plan_run_field(dm_grid* g, const int64_t* cells, int32_t n, const int32_t* tiles, int32_t n_tiles,
+// The field from n source cells (host arrays: cells, and their distinct
+// tiles) over g->plan_trav; synchronous.  stats: [4] or nullptr.
+static int dm_plan_run_field(dm_grid* g, const int64_t* cells, int32_t n, const int32_t* tiles, int32_t n_tiles,
                       uint32_t max_cost, uint64_t* stats) {
   using namespace dm_plan;
   const int64_t ncell = g->W * g->H;
@@ -313,7 +322,7 @@ int dm_plan_run_field(dm_grid* g, const int64_t* cells, int32_t n, const int32_t
   return DM_OK;
 }
 
-int dm_plan_launch_query(dm_grid* g, const double* d_xy, int64_t stride, int64_t n, int32_t snap_cells,
+static int dm_plan_launch_query(dm_grid* g, const double* d_xy, int64_t stride, int64_t n, int32_t snap_cells,
                          uint32_t* d_cost, int64_t* d_cell) {
   if (n <= 0) return DM_OK;
   KernelTimer t;
@@ -326,7 +335,9 @@ int dm_plan_launch_query(dm_grid* g, const double* d_xy, int64_t stride, int64_t
   return DM_OK;
 }
 
-int dm_plan_launch_path(dm_grid* g, const int64_t* d_start, int64_t cap) {
+// walk back from *d_start into g->plan_path (cap entries); length and error
+// word go to g->plan_stat[4], [5]
+static int dm_plan_launch_path(dm_grid* g, const int64_t* d_start, int64_t cap) {
   KernelTimer t;
   dm_timer_begin(g, "plan_path", &t);
   hipLaunchKernelGGL(dm_plan::k_plan_path, dim3(1), dim3(64), 0, g->stream, g->plan_cost, g->plan_travs, g->W,
@@ -336,178 +347,10 @@ int dm_plan_launch_path(dm_grid* g, const int64_t* d_start, int64_t cap) {
   return DM_OK;
 }
 
-// ---- scan matcher (dm_match.h) ------------------------------------------------
-
-int dm_match_launch_field(dm_grid* g, int32_t n_tiles, int32_t r, bool mono) {
-  if (n_tiles <= 0) return DM_OK;
-  KernelTimer t;
-  dm_timer_begin(g, "match_field", &t);
-  hipLaunchKernelGGL(dm_match::k_match_field, dim3((unsigned)n_tiles), dim3(dm_match::kThreads), 0, g->stream,
-                     g->state, g->tile_seen, g->W, g->H, g->TX, r, g->match_kern, mono ? 1 : 0, g->match_tiles,
-                     g->match_V);
-  DM_HIP(hipGetLastError());
-  dm_timer_end(g, &t);
-  return DM_OK;
-}
-
-int dm_match_launch_scans(dm_grid* g, int32_t S, int32_t N, int32_t A, int32_t k0, int32_t sub, int32_t half,
-                          int32_t stride) {
-  using namespace dm_match;
-  hipStream_t s = g->stream;
-  const int64_t SA = (int64_t)S * A, T = (int64_t)(2 * half + 1) * (2 * half + 1);
-  int32_t* d_used = g->match_out + 4 * (int64_t)S;
-  DM_HIP(hipMemsetAsync(d_used, 0, sizeof(int32_t) * (size_t)S, s));
-  DM_HIP(hipMemsetAsync(g->match_vol, 0, sizeof(uint32_t) * (size_t)(SA * T), s));
-  KernelTimer t;
-  if (N > 0) {
-    MatchArgs a;
-    a.N = N;
-    a.ox = g->p.origin_x;
-    a.oy = g->p.origin_y;
-    a.step = g->p.resolution / (double)sub;
-    a.range_min = g->p.range_min;
-    a.range_max = g->p.range_max;
-    dm_timer_begin(g, "match_prep", &t);
-    hipLaunchKernelGGL(k_match_prep, dim3((unsigned)SA, (unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                       s, a, g->match_pose4, g->match_ranges, g->match_trig, A, k0, g->match_q, d_used);
-    DM_HIP(hipGetLastError());
-    dm_timer_end(g, &t);
-    // beam chunks: at least what one workgroup's LDS stage holds; more (down
-    // to 32 beams each) while the candidate yaws alone leave the chip idle
-    const int64_t want = (2048 + SA - 1) / SA;
-    int64_t chunks = std::max<int64_t>((N + kBeamsPerChunk - 1) / kBeamsPerChunk,
-                                       std::min<int64_t>(want, (N + 31) / 32));
-    const int32_t chunk_len = (int32_t)((N + chunks - 1) / chunks);
-    chunks = (N + chunk_len - 1) / chunk_len;
-    dm_timer_begin(g, "match_score", &t);
-    hipLaunchKernelGGL(k_match_score, dim3((unsigned)SA, (unsigned)chunks), dim3(kThreads), 0, s, g->match_q, N,
-                       chunk_len, g->match_V, g->W, g->H, sub, half, stride, g->match_vol);
-    DM_HIP(hipGetLastError());
-    dm_timer_end(g, &t);
-  }
-  dm_timer_begin(g, "match_best", &t);
-  hipLaunchKernelGGL(k_match_best, dim3((unsigned)S), dim3(kThreads), 0, s, g->match_vol, A, half, k0, g->match_out);
-  DM_HIP(hipGetLastError());
-  dm_timer_end(g, &t);
-  return DM_OK;
-}
-
-// ---- whole-window relocalisation (dm_match_global.h) ---------------------------
-
-int dm_mg_launch_pool(dm_grid* g, int32_t n_tiles, int32_t lb, int32_t EWB, int32_t EHB, int32_t PTX) {
-  if (n_tiles <= 0) return DM_OK;
-  KernelTimer t;
-  dm_timer_begin(g, "mg_pool", &t);
-  hipLaunchKernelGGL(dm_mg::k_mg_pool, dim3((unsigned)n_tiles), dim3(dm_mg::kThreads), 0, g->stream, g->match_V, g->W,
-                     g->H, lb, EWB, EHB, PTX, g->mg_ptiles, g->mg_pool);
-  DM_HIP(hipGetLastError());
-  dm_timer_end(g, &t);
-  return DM_OK;
-}
-
-int dm_mg_run_scan(dm_grid* g, const MgShape& sh, const double* d_pose4, const float* d_ranges, int32_t* res,
-                   uint64_t* stats) {
-  using namespace dm_mg;
-  hipStream_t s = g->stream;
-  Cand* best = (Cand*)g->mg_best;
-  Cand* cand = (Cand*)g->mg_cand;
-  const int32_t N = sh.N, A = sh.A, nb = sh.nbx * sh.nby;
-  const int64_t blocks = (int64_t)A * nb;
-  KernelTimer t;
-  hipLaunchKernelGGL(k_mg_init, dim3(1), dim3(64), 0, s, best, sh.k0, g->mg_nused);
-  DM_HIP(hipGetLastError());
-  {
-    MatchArgs a;
-    a.N = N;
-    a.ox = g->p.origin_x;
-    a.oy = g->p.origin_y;
-    a.step = g->p.resolution;  // sub = 1
-    a.range_min = g->p.range_min;
-    a.range_max = g->p.range_max;
-    dm_timer_begin(g, "match_prep", &t);
-    hipLaunchKernelGGL(dm_match::k_match_prep, dim3((unsigned)A, (unsigned)((N + kThreads - 1) / kThreads)),
-                       dim3(dm_match::kThreads), 0, s, a, d_pose4, d_ranges, g->match_trig, A, sh.k0, g->match_q,
-                       g->mg_nused);
-    DM_HIP(hipGetLastError());
-    dm_timer_end(g, &t);
-  }
-  uint64_t refined = 0, rounds = 0;
-  if (sh.exhaustive) {
-    for (int64_t base = 0; base < blocks; base += dm_grid::kMgExhaustiveBatch) {
-      const int32_t n = (int32_t)std::min<int64_t>(dm_grid::kMgExhaustiveBatch, blocks - base);
-      dm_timer_begin(g, "mg_refine", &t);
-      hipLaunchKernelGGL(k_mg_refine, dim3((unsigned)n), dim3(kThreads), 0, s, g->match_q, N, g->match_V, g->W, g->H,
-                         sh.lb, sh.half_x, sh.half_y, sh.nbx, nb, sh.k0, (const int32_t*)nullptr, (int32_t)base,
-                         (const uint32_t*)nullptr, n, cand);
-      DM_HIP(hipGetLastError());
-      dm_timer_end(g, &t);
-      dm_timer_begin(g, "mg_fold", &t);
-      hipLaunchKernelGGL(k_mg_fold, dim3(1), dim3(kThreads), 0, s, cand, (const uint32_t*)nullptr, n, sh.k0, best,
-                         g->mg_nused, g->h_mg_dev);
-      DM_HIP(hipGetLastError());
-      dm_timer_end(g, &t);
-      refined += (uint64_t)n;
-      ++rounds;
-    }
-    DM_HIP(hipStreamSynchronize(s));
-  } else {
-    dm_timer_begin(g, "mg_bound", &t);
-    hipLaunchKernelGGL(k_mg_bound, dim3((unsigned)((nb + kThreads - 1) / kThreads), (unsigned)A), dim3(kThreads), 0, s,
-                       g->match_q, N, g->mg_pool, sh.lb, sh.EWB, sh.EHB, sh.half_x, sh.half_y, sh.nbx, nb,
-                       g->mg_bound);
-    DM_HIP(hipGetLastError());
-    dm_timer_end(g, &t);
-    // rounds: the blocks whose bound reaches the best exact score so far (and
-    // 1), the highest bounds first; few in the first round, when nothing is
-    // known yet, then up to mg_batch
-    const uint32_t hi = 255u * (uint32_t)N;
-    const unsigned scan_grid = (unsigned)std::min<int64_t>((blocks + kThreads - 1) / kThreads, 2048);
-    uint32_t s_best = 0;
-    uint32_t cap = (uint32_t)std::min<int64_t>(g->mg_batch, 8);
-    for (;;) {
-      const uint32_t lo = std::max(s_best, 1u);
-      DM_HIP(hipMemsetAsync(g->mg_hist, 0, sizeof(uint32_t) * kBins, s));
-      dm_timer_begin(g, "mg_select", &t);
-      hipLaunchKernelGGL(k_mg_hist, dim3(scan_grid), dim3(kThreads), 0, s, g->mg_bound, blocks, lo, hi, g->mg_hist);
-      hipLaunchKernelGGL(k_mg_pick, dim3(1), dim3(kThreads), 0, s, g->mg_hist, cap, g->mg_ctl);
-      hipLaunchKernelGGL(k_mg_compact, dim3(scan_grid), dim3(kThreads), 0, s, g->mg_bound, blocks, lo, hi, g->mg_ctl,
-                         g->mg_list);
-      DM_HIP(hipGetLastError());
-      dm_timer_end(g, &t);
-      dm_timer_begin(g, "mg_refine", &t);
-      hipLaunchKernelGGL(k_mg_refine, dim3(cap), dim3(kThreads), 0, s, g->match_q, N, g->match_V, g->W, g->H, sh.lb,
-                         sh.half_x, sh.half_y, sh.nbx, nb, sh.k0, g->mg_list, 0, g->mg_ctl, 0, cand);
-      DM_HIP(hipGetLastError());
-      dm_timer_end(g, &t);
-      dm_timer_begin(g, "mg_fold", &t);
-      hipLaunchKernelGGL(k_mg_fold, dim3(1), dim3(kThreads), 0, s, cand, g->mg_ctl, 0, sh.k0, best, g->mg_nused,
-                         g->h_mg_dev);
-      DM_HIP(hipGetLastError());
-      dm_timer_end(g, &t);
-      DM_HIP(hipStreamSynchronize(s));
-      const uint32_t n = g->h_mg[4];
-      if (n == 0) break;  // no unrefined block can reach the best score: it is exact
-      refined += n;
-      ++rounds;
-      s_best = g->h_mg[0];
-      cap = (uint32_t)std::min<int64_t>(g->mg_batch, (int64_t)cap * 4);
-    }
-  }
-  res[0] = (int32_t)g->h_mg[1];
-  res[1] = (int32_t)g->h_mg[2];
-  res[2] = (int32_t)g->h_mg[3];
-  res[3] = (int32_t)g->h_mg[0];
-  res[4] = (int32_t)g->h_mg[5];
-  stats[0] = (uint64_t)blocks;
-  stats[1] = sh.exhaustive ? 0 : (uint64_t)blocks;
-  stats[2] = refined;
-  stats[3] = rounds;
-  return DM_OK;
-}
-
 // ---- information gain (dm_gain.h) ---------------------------------------------
 
-int dm_gain_launch_cells(dm_grid* g, int64_t n) {
+// cells of n view points in g->gain_xy into g->gain_cell
+static int dm_gain_launch_cells(dm_grid* g, int64_t n) {
   if (n <= 0) return DM_OK;
   hipLaunchKernelGGL(dm_gain::k_gain_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g->stream, g->gain_xy, n,
                      g->W, g->H, g->p.origin_x, g->p.origin_y, g->p.resolution, g->gain_cell);
@@ -515,7 +358,8 @@ int dm_gain_launch_cells(dm_grid* g, int64_t n) {
   return DM_OK;
 }
 
-int dm_gain_launch_skip(dm_grid* g, const dm_cluster* d_recs, const uint32_t* d_cost, int64_t K, int64_t min_size) {
+// skip flags of K clusters (size < min_size or d_cost unreachable) into g->gain_skip
+static int dm_gain_launch_skip(dm_grid* g, const dm_cluster* d_recs, const uint32_t* d_cost, int64_t K, int64_t min_size) {
   if (K <= 0) return DM_OK;
   hipLaunchKernelGGL(dm_gain::k_gain_skip, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, g->stream, d_recs, d_cost,
                      K, min_size, g->gain_skip);
@@ -542,7 +386,8 @@ void gain_launch(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64
 
 }  // namespace
 
-int dm_gain_launch_views(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R, bool memo) {
+// gains of n view cells into g->gain_out; d_skip and the memo (g->gain_memo_*) are optional
+static int dm_gain_launch_views(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R, bool memo) {
   if (n <= 0) return DM_OK;
   int64_t* const mc = memo ? g->gain_memo_cell : nullptr;
   uint32_t* const mg = memo ? g->gain_memo_gain : nullptr;
@@ -554,7 +399,9 @@ int dm_gain_launch_views(dm_grid* g, const int64_t* d_cell, const uint8_t* d_ski
   return DM_OK;
 }
 
-int dm_gain_launch_marginal(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R,
+// The overlap-aware forms, over the claimed set g->gain_claimed:
+// marginal gains of n view cells into g->gain_out, reading the claimed set only
+static int dm_gain_launch_marginal(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R,
                             bool memo) {
   if (n <= 0) return DM_OK;
   int64_t* const mc = memo ? g->gain_memo_cell : nullptr;
@@ -567,7 +414,8 @@ int dm_gain_launch_marginal(dm_grid* g, const int64_t* d_cell, const uint8_t* d_
   return DM_OK;
 }
 
-int dm_gain_launch_commit(dm_grid* g, const int64_t* d_cell, int64_t n, int32_t R) {
+// the n views' visible sets into the claimed set, in one launch; reports nothing
+static int dm_gain_launch_commit(dm_grid* g, const int64_t* d_cell, int64_t n, int32_t R) {
   if (n <= 0) return DM_OK;
   KernelTimer t;
   dm_timer_begin(g, "gain_commit", &t);
@@ -577,7 +425,8 @@ int dm_gain_launch_commit(dm_grid* g, const int64_t* d_cell, int64_t n, int32_t 
   return DM_OK;
 }
 
-int dm_gain_launch_joint(dm_grid* g, const int64_t* d_cell, int64_t n, int32_t R, uint32_t* d_out) {
+// view i's marginal gain into d_out[i], then its commit, for i = 0..n-1 in order (one launch each)
+static int dm_gain_launch_joint(dm_grid* g, const int64_t* d_cell, int64_t n, int32_t R, uint32_t* d_out) {
   if (n <= 0) return DM_OK;
   KernelTimer t;
   dm_timer_begin(g, "gain_joint", &t);
@@ -590,10 +439,548 @@ int dm_gain_launch_joint(dm_grid* g, const int64_t* d_cell, int64_t n, int32_t R
   return DM_OK;
 }
 
-int dm_gain_launch_expand(dm_grid* g, uint8_t* d_out) {
+// the claimed set as H * W bytes
+static int dm_gain_launch_expand(dm_grid* g, uint8_t* d_out) {
   const int64_t cells = g->W * g->H;
   hipLaunchKernelGGL(dm_gain::k_gain_expand, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, g->stream,
                      g->gain_claimed, (int32_t)g->W, (int32_t)g->H, d_out);
   DM_HIP(hipGetLastError());
   return DM_OK;
 }
+
+extern "C" {
+
+// ---- path planning (csrc/dm_plan.h): traversability, distance field, snapped
+// queries, paths, path-length goals ---------------------------------------------
+
+static int ensure_plan(dm_grid* g) {
+  if (g->plan_cost) return DM_OK;  // allocated last: everything else is there too
+  int rc = DM_OK;
+  if (!g->h_plan) {
+    hipError_t e = hipHostMalloc((void**)&g->h_plan, sizeof(unsigned long long) * 16,
+                                 hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess) {
+      g->h_plan = nullptr;
+      return dm_hip_check(e, "hipHostMalloc(plan rounds)");
+    }
+    memset(g->h_plan, 0, sizeof(unsigned long long) * 16);
+    DM_HIP(hipHostGetDevicePointer((void**)&g->h_plan_dev, g->h_plan, 0));
+  }
+  const int64_t rows = g->NT * DM_TILE;
+  if ((rc = dev_alloc(&g->plan_trav, rows, "traversable bit rows"))) return rc;
+  if ((rc = dev_alloc(&g->plan_travs, rows, "traversable bit rows with sources"))) return rc;
+  if ((rc = dev_alloc(&g->plan_list[0], g->NT, "plan tile list"))) return rc;
+  if ((rc = dev_alloc(&g->plan_list[1], g->NT, "plan tile list"))) return rc;
+  if ((rc = dev_alloc(&g->plan_stamp, g->NT, "plan tile stamps"))) return rc;
+  if ((rc = dev_alloc(&g->plan_len, 4, "plan list lengths"))) return rc;
+  if ((rc = dev_alloc(&g->plan_stat, 8, "plan statistics"))) return rc;
+  DM_HIP(hipMemset(g->plan_stat, 0, sizeof(unsigned long long) * 8));
+  if ((rc = dev_alloc(&g->plan_src, 256, "plan sources"))) return rc;
+  return dev_alloc(&g->plan_cost, g->W * g->H, "distance field");
+}
+
+static int grow_plan_query(dm_grid* g, int64_t n) {
+  if (n <= g->plan_qcap) return DM_OK;
+  g->plan_qcap = 0;
+  int rc = dev_alloc(&g->plan_qxy, 2 * n, "plan query targets");
+  if (!rc) rc = dev_alloc(&g->plan_qcost, n, "plan query costs");
+  if (!rc) rc = dev_alloc(&g->plan_qcell, n, "plan query cells");
+  if (!rc) g->plan_qcap = n;
+  return rc;
+}
+
+// SPEC a4's cell of a point: floor((x - origin) / resolution) per axis
+static bool plan_cell_of(const dm_grid* g, double x, double y, int64_t* cell) {
+  const double fx = floor((x - g->p.origin_x) / g->p.resolution);
+  const double fy = floor((y - g->p.origin_y) / g->p.resolution);
+  if (!(fx >= 0.0 && fx < (double)g->W && fy >= 0.0 && fy < (double)g->H)) return false;  // NaN too
+  *cell = (int64_t)fy * g->W + (int64_t)fx;
+  return true;
+}
+
+static int plan_need_field(const dm_grid* g, const char* what) {
+  if (!g->plan_cost || !g->plan_valid)
+    return dm_set_error(DM_ERR_STATE, "%s: no distance field (call dm_plan_field first)", what);
+  if (g->plan_version != dm_map_version(g))
+    return dm_set_error(DM_ERR_STATE, "%s: the map changed since the distance field was computed (call "
+                        "dm_plan_field again)", what);
+  return DM_OK;
+}
+
+// The field from n sources (metres) over g->plan_trav, which the caller computed.
+static int plan_field_from(dm_grid* g, const double* sources_xy, int32_t n, uint32_t max_cost, uint64_t* stats) {
+  std::vector<int64_t> cells((size_t)n);
+  std::vector<int32_t> tiles;
+  for (int32_t i = 0; i < n; ++i) {
+    if (!plan_cell_of(g, sources_xy[2 * i], sources_xy[2 * i + 1], &cells[(size_t)i]))
+      return dm_set_error(DM_ERR_INVALID_ARG, "source %d (%g, %g) is outside the grid", i, sources_xy[2 * i],
+                          sources_xy[2 * i + 1]);
+    const int64_t x = cells[(size_t)i] % g->W, y = cells[(size_t)i] / g->W;
+    const int32_t t = (int32_t)((y / DM_TILE) * g->TX + x / DM_TILE);
+    if (std::find(tiles.begin(), tiles.end(), t) == tiles.end()) tiles.push_back(t);
+  }
+  if (max_cost == 0u || max_cost > 0xFFFFFFEFu) max_cost = 0xFFFFFFEFu;
+  g->plan_valid = false;
+  int rc = dm_plan_run_field(g, cells.data(), n, tiles.data(), (int32_t)tiles.size(), max_cost, stats);
+  if (rc) return rc;
+  g->plan_valid = true;
+  g->plan_version = dm_map_version(g);
+  return DM_OK;
+}
+
+static int plan_check_inflate(int32_t inflate_cells) {
+  if (inflate_cells < 0 || inflate_cells > 32)
+    return dm_set_error(DM_ERR_INVALID_ARG, "inflate_cells must be in [0, 32] (got %d)", inflate_cells);
+  return DM_OK;
+}
+
+static int plan_check_snap(int32_t snap_cells) {
+  if (snap_cells < 0 || snap_cells > 16)
+    return dm_set_error(DM_ERR_INVALID_ARG, "snap_cells must be in [0, 16] (got %d)", snap_cells);
+  return DM_OK;
+}
+
+int dm_plan_traversable(dm_grid* g, int32_t inflate_cells, uint8_t* out) {
+  int rc = dm_check_whole_map(g, "dm_plan_traversable");
+  if (rc || (rc = use_device(g))) return rc;
+  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
+  if ((rc = plan_check_inflate(inflate_cells)) || (rc = ensure_plan(g))) return rc;
+  DM_HIP(dm_join_pass_stream(g));
+  const int64_t cells = g->W * g->H;
+  uint8_t* d = nullptr;
+  if ((rc = dev_alloc(&d, cells, "traversable image"))) return rc;
+  rc = dm_plan_launch_travers(g, inflate_cells);
+  if (!rc) rc = dm_plan_launch_expand(g, d);
+  hipError_t e = hipSuccess;
+  if (!rc) e = hipMemcpyAsync(out, d, (size_t)cells, hipMemcpyDeviceToHost, g->stream);
+  if (!rc && e == hipSuccess) e = hipStreamSynchronize(g->stream);
+  (void)hipFree(d);
+  if (e != hipSuccess) return dm_hip_check(e, "dm_plan_traversable");
+  return rc;
+}
+
+int dm_plan_field(dm_grid* g, const double* sources_xy, int32_t n_sources, int32_t inflate_cells,
+                  uint32_t max_cost, uint64_t* out_stats) {
+  int rc = dm_check_whole_map(g, "dm_plan_field");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n_sources < 1 || n_sources > 256)
+    return dm_set_error(DM_ERR_INVALID_ARG, "n_sources must be in [1, 256] (got %d)", n_sources);
+  if (!sources_xy) return dm_set_error(DM_ERR_INVALID_ARG, "sources_xy is NULL");
+  if ((rc = plan_check_inflate(inflate_cells)) || (rc = ensure_plan(g))) return rc;
+  DM_HIP(dm_join_pass_stream(g));
+  if ((rc = dm_plan_launch_travers(g, inflate_cells))) return rc;
+  return plan_field_from(g, sources_xy, n_sources, max_cost, out_stats);
+}
+
+int dm_plan_get_field(dm_grid* g, uint32_t* out) {
+  int rc = dm_check_whole_map(g, "dm_plan_get_field");
+  if (rc || (rc = use_device(g))) return rc;
+  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
+  if ((rc = plan_need_field(g, "dm_plan_get_field"))) return rc;
+  DM_HIP(hipMemcpyAsync(out, g->plan_cost, sizeof(uint32_t) * (size_t)(g->W * g->H), hipMemcpyDeviceToHost,
+                        g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  return DM_OK;
+}
+
+int dm_plan_query(dm_grid* g, const double* targets_xy, int64_t n, int32_t snap_cells, uint32_t* out_cost,
+                  int64_t* out_cell) {
+  int rc = dm_check_whole_map(g, "dm_plan_query");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n < 0) return dm_set_error(DM_ERR_INVALID_ARG, "n must be >= 0");
+  if (n > 0 && (!targets_xy || !out_cost || !out_cell))
+    return dm_set_error(DM_ERR_INVALID_ARG, "targets_xy / out_cost / out_cell is NULL");
+  if ((rc = plan_check_snap(snap_cells)) || (rc = plan_need_field(g, "dm_plan_query"))) return rc;
+  if (n == 0) return DM_OK;
+  if ((rc = grow_plan_query(g, n))) return rc;
+  DM_HIP(hipMemcpyAsync(g->plan_qxy, targets_xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, g->stream));
+  if ((rc = dm_plan_launch_query(g, g->plan_qxy, 2, n, snap_cells, g->plan_qcost, g->plan_qcell))) return rc;
+  DM_HIP(hipMemcpyAsync(out_cost, g->plan_qcost, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipMemcpyAsync(out_cell, g->plan_qcell, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  return DM_OK;
+}
+
+int dm_plan_path(dm_grid* g, double tx, double ty, int32_t snap_cells, int64_t* out_cells, int64_t cap,
+                 int64_t* n_out) {
+  int rc = dm_check_whole_map(g, "dm_plan_path");
+  if (rc || (rc = use_device(g))) return rc;
+  if (!n_out) return dm_set_error(DM_ERR_INVALID_ARG, "n_out is NULL");
+  *n_out = 0;
+  if (cap < 0 || (cap > 0 && !out_cells)) return dm_set_error(DM_ERR_INVALID_ARG, "cap < 0 or out_cells is NULL");
+  if ((rc = plan_check_snap(snap_cells)) || (rc = plan_need_field(g, "dm_plan_path"))) return rc;
+  if ((rc = grow_plan_query(g, 1))) return rc;
+  // a path visits no cell twice: H * W entries hold any
+  const int64_t dcap = std::max<int64_t>(1, std::min<int64_t>(cap, g->W * g->H));
+  if (dcap > g->plan_pathcap) {
+    g->plan_pathcap = 0;
+    if ((rc = dev_alloc(&g->plan_path, dcap, "path cells"))) return rc;
+    g->plan_pathcap = dcap;
+  }
+  const double txy[2] = {tx, ty};
+  DM_HIP(hipMemcpyAsync(g->plan_qxy, txy, sizeof txy, hipMemcpyHostToDevice, g->stream));
+  if ((rc = dm_plan_launch_query(g, g->plan_qxy, 2, 1, snap_cells, g->plan_qcost, g->plan_qcell))) return rc;
+  if ((rc = dm_plan_launch_path(g, g->plan_qcell, std::min(cap, dcap)))) return rc;
+  unsigned long long st[2] = {0ull, 0ull};
+  DM_HIP(hipMemcpyAsync(st, g->plan_stat + 4, sizeof st, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  if (st[1])
+    return dm_set_error(DM_ERR_INCOMPLETE, "dm_plan_path: the walk found no predecessor after %llu cells (the "
+                        "field is not a fixpoint)", st[0]);
+  const int64_t n = (int64_t)st[0];
+  *n_out = n;
+  if (n > cap)
+    return dm_set_error(DM_ERR_CAPACITY, "the path has %lld cells, cap is %lld", (long long)n, (long long)cap);
+  if (n > 0) {
+    std::vector<int64_t> rev((size_t)n);
+    DM_HIP(hipMemcpy(rev.data(), g->plan_path, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) out_cells[i] = rev[(size_t)(n - 1 - i)];  // source first
+  }
+  return DM_OK;
+}
+
+// ---- information gain (csrc/dm_gain.h): visible-unknown counts of view
+// points, gain-scored goals ---------------------------------------------------------
+
+static int grow_gain(dm_grid* g, int64_t n) {
+  if (n <= g->gain_cap) return DM_OK;
+  g->gain_cap = 0;
+  int rc = dev_alloc(&g->gain_xy, 2 * n, "view points");
+  if (!rc) rc = dev_alloc(&g->gain_cell, n, "view cells");
+  if (!rc) rc = dev_alloc(&g->gain_out, n, "view gains");
+  if (!rc) rc = dev_alloc(&g->gain_skip, n, "view skip flags");
+  if (!rc) rc = dev_alloc(&g->gain_memo_cell, n, "gain memo cells");
+  if (!rc) rc = dev_alloc(&g->gain_memo_gain, n, "gain memo gains");
+  if (!rc) g->gain_cap = n;
+  return rc;
+}
+
+static int gain_check_radius(int32_t radius_cells) {
+  if (radius_cells < 1 || radius_cells > 511)
+    return dm_set_error(DM_ERR_INVALID_ARG, "radius_cells must be in [1, 511] (got %d)", radius_cells);
+  return DM_OK;
+}
+
+int dm_gain_views(dm_grid* g, const double* views_xy, int64_t n, int32_t radius_cells, uint32_t* out_gain,
+                  int64_t* out_cell) {
+  int rc = dm_check_whole_map(g, "dm_gain_views");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n < 0 || n > (1ll << 20))
+    return dm_set_error(DM_ERR_INVALID_ARG, "n must be in [0, 2^20] (got %lld)", (long long)n);
+  if (n > 0 && (!views_xy || !out_gain || !out_cell))
+    return dm_set_error(DM_ERR_INVALID_ARG, "views_xy / out_gain / out_cell is NULL");
+  if ((rc = gain_check_radius(radius_cells))) return rc;
+  if (n == 0) return DM_OK;
+  if ((rc = grow_gain(g, n))) return rc;
+  DM_HIP(dm_sync_all(g));  // after everything enqueued on the handle, on every stream of it
+  DM_HIP(hipMemcpyAsync(g->gain_xy, views_xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, g->stream));
+  if ((rc = dm_gain_launch_cells(g, n))) return rc;
+  if ((rc = dm_gain_launch_views(g, g->gain_cell, nullptr, n, radius_cells, false))) return rc;
+  DM_HIP(hipMemcpyAsync(out_gain, g->gain_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipMemcpyAsync(out_cell, g->gain_cell, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  return DM_OK;
+}
+
+// The claimed set of the overlap-aware calls: allocated by the first of them.
+static int64_t claimed_words(const dm_grid* g) { return g->H * ((g->W + 31) / 32); }
+
+static int ensure_claimed(dm_grid* g) {
+  if (g->gain_claimed) return DM_OK;
+  return dev_alloc(&g->gain_claimed, claimed_words(g), "claimed set");
+}
+
+// n points (metres) to g->gain_xy and their cells to g->gain_cell.
+static int gain_upload_views(dm_grid* g, const double* xy, int64_t n) {
+  if (n <= 0) return DM_OK;
+  DM_HIP(hipMemcpyAsync(g->gain_xy, xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, g->stream));
+  return dm_gain_launch_cells(g, n);
+}
+
+int dm_gain_views_joint(dm_grid* g, const double* views_xy, int64_t n, int32_t radius_cells, uint32_t* out_marginal,
+                        int64_t* out_cell) {
+  int rc = dm_check_whole_map(g, "dm_gain_views_joint");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n < 0 || n > 1024) return dm_set_error(DM_ERR_INVALID_ARG, "n must be in [0, 1024] (got %lld)", (long long)n);
+  if (n > 0 && (!views_xy || !out_marginal || !out_cell))
+    return dm_set_error(DM_ERR_INVALID_ARG, "views_xy / out_marginal / out_cell is NULL");
+  if ((rc = gain_check_radius(radius_cells))) return rc;
+  if ((rc = ensure_claimed(g)) || (rc = grow_gain(g, std::max<int64_t>(n, 1)))) return rc;
+  DM_HIP(dm_sync_all(g));  // after everything enqueued on the handle, on every stream of it
+  g->gain_claimed_valid = false;
+  DM_HIP(hipMemsetAsync(g->gain_claimed, 0, sizeof(uint32_t) * (size_t)claimed_words(g), g->stream));
+  if ((rc = gain_upload_views(g, views_xy, n))) return rc;
+  if ((rc = dm_gain_launch_joint(g, g->gain_cell, n, radius_cells, g->gain_out))) return rc;
+  if (n > 0) {
+    DM_HIP(hipMemcpyAsync(out_marginal, g->gain_out, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+    DM_HIP(hipMemcpyAsync(out_cell, g->gain_cell, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  }
+  DM_HIP(hipStreamSynchronize(g->stream));
+  g->gain_claimed_valid = true;
+  return DM_OK;
+}
+
+int dm_gain_claimed(dm_grid* g, uint8_t* out) {
+  int rc = dm_check_whole_map(g, "dm_gain_claimed");
+  if (rc || (rc = use_device(g))) return rc;
+  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
+  if (!g->gain_claimed || !g->gain_claimed_valid)
+    return dm_set_error(DM_ERR_STATE, "dm_gain_claimed: no claimed set (call dm_gain_views_joint or "
+                        "dm_assign_goals_coord first)");
+  const int64_t cells = g->W * g->H;
+  uint8_t* d = nullptr;
+  if ((rc = dev_alloc(&d, cells, "claimed image"))) return rc;
+  rc = dm_gain_launch_expand(g, d);
+  hipError_t e = hipSuccess;
+  if (!rc) e = hipMemcpyAsync(out, d, (size_t)cells, hipMemcpyDeviceToHost, g->stream);
+  if (!rc && e == hipSuccess) e = hipStreamSynchronize(g->stream);
+  (void)hipFree(d);
+  if (e != hipSuccess) return dm_hip_check(e, "dm_gain_claimed");
+  return rc;
+}
+
+// ---- goal assignment: dm_assign_goals (Euclidean distance to the centroid)
+// and the three calls that score by a robot's own distance field --------------
+
+// What every goal call checks first, in this order; `null_names`: the
+// buffers of the call, for the message, and whether one of them is NULL.
+static int check_goal_args(int32_t n_robots, bool any_null, const char* null_names, double distance_weight,
+                           double min_distance) {
+  if (n_robots < 0 || n_robots > 256)
+    return dm_set_error(DM_ERR_INVALID_ARG, "n_robots must be in [0, 256] (got %d)", n_robots);
+  if (n_robots > 0 && any_null) return dm_set_error(DM_ERR_INVALID_ARG, "%s is NULL", null_names);
+  if (!isfinite(distance_weight) || !isfinite(min_distance))
+    return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight / min_distance must be finite");
+  // the device ranks by the util's IEEE bits, an order that holds for util > 0
+  // only: w >= 0 keeps util = numerator / (1 + w*dist) positive and finite
+  if (distance_weight < 0.0)
+    return dm_set_error(DM_ERR_INVALID_ARG, "distance_weight must be >= 0");
+  return DM_OK;
+}
+
+// The label-sorted device records of the last collected frontier result
+// (dm_api.cpp: note_goal_source), if its readback slot still holds them.
+static int goal_source(const dm_grid* g, const dm_cluster** recs, int64_t* K) {
+  const int s = g->goal_slot;
+  if (s < 0 || g->goal_gen != g->rb_gen ||
+      (g->goal_kind == 1 ? g->rb[s].wepoch : g->rb[s].mepoch) != g->goal_epoch)
+    return dm_set_error(DM_ERR_INVALID_ARG, "no collected frontier result on the device (call dm_frontiers, "
+                                            "dm_frontiers_end or dm_merge_bands first; a later pass may have "
+                                            "reused its readback slot)");
+  *recs = g->goal_kind == 1 ? g->rb[s].out_clu : g->rb[s].m_out;
+  *K = g->goal_n;
+  return DM_OK;
+}
+
+// Robot r's turn of the greedy assignment: the first cluster of its best-first
+// list (T keys and indices; key 0: no eligible cluster left) that none of the
+// robots before it took, or -1.  Its choice is within the first r + 1 entries:
+// r clusters are taken before its turn.
+static int64_t greedy_pick(const unsigned long long* hk, const uint32_t* hi, int32_t T,
+                           const std::vector<int64_t>& idx, int32_t r) {
+  for (int32_t t = 0; t < T; ++t) {
+    if (hk[t] == 0ull) break;
+    const int64_t c = hi[t];
+    if (std::find(idx.begin(), idx.begin() + r, c) == idx.begin() + r) return c;
+  }
+  return -1;
+}
+
+// The centre of a cell (linear index) in metres.
+static void cell_centre(const dm_grid* g, int64_t cell, double* xy) {
+  xy[0] = g->p.origin_x + ((double)(cell % g->W) + 0.5) * g->p.resolution;
+  xy[1] = g->p.origin_y + ((double)(cell / g->W) + 0.5) * g->p.resolution;
+}
+
+int dm_assign_goals(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size,
+                    double distance_weight, double min_distance, int64_t* out_index, double* out_xy) {
+  if (g && g->sh) return dm_sh_assign_goals(g, robots_xy, n_robots, min_size, distance_weight, min_distance, out_index, out_xy);
+  int rc = check_grid(g);
+  if (rc || (rc = use_device(g))) return rc;
+  if ((rc = check_goal_args(n_robots, !robots_xy || !out_index || !out_xy, "robots_xy / out_index / out_xy",
+                            distance_weight, min_distance)))
+    return rc;
+  const dm_cluster* recs = nullptr;
+  int64_t K = 0;
+  if ((rc = goal_source(g, &recs, &K))) return rc;
+  if (n_robots == 0) return DM_OK;
+  if (!g->goal_io) {
+    DM_HIP(hipMalloc((void**)&g->goal_io, sizeof(double) * 4 * 256));
+    DM_HIP(hipMalloc((void**)&g->goal_idx, sizeof(int64_t) * 256));
+  }
+  DM_HIP(dm_join_pass_stream(g));
+  const int32_t R = n_robots, T = n_robots;
+  DM_HIP(hipMemcpyAsync(g->goal_io, robots_xy, sizeof(double) * 2 * (size_t)R, hipMemcpyHostToDevice,
+                        g->stream));
+  std::vector<int64_t> idx((size_t)R, -1);
+  if (K > 0) {
+    const unsigned long long* dk = nullptr;
+    const uint32_t* di = nullptr;
+    if ((rc = dm_launch_goal_topk(g, recs, K, g->goal_io, R, T, min_size, distance_weight, min_distance, &dk,
+                                  &di)))
+      return rc;
+    std::vector<unsigned long long> hk((size_t)R * T);
+    std::vector<uint32_t> hi((size_t)R * T);
+    DM_HIP(hipMemcpyAsync(hk.data(), dk, sizeof(unsigned long long) * hk.size(), hipMemcpyDeviceToHost,
+                          g->stream));
+    DM_HIP(hipMemcpyAsync(hi.data(), di, sizeof(uint32_t) * hi.size(), hipMemcpyDeviceToHost, g->stream));
+    DM_HIP(hipStreamSynchronize(g->stream));
+    for (int32_t r = 0; r < R; ++r) idx[(size_t)r] = greedy_pick(&hk[(size_t)r * T], &hi[(size_t)r * T], T, idx, r);
+  }
+  DM_HIP(hipMemcpyAsync(g->goal_idx, idx.data(), sizeof(int64_t) * (size_t)R, hipMemcpyHostToDevice,
+                        g->stream));
+  if ((rc = dm_launch_goal_gather(g, recs, g->goal_idx, R, g->goal_io + 2 * 256))) return rc;
+  DM_HIP(hipMemcpyAsync(out_xy, g->goal_io + 2 * 256, sizeof(double) * 2 * (size_t)R, hipMemcpyDeviceToHost,
+                        g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  memcpy(out_index, idx.data(), sizeof(int64_t) * (size_t)R);
+  return DM_OK;
+}
+
+// How a field-scored goal call scores a cluster: util = numerator / (1 + w *
+// dist), dist the path length from the robot to the cluster's snapped centroid.
+struct GoalScoring {
+  const char* what;  // the entry point, for messages
+  // the numerator: the cluster's size (dm_assign_goals_path), the
+  // visible-unknown count of its snapped cell (dm_assign_goals_gain), or what
+  // that cell sees outside the claimed set (dm_assign_goals_coord), which
+  // starts as the held views and takes every goal's view as it is assigned
+  enum { kSize, kGain, kMarginal } numerator;
+  int64_t min_gain;        // the rest is not read with kSize
+  int32_t radius_cells;
+  const double* held_xy;   // kMarginal only
+  int32_t n_held;
+};
+
+// out_gain: nullptr with kSize.  The field left in the handle is the last robot's.
+static int assign_goals_field(dm_grid* g, const GoalScoring& sc, const double* robots_xy, int32_t n_robots,
+                              int64_t min_size, double distance_weight, double min_distance, int32_t inflate_cells,
+                              uint32_t max_cost, int32_t snap_cells, int64_t* out_index, double* out_xy,
+                              int64_t* out_cell, uint32_t* out_gain) {
+  const bool gain = sc.numerator != GoalScoring::kSize, coord = sc.numerator == GoalScoring::kMarginal;
+  int rc = dm_check_whole_map(g, sc.what);
+  if (rc || (rc = use_device(g))) return rc;
+  if ((rc = check_goal_args(n_robots, !robots_xy || !out_index || !out_xy || !out_cell || (gain && !out_gain),
+                            gain ? "robots_xy / out_index / out_xy / out_cell / out_gain"
+                                 : "robots_xy / out_index / out_xy / out_cell",
+                            distance_weight, min_distance)))
+    return rc;
+  if (gain) {
+    if (sc.min_gain < 0)
+      return dm_set_error(DM_ERR_INVALID_ARG, "min_gain must be >= 0 (got %lld)", (long long)sc.min_gain);
+    if (sc.n_held < 0 || sc.n_held > 1024)
+      return dm_set_error(DM_ERR_INVALID_ARG, "n_held must be in [0, 1024] (got %d)", sc.n_held);
+    if (sc.n_held > 0 && !sc.held_xy) return dm_set_error(DM_ERR_INVALID_ARG, "held_xy is NULL");
+  }
+  if ((rc = plan_check_inflate(inflate_cells)) || (rc = plan_check_snap(snap_cells)) ||
+      (gain && (rc = gain_check_radius(sc.radius_cells))))
+    return rc;
+  const dm_cluster* recs = nullptr;
+  int64_t K = 0;
+  if ((rc = goal_source(g, &recs, &K))) return rc;
+  if (n_robots == 0 && !coord) return DM_OK;
+  for (int32_t r = 0; r < n_robots; ++r) {
+    int64_t c;
+    if (!plan_cell_of(g, robots_xy[2 * r], robots_xy[2 * r + 1], &c))
+      return dm_set_error(DM_ERR_INVALID_ARG, "robot %d (%g, %g) is outside the grid", r, robots_xy[2 * r],
+                          robots_xy[2 * r + 1]);
+  }
+  if ((rc = ensure_plan(g)) || (rc = grow_plan_query(g, std::max<int64_t>(K, 1)))) return rc;
+  if (gain && (rc = grow_gain(g, std::max<int64_t>(std::max<int64_t>(K, sc.n_held), 1)))) return rc;
+  if (coord && (rc = ensure_claimed(g))) return rc;
+  DM_HIP(dm_join_pass_stream(g));
+  if (coord) {
+    // C: empty, then the held views, all in one launch (ORs commute)
+    g->gain_claimed_valid = false;
+    DM_HIP(hipMemsetAsync(g->gain_claimed, 0, sizeof(uint32_t) * (size_t)claimed_words(g), g->stream));
+    if ((rc = gain_upload_views(g, sc.held_xy, sc.n_held))) return rc;
+    if ((rc = dm_gain_launch_commit(g, g->gain_cell, sc.n_held, sc.radius_cells))) return rc;
+    if (n_robots == 0) {
+      DM_HIP(hipStreamSynchronize(g->stream));
+      g->gain_claimed_valid = true;
+      return DM_OK;
+    }
+  }
+  if ((rc = dm_plan_launch_travers(g, inflate_cells))) return rc;
+  // the memo of this call: no cluster has a cast yet (every byte 0xFF: cell -1,
+  // which no cast view has)
+  if (gain && K > 0) DM_HIP(hipMemsetAsync(g->gain_memo_cell, 0xFF, sizeof(int64_t) * (size_t)K, g->stream));
+  const int32_t R = n_robots, T = n_robots;
+  std::vector<int64_t> idx((size_t)R, -1);
+  std::vector<unsigned long long> hk((size_t)T);
+  std::vector<uint32_t> hi((size_t)T);
+  for (int32_t r = 0; r < R; ++r) {
+    // robot r's field, its path cost to every cluster's snapped centroid, then
+    // (gain) the numerator of every snapped cell that can still be a goal
+    if ((rc = plan_field_from(g, robots_xy + 2 * r, 1, max_cost, nullptr))) return rc;
+    out_cell[r] = -1;
+    if (gain) out_gain[r] = 0u;
+    out_xy[2 * r] = out_xy[2 * r + 1] = NAN;
+    if (K == 0) continue;
+    if ((rc = dm_plan_launch_query(g, &recs[0].cx_m, (int64_t)(sizeof(dm_cluster) / sizeof(double)), K, snap_cells,
+                                   g->plan_qcost, g->plan_qcell)))
+      return rc;
+    if (gain) {
+      if ((rc = dm_gain_launch_skip(g, recs, g->plan_qcost, K, min_size))) return rc;
+      if ((rc = coord ? dm_gain_launch_marginal(g, g->plan_qcell, g->gain_skip, K, sc.radius_cells, true)
+                      : dm_gain_launch_views(g, g->plan_qcell, g->gain_skip, K, sc.radius_cells, true)))
+        return rc;
+    }
+    const unsigned long long* dk = nullptr;
+    const uint32_t* di = nullptr;
+    if ((rc = dm_launch_goal_topk(g, recs, K, nullptr, 1, T, min_size, distance_weight, min_distance, &dk, &di,
+                                  g->plan_qcost, gain ? g->gain_out : nullptr, gain ? sc.min_gain : 0)))
+      return rc;
+    DM_HIP(hipMemcpyAsync(hk.data(), dk, sizeof(unsigned long long) * (size_t)T, hipMemcpyDeviceToHost, g->stream));
+    DM_HIP(hipMemcpyAsync(hi.data(), di, sizeof(uint32_t) * (size_t)T, hipMemcpyDeviceToHost, g->stream));
+    DM_HIP(hipStreamSynchronize(g->stream));
+    const int64_t c = idx[(size_t)r] = greedy_pick(hk.data(), hi.data(), T, idx, r);
+    if (c < 0) continue;
+    int64_t cell = -1;
+    DM_HIP(hipMemcpy(&cell, g->plan_qcell + c, sizeof cell, hipMemcpyDeviceToHost));
+    if (gain) DM_HIP(hipMemcpy(&out_gain[r], g->gain_out + c, sizeof out_gain[r], hipMemcpyDeviceToHost));
+    out_cell[r] = cell;
+    cell_centre(g, cell, out_xy + 2 * r);  // a reachable goal, not the centroid
+    if (coord) {
+      // the goal's view joins C before the next robot is scored; its gain
+      // is > 0, so C changed and no memo entry holds any longer
+      if ((rc = dm_gain_launch_commit(g, g->plan_qcell + c, 1, sc.radius_cells))) return rc;
+      DM_HIP(hipMemsetAsync(g->gain_memo_cell, 0xFF, sizeof(int64_t) * (size_t)K, g->stream));
+    }
+  }
+  if (coord) {
+    DM_HIP(hipStreamSynchronize(g->stream));
+    g->gain_claimed_valid = true;
+  }
+  memcpy(out_index, idx.data(), sizeof(int64_t) * (size_t)R);
+  return DM_OK;
+}
+
+int dm_assign_goals_path(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size,
+                         double distance_weight, double min_distance, int32_t inflate_cells, uint32_t max_cost,
+                         int32_t snap_cells, int64_t* out_index, double* out_xy, int64_t* out_cell) {
+  const GoalScoring sc = {"dm_assign_goals_path", GoalScoring::kSize, 0, 0, nullptr, 0};
+  return assign_goals_field(g, sc, robots_xy, n_robots, min_size, distance_weight, min_distance, inflate_cells,
+                            max_cost, snap_cells, out_index, out_xy, out_cell, nullptr);
+}
+
+int dm_assign_goals_gain(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size, int64_t min_gain,
+                         double distance_weight, double min_distance, int32_t inflate_cells, uint32_t max_cost,
+                         int32_t snap_cells, int32_t radius_cells, int64_t* out_index, double* out_xy,
+                         int64_t* out_cell, uint32_t* out_gain) {
+  const GoalScoring sc = {"dm_assign_goals_gain", GoalScoring::kGain, min_gain, radius_cells, nullptr, 0};
+  return assign_goals_field(g, sc, robots_xy, n_robots, min_size, distance_weight, min_distance, inflate_cells,
+                            max_cost, snap_cells, out_index, out_xy, out_cell, out_gain);
+}
+
+int dm_assign_goals_coord(dm_grid* g, const double* robots_xy, int32_t n_robots, const double* held_xy,
+                          int32_t n_held, int64_t min_size, int64_t min_gain, double distance_weight,
+                          double min_distance, int32_t inflate_cells, uint32_t max_cost, int32_t snap_cells,
+                          int32_t radius_cells, int64_t* out_index, double* out_xy, int64_t* out_cell,
+                          uint32_t* out_gain) {
+  const GoalScoring sc = {"dm_assign_goals_coord", GoalScoring::kMarginal, min_gain, radius_cells, held_xy, n_held};
+  return assign_goals_field(g, sc, robots_xy, n_robots, min_size, distance_weight, min_distance, inflate_cells,
+                            max_cost, snap_cells, out_index, out_xy, out_cell, out_gain);
+}
+
+}  // extern "C"

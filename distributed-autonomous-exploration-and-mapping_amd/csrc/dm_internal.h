@@ -744,67 +744,6 @@ int dm_launch_merge(dm_grid* g, hipStream_t s, const void* d_gathered, int32_t n
                     int64_t min_size);
 // The stream band exports end on and merges run on (dm_exchange_stream).
 inline hipStream_t dm_exchange_stream_of(const dm_grid* g) { return g->overlap ? g->pass_stream : g->stream; }
-// goal selection (dm_goals.hip)
-int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, const double* d_robots, int32_t R,
-                        int32_t T, int64_t min_size, double w, double min_dist,
-                        const unsigned long long** d_k, const uint32_t** d_i, const uint32_t* d_cost = nullptr,
-                        const uint32_t* d_gain = nullptr, int64_t min_gain = 0);
-// information gain (dm_gain.h, launched from dm_goals.hip); the gain_* arrays
-// of the handle are allocated by the caller (dm_api.cpp: grow_gain)
-// cells of n view points in g->gain_xy into g->gain_cell
-int dm_gain_launch_cells(dm_grid* g, int64_t n);
-// skip flags of K clusters (size < min_size or d_cost unreachable) into g->gain_skip
-int dm_gain_launch_skip(dm_grid* g, const dm_cluster* d_recs, const uint32_t* d_cost, int64_t K, int64_t min_size);
-// gains of n view cells into g->gain_out; d_skip and the memo (g->gain_memo_*) are optional
-int dm_gain_launch_views(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R,
-                         bool memo);
-// the overlap-aware forms, over the claimed set g->gain_claimed (allocated by
-// the caller, dm_api.cpp: ensure_claimed):
-// marginal gains of n view cells into g->gain_out, reading the claimed set only
-int dm_gain_launch_marginal(dm_grid* g, const int64_t* d_cell, const uint8_t* d_skip, int64_t n, int32_t R,
-                            bool memo);
-// the n views' visible sets into the claimed set, in one launch; reports nothing
-int dm_gain_launch_commit(dm_grid* g, const int64_t* d_cell, int64_t n, int32_t R);
-// view i's marginal gain into d_out[i], then its commit, for i = 0..n-1 in order (one launch each)
-int dm_gain_launch_joint(dm_grid* g, const int64_t* d_cell, int64_t n, int32_t R, uint32_t* d_out);
-// the claimed set as H * W bytes
-int dm_gain_launch_expand(dm_grid* g, uint8_t* d_out);
-// path planning (dm_plan.h, launched from dm_goals.hip); the plan_* arrays
-// of the handle are allocated by the caller (dm_api.cpp: ensure_plan)
-int dm_plan_launch_travers(dm_grid* g, int32_t inflate_cells);
-int dm_plan_launch_expand(dm_grid* g, uint8_t* d_out);
-// The field from n source cells (host arrays: cells, and their distinct
-// tiles) over g->plan_trav; synchronous.  stats: [4] or nullptr.
-int dm_plan_run_field(dm_grid* g, const int64_t* cells, int32_t n, const int32_t* tiles, int32_t n_tiles,
-                      uint32_t max_cost, uint64_t* stats);
-int dm_plan_launch_query(dm_grid* g, const double* d_xy, int64_t stride, int64_t n, int32_t snap_cells,
-                         uint32_t* d_cost, int64_t* d_cell);
-// walk back from *d_start into g->plan_path (cap entries); length and error
-// word go to g->plan_stat[4], [5]
-int dm_plan_launch_path(dm_grid* g, const int64_t* d_start, int64_t cap);
-int dm_launch_goal_gather(dm_grid* g, const dm_cluster* d_recs, const int64_t* d_idx, int32_t R, double* d_xy);
-// scan matcher (dm_match.h, launched from dm_goals.hip); the match_* arrays of
-// the handle are allocated by the caller (dm_api.cpp)
-// the response field of the first n_tiles tiles of g->match_tiles into g->match_V
-int dm_match_launch_field(dm_grid* g, int32_t n_tiles, int32_t r, bool mono);
-// fine coordinates (g->match_q, used beams at g->match_out + 4 S), the score
-// volume (g->match_vol) and the best candidates (g->match_out) of S scans
-int dm_match_launch_scans(dm_grid* g, int32_t S, int32_t N, int32_t A, int32_t k0, int32_t sub, int32_t half,
-                          int32_t stride);
-// whole-window relocalisation (dm_match_global.h, launched from dm_goals.hip);
-// the mg_* arrays of the handle are allocated by the caller (dm_api.cpp)
-struct MgShape {
-  int32_t N, A, k0, half_x, half_y, lb;  // block = 1 << lb
-  int32_t nbx, nby;                      // blocks per yaw along x and y
-  int32_t EWB, EHB;                      // the pooled field's planes: [EHB][EWB]
-  int32_t exhaustive;
-};
-// M_B of the first n_tiles tiles of g->mg_ptiles (PTX tiles per row) into g->mg_pool
-int dm_mg_launch_pool(dm_grid* g, int32_t n_tiles, int32_t lb, int32_t EWB, int32_t EHB, int32_t PTX);
-// One scan: candidate poses d_pose4 [A][4], ranges d_ranges [N], g->match_trig.
-// Synchronous.  res = k, i, j, score, used beams; stats [4] as dm_match_global's.
-int dm_mg_run_scan(dm_grid* g, const MgShape& sh, const double* d_pose4, const float* d_ranges, int32_t* res,
-                   uint64_t* stats);
 int dm_launch_ld06(dm_grid* g, int32_t S, const dm_ld06_point* d_pts, const int64_t* d_offsets,
                    int32_t N, int dir, float* d_ranges, float* d_intensities);
 
@@ -852,6 +791,50 @@ void dm_timer_end(dm_grid* g, KernelTimer* t);
     hipError_t _e = (call);                                  \
     if (_e != hipSuccess) return dm_hip_check(_e, #call);    \
   } while (0)
+
+// ---- what the entry points of every file share (dm_api.cpp, dm_goals.hip,
+// dm_match.hip) ---------------------------------------------------------------
+int check_grid(const dm_grid* g);   // the handle is not NULL
+int use_device(const dm_grid* g);   // hipSetDevice(the handle's)
+int check_integrate_args(int32_t S, int32_t N, const void* poses, const void* ranges);
+// Wait for all four streams; nothing of this handle is in flight afterwards.
+hipError_t dm_sync_all(dm_grid* g);
+// The planner, the gain calls, the goal calls that use them and both matchers
+// need the whole map in one handle: not a sharded parent, not a row band.
+int dm_check_whole_map(const dm_grid* g, const char* what);
+// What a field, a response field or a claimed set was computed for: any map
+// change moves it.
+inline uint64_t dm_map_version(const dm_grid* g) { return g->integrate_seq + g->reset_seq; }
+
+template <class T>
+int dev_alloc(T** p, int64_t count, const char* what) {
+  if (*p) { (void)hipFree(*p); *p = nullptr; }
+  if (count <= 0) count = 1;
+  hipError_t e = hipMalloc((void**)p, sizeof(T) * (size_t)count);
+  if (e != hipSuccess) {
+    *p = nullptr;
+    return dm_set_error(e == hipErrorOutOfMemory ? DM_ERR_OOM : DM_ERR_HIP,
+                        "hipMalloc(%s, %lld bytes): %s", what,
+                        (long long)(sizeof(T) * (size_t)count), hipGetErrorString(e));
+  }
+  return DM_OK;
+}
+
+template <class T>
+void dev_free(T*& p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+
+// grow-on-demand scratch: (re)allocate *p to n elements when *cap is smaller
+template <class T>
+int dev_grow(T** p, int64_t* cap, int64_t n, const char* what) {
+  if (n <= *cap) return DM_OK;
+  *cap = 0;
+  const int rc = dev_alloc(p, n, what);
+  if (!rc) *cap = n;
+  return rc;
+}
 
 // Kernel launch.
 #define DM_LAUNCH(kernel, grid, block, shmem, stream, ...) \

@@ -185,49 +185,19 @@ def assign_goals_gain(state, clusters: np.ndarray, robots_xy, origin_x: float, o
     R = check_radius(radius_cells)
     st = np.asarray(state)
     H, W = st.shape
-    robots = [(float(x), float(y)) for x, y in robots_xy]
-    cells = [plan.cell_of(x, y, origin_x, origin_y, resolution, W, H) for x, y in robots]
-    if any(c is None for c in cells):
-        raise ValueError("a robot is outside the grid")
+    cells = plan._robot_cells(robots_xy, origin_x, origin_y, resolution, W, H)
     if clusters is None or len(clusters) == 0:
-        return [None] * len(robots)
-    trav = plan.traversable(st, inflate_cells)
-    targets = [plan.cell_of(float(c["cx_m"]), float(c["cy_m"]), origin_x, origin_y, resolution, W, H)
-               for c in clusters]
+        return [None] * len(cells)
     gains: dict = cache if cache is not None else {}
-    taken = np.zeros(len(clusters), bool)
-    out = []
-    for rc in cells:
-        f = cache.get(rc) if cache is not None else None
-        if f is None:
-            f = plan.field(st, [rc], inflate_cells, max_cost, trav=trav)
-            if cache is not None:
-                cache[rc] = f
-        snapped = [plan.snap(f, t, snap_cells) for t in targets]
-        cost = np.array([s[0] for s in snapped], np.uint32)
-        dist = cost.astype(np.float64) * float(resolution) / 5.0
-        gain = np.zeros(len(clusters), np.int64)
-        for i, (_, cell) in enumerate(snapped):
-            if cell < 0:
-                continue
-            key = ("gain", R, cell)
-            if key not in gains:
-                gains[key] = visible_unknown(st, (cell % W, cell // W), R)
-            gain[i] = gains[key]
-        ok = ((clusters["size"] >= min_size) & (cost != plan.UNREACHABLE) & (dist >= min_distance)
-              & (gain >= int(min_gain)) & (gain > 0) & ~taken)
-        util = np.where(ok, gain.astype(np.float64) / (1.0 + float(distance_weight) * dist), -np.inf)
-        m = util.max()
-        if not np.isfinite(m):
-            out.append(None)
-            continue
-        best = np.flatnonzero(util == m)
-        i = int(best[np.argmin(clusters["label"][best])])  # ties: the smaller label
-        taken[i] = True
-        cell = snapped[i][1]
-        xy = (origin_x + ((cell % W) + 0.5) * resolution, origin_y + ((cell // W) + 0.5) * resolution)
-        out.append((i, xy, cell, int(gain[i])))
-    return out
+
+    def numerator(i, cell):
+        key = ("gain", R, cell)
+        if key not in gains:
+            gains[key] = visible_unknown(st, (cell % W, cell // W), R)
+        return gains[key]
+
+    return plan._greedy_goals(st, clusters, cells, origin_x, origin_y, resolution, min_size, distance_weight,
+                              min_distance, inflate_cells, max_cost, snap_cells, cache, numerator, min_gain)
 
 
 def assign_goals_coord(state, clusters: np.ndarray, robots_xy, origin_x: float, origin_y: float, resolution: float,
@@ -254,10 +224,7 @@ def assign_goals_coord(state, clusters: np.ndarray, robots_xy, origin_x: float, 
     held = np.asarray(held_xy, np.float64).reshape(-1, 2)
     if held.shape[0] > MAX_JOINT_VIEWS:
         raise ValueError(f"at most {MAX_JOINT_VIEWS} held views")
-    robots = [(float(x), float(y)) for x, y in robots_xy]
-    cells = [plan.cell_of(x, y, origin_x, origin_y, resolution, W, H) for x, y in robots]
-    if any(c is None for c in cells):
-        raise ValueError("a robot is outside the grid")
+    cells = plan._robot_cells(robots_xy, origin_x, origin_y, resolution, W, H)
     views: dict = cache if cache is not None else {}
 
     def window(cell):
@@ -273,37 +240,8 @@ def assign_goals_coord(state, clusters: np.ndarray, robots_xy, origin_x: float, 
             _commit(claimed, window(c[1] * W + c[0]))
     done = lambda out: (out, claimed) if return_claimed else out
     if clusters is None or len(clusters) == 0:
-        return done([None] * len(robots))
-    trav = plan.traversable(st, inflate_cells)
-    targets = [plan.cell_of(float(c["cx_m"]), float(c["cy_m"]), origin_x, origin_y, resolution, W, H)
-               for c in clusters]
-    taken = np.zeros(len(clusters), bool)
-    out = []
-    for rc in cells:
-        f = cache.get(rc) if cache is not None else None
-        if f is None:
-            f = plan.field(st, [rc], inflate_cells, max_cost, trav=trav)
-            if cache is not None:
-                cache[rc] = f
-        snapped = [plan.snap(f, t, snap_cells) for t in targets]
-        cost = np.array([s[0] for s in snapped], np.uint32)
-        dist = cost.astype(np.float64) * float(resolution) / 5.0
-        gain = np.zeros(len(clusters), np.int64)
-        for i, (_, cell) in enumerate(snapped):
-            if cell >= 0:
-                gain[i] = _marginal(claimed, window(cell))
-        ok = ((clusters["size"] >= min_size) & (cost != plan.UNREACHABLE) & (dist >= min_distance)
-              & (gain >= int(min_gain)) & (gain > 0) & ~taken)
-        util = np.where(ok, gain.astype(np.float64) / (1.0 + float(distance_weight) * dist), -np.inf)
-        m = util.max()
-        if not np.isfinite(m):
-            out.append(None)
-            continue
-        best = np.flatnonzero(util == m)
-        i = int(best[np.argmin(clusters["label"][best])])  # ties: the smaller label
-        taken[i] = True
-        cell = snapped[i][1]
-        _commit(claimed, window(cell))
-        xy = (origin_x + ((cell % W) + 0.5) * resolution, origin_y + ((cell // W) + 0.5) * resolution)
-        out.append((i, xy, cell, int(gain[i])))
-    return done(out)
+        return done([None] * len(cells))
+    return done(plan._greedy_goals(st, clusters, cells, origin_x, origin_y, resolution, min_size, distance_weight,
+                                   min_distance, inflate_cells, max_cost, snap_cells, cache,
+                                   lambda i, cell: _marginal(claimed, window(cell)), min_gain,
+                                   on_pick=lambda cell: _commit(claimed, window(cell))))

@@ -251,20 +251,28 @@ class OccupancyMapper:
             check(self._lib.dm_map_image(self._handle(), _vp(out)))
         return out
 
+    def _assign(self, fn, robots_xy, args, extra=()):
+        """One goal call: fn(handle, robots, R, *args, out_index, out_xy,
+        *extra outputs).  `extra`: the dtypes of the int64 / uint32 [R]
+        outputs behind out_xy.  Per robot (index, (x, y), *extra) or None."""
+        xy = np.ascontiguousarray(np.asarray(robots_xy, np.float64).reshape(-1, 2))
+        R = xy.shape[0]
+        idx = np.empty(R, np.int64)
+        out = np.empty((R, 2), np.float64)
+        more = [np.empty(R, dt) for dt in extra]
+        with self._lock:
+            check(fn(self._handle(), _vp(xy), R, *args, _vp(idx), _vp(out), *[_vp(a) for a in more]))
+        return [(int(i), (float(p[0]), float(p[1])), *(int(a[r]) for a in more)) if i >= 0 else None
+                for r, (i, p) in enumerate(zip(idx, out))]
+
     def assign_goals(self, robots_xy, min_size: int = 8, distance_weight: float = 1.0,
                      min_distance: float = 0.0):
         """Frontier goals on the device (dm_assign_goals) over the clusters of
         the last collected frontier result: per robot, in order, (index into
         that result's cluster list, (x, y)) or None.  Same policy as
         dm.goals.assign_goals (the host restatement the tests compare with)."""
-        xy = np.ascontiguousarray(np.asarray(robots_xy, np.float64).reshape(-1, 2))
-        R = xy.shape[0]
-        idx = np.empty(R, np.int64)
-        out = np.empty((R, 2), np.float64)
-        with self._lock:
-            check(self._lib.dm_assign_goals(self._handle(), _vp(xy), R, int(min_size), float(distance_weight),
-                                            float(min_distance), _vp(idx), _vp(out)))
-        return [(int(i), (float(p[0]), float(p[1]))) if i >= 0 else None for i, p in zip(idx, out)]
+        return self._assign(self._lib.dm_assign_goals, robots_xy,
+                            (int(min_size), float(distance_weight), float(min_distance)))
 
     # -- path planning (csrc/dm_plan.h; host restatement: dm/plan.py) ------
     PLAN_STAT_NAMES = ("reached", "traversable", "rounds", "tile_relaxations")
@@ -334,17 +342,9 @@ class OccupancyMapper:
         robot, in order, (cluster index, (x, y), cell) or None, where (x, y) is
         the centre of the reachable cell the cluster's centroid snaps to.
         Same policy as dm.plan.assign_goals_path."""
-        xy = np.ascontiguousarray(np.asarray(robots_xy, np.float64).reshape(-1, 2))
-        R = xy.shape[0]
-        idx = np.empty(R, np.int64)
-        out = np.empty((R, 2), np.float64)
-        cell = np.empty(R, np.int64)
-        with self._lock:
-            check(self._lib.dm_assign_goals_path(self._handle(), _vp(xy), R, int(min_size), float(distance_weight),
-                                                 float(min_distance), int(inflate_cells), int(max_cost),
-                                                 int(snap_cells), _vp(idx), _vp(out), _vp(cell)))
-        return [(int(i), (float(p[0]), float(p[1])), int(c)) if i >= 0 else None
-                for i, p, c in zip(idx, out, cell)]
+        return self._assign(self._lib.dm_assign_goals_path, robots_xy,
+                            (int(min_size), float(distance_weight), float(min_distance), int(inflate_cells),
+                             int(max_cost), int(snap_cells)), (np.int64,))
 
     # -- information gain (csrc/dm_gain.h; host restatement: dm/gain.py) ----
     def default_gain_radius(self) -> int:
@@ -374,20 +374,10 @@ class OccupancyMapper:
         per robot, in order, (cluster index, (x, y), cell, gain) or None, where
         gain is the visible-unknown count of the reachable cell the cluster's
         centroid snaps to.  Same policy as dm.gain.assign_goals_gain."""
-        xy = np.ascontiguousarray(np.asarray(robots_xy, np.float64).reshape(-1, 2))
-        R = xy.shape[0]
         rad = self.default_gain_radius() if radius_cells is None else int(radius_cells)
-        idx = np.empty(R, np.int64)
-        out = np.empty((R, 2), np.float64)
-        cell = np.empty(R, np.int64)
-        gain = np.empty(R, np.uint32)
-        with self._lock:
-            check(self._lib.dm_assign_goals_gain(self._handle(), _vp(xy), R, int(min_size), int(min_gain),
-                                                 float(distance_weight), float(min_distance), int(inflate_cells),
-                                                 int(max_cost), int(snap_cells), rad, _vp(idx), _vp(out),
-                                                 _vp(cell), _vp(gain)))
-        return [(int(i), (float(p[0]), float(p[1])), int(c), int(gn)) if i >= 0 else None
-                for i, p, c, gn in zip(idx, out, cell, gain)]
+        return self._assign(self._lib.dm_assign_goals_gain, robots_xy,
+                            (int(min_size), int(min_gain), float(distance_weight), float(min_distance),
+                             int(inflate_cells), int(max_cost), int(snap_cells), rad), (np.int64, np.uint32))
 
     def gain_views_joint(self, views_xy, radius_cells: int | None = None):
         """The marginal gains of view points (metres) taken in order
@@ -412,22 +402,12 @@ class OccupancyMapper:
         in this call see.  Per robot, in order, (cluster index, (x, y), cell,
         marginal gain) or None; the claimed set it leaves is gain_claimed().
         Same policy as dm.gain.assign_goals_coord."""
-        xy = np.ascontiguousarray(np.asarray(robots_xy, np.float64).reshape(-1, 2))
         held = np.ascontiguousarray(np.asarray(held_xy, np.float64).reshape(-1, 2))
-        R = xy.shape[0]
         rad = self.default_gain_radius() if radius_cells is None else int(radius_cells)
-        idx = np.empty(R, np.int64)
-        out = np.empty((R, 2), np.float64)
-        cell = np.empty(R, np.int64)
-        gain = np.empty(R, np.uint32)
-        with self._lock:
-            check(self._lib.dm_assign_goals_coord(self._handle(), _vp(xy), R, _vp(held) if held.shape[0] else None,
-                                                  held.shape[0], int(min_size), int(min_gain),
-                                                  float(distance_weight), float(min_distance), int(inflate_cells),
-                                                  int(max_cost), int(snap_cells), rad, _vp(idx), _vp(out),
-                                                  _vp(cell), _vp(gain)))
-        return [(int(i), (float(p[0]), float(p[1])), int(c), int(gn)) if i >= 0 else None
-                for i, p, c, gn in zip(idx, out, cell, gain)]
+        return self._assign(self._lib.dm_assign_goals_coord, robots_xy,
+                            (_vp(held) if held.shape[0] else None, held.shape[0], int(min_size), int(min_gain),
+                             float(distance_weight), float(min_distance), int(inflate_cells), int(max_cost),
+                             int(snap_cells), rad), (np.int64, np.uint32))
 
     def gain_claimed(self) -> np.ndarray:
         """The claimed set left by the last gain_views_joint or

@@ -171,6 +171,66 @@ def path(cost: np.ndarray, trav: np.ndarray, cell: int) -> list[int]:
     return out[::-1]
 
 
+def _greedy_goals(st, clusters: np.ndarray, robot_cells, origin_x: float, origin_y: float, resolution: float,
+                  min_size: int, distance_weight: float, min_distance: float, inflate_cells: int, max_cost: int,
+                  snap_cells: int, cache: dict | None, numerator, min_numerator: int = 0, on_pick=None):
+    """The one greedy loop of assign_goals_path, dm.gain.assign_goals_gain and
+    dm.gain.assign_goals_coord (device: assign_goals_field, csrc/dm_goals.hip).
+    Robots choose in order.  Each gets its own field (kept in `cache` under
+    its cell (cx, cy) when a dict is given) and the snapped cell of every
+    cluster centroid under it; cluster i scores
+        util = numerator(i, cell) / (1 + distance_weight * dist),
+        dist = cost * resolution / 5,
+    where `numerator` is asked for every cluster that snapped somewhere and
+    returns an integer.  A cluster is eligible iff size >= min_size, it is
+    reached, dist >= min_distance, numerator >= min_numerator, numerator > 0
+    (util 0 is the device's key of "not eligible") and no earlier robot took
+    it.  The best util wins, ties go to the smaller label; `on_pick(cell)`
+    runs before the next robot is scored.  Returns, per robot, (cluster index,
+    (x, y) centre of the snapped cell, snapped cell, numerator) or None."""
+    H, W = st.shape
+    trav = traversable(st, inflate_cells)
+    targets = [cell_of(float(c["cx_m"]), float(c["cy_m"]), origin_x, origin_y, resolution, W, H) for c in clusters]
+    taken = np.zeros(len(clusters), bool)
+    out = []
+    for rc in robot_cells:
+        f = cache.get(rc) if cache is not None else None
+        if f is None:
+            f = field(st, [rc], inflate_cells, max_cost, trav=trav)
+            if cache is not None:
+                cache[rc] = f
+        snapped = [snap(f, t, snap_cells) for t in targets]
+        cost = np.array([s[0] for s in snapped], np.uint32)
+        dist = cost.astype(np.float64) * float(resolution) / 5.0
+        num = np.zeros(len(clusters), np.int64)
+        for i, (_, cell) in enumerate(snapped):
+            if cell >= 0:
+                num[i] = numerator(i, cell)
+        ok = ((clusters["size"] >= min_size) & (cost != UNREACHABLE) & (dist >= min_distance)
+              & (num >= int(min_numerator)) & (num > 0) & ~taken)
+        util = np.where(ok, num.astype(np.float64) / (1.0 + float(distance_weight) * dist), -np.inf)
+        m = util.max()
+        if not np.isfinite(m):
+            out.append(None)
+            continue
+        best = np.flatnonzero(util == m)
+        i = int(best[np.argmin(clusters["label"][best])])  # ties: the smaller label
+        taken[i] = True
+        cell = snapped[i][1]
+        if on_pick is not None:
+            on_pick(cell)
+        xy = (origin_x + ((cell % W) + 0.5) * resolution, origin_y + ((cell // W) + 0.5) * resolution)
+        out.append((i, xy, cell, int(num[i])))
+    return out
+
+
+def _robot_cells(robots_xy, origin_x: float, origin_y: float, resolution: float, width: int, height: int):
+    cells = [cell_of(float(x), float(y), origin_x, origin_y, resolution, width, height) for x, y in robots_xy]
+    if any(c is None for c in cells):
+        raise ValueError("a robot is outside the grid")
+    return cells
+
+
 def assign_goals_path(state, clusters: np.ndarray, robots_xy, origin_x: float, origin_y: float, resolution: float,
                       min_size: int = 8, distance_weight: float = 1.0, min_distance: float = 0.0,
                       inflate_cells: int = 2, max_cost: int = 0, snap_cells: int = 5, cache: dict | None = None):
@@ -184,36 +244,9 @@ def assign_goals_path(state, clusters: np.ndarray, robots_xy, origin_x: float, o
         raise ValueError("distance_weight must be >= 0 (dm_assign_goals_path rejects it too)")
     st = np.asarray(state)
     H, W = st.shape
-    robots = [(float(x), float(y)) for x, y in robots_xy]
-    cells = [cell_of(x, y, origin_x, origin_y, resolution, W, H) for x, y in robots]
-    if any(c is None for c in cells):
-        raise ValueError("a robot is outside the grid")
+    cells = _robot_cells(robots_xy, origin_x, origin_y, resolution, W, H)
     if clusters is None or len(clusters) == 0:
-        return [None] * len(robots)
-    trav = traversable(st, inflate_cells)
-    targets = [cell_of(float(c["cx_m"]), float(c["cy_m"]), origin_x, origin_y, resolution, W, H) for c in clusters]
-    size = clusters["size"].astype(np.float64)
-    taken = np.zeros(len(clusters), bool)
-    out = []
-    for rc in cells:
-        f = cache.get(rc) if cache is not None else None
-        if f is None:
-            f = field(st, [rc], inflate_cells, max_cost, trav=trav)
-            if cache is not None:
-                cache[rc] = f
-        snapped = [snap(f, t, snap_cells) for t in targets]
-        cost = np.array([s[0] for s in snapped], np.uint32)
-        dist = cost.astype(np.float64) * float(resolution) / 5.0
-        ok = (clusters["size"] >= min_size) & (cost != UNREACHABLE) & (dist >= min_distance) & ~taken
-        util = np.where(ok, size / (1.0 + float(distance_weight) * dist), -np.inf)
-        m = util.max()
-        if not np.isfinite(m):
-            out.append(None)
-            continue
-        best = np.flatnonzero(util == m)
-        i = int(best[np.argmin(clusters["label"][best])])  # ties: the smaller label
-        taken[i] = True
-        cell = snapped[i][1]
-        xy = (origin_x + ((cell % W) + 0.5) * resolution, origin_y + ((cell // W) + 0.5) * resolution)
-        out.append((i, xy, cell))
-    return out
+        return [None] * len(cells)
+    got = _greedy_goals(st, clusters, cells, origin_x, origin_y, resolution, min_size, distance_weight, min_distance,
+                        inflate_cells, max_cost, snap_cells, cache, lambda i, cell: int(clusters["size"][i]))
+    return [g and g[:3] for g in got]
