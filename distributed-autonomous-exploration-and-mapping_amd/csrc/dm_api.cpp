@@ -670,6 +670,7 @@ int dm_destroy(dm_grid* g) {
   if (g->h_mg) (void)hipHostFree(g->h_mg);
   dev_free(g->gain_xy); dev_free(g->gain_cell); dev_free(g->gain_out); dev_free(g->gain_skip);
   dev_free(g->gain_memo_cell); dev_free(g->gain_memo_gain); dev_free(g->gain_claimed);
+  dev_free(g->fuse_stats);
   for (auto& w : g->iw) {
     dev_free(w.pieces); dev_free(w.hitems); dev_free(w.litems); dev_free(w.heavy_list); dev_free(w.slabs);
     dev_free(w.heavy_done); dev_free(w.tile_count); dev_free(w.tile_cur); dev_free(w.cnt); dev_free(w.sh);

@@ -426,13 +426,7 @@ struct ApplyArgs {
 
 // SPEC a7 as selects (no branches), lowest priority first: L == 0 -> -1,
 // else L >= occ_t -> 100, else L <= free_t -> 0, else -1.
-__device__ inline int8_t state_of(const ApplyArgs& p, float L) {
-  int32_t r = -1;
-  r = L <= p.free_t ? 0 : r;
-  r = L >= p.occ_t ? 100 : r;
-  r = L == 0.0f ? -1 : r;
-  return (int8_t)r;
-}
+__device__ inline int8_t state_of(const ApplyArgs& p, float L) { return dm_state_a7(L, p.occ_t, p.free_t); }
 
 // SPEC a6 in this exact op order (no FMA: -ffp-contract=off).
 __device__ inline float apply_one(const ApplyArgs& p, float L, uint32_t h, uint32_t m) {
@@ -1732,19 +1726,28 @@ int dm_launch_recount(dm_grid* g) {
   // pass stream read it (bulk calls have already joined every stream; an
   // fmask switch-on inside dm_enqueue_frontiers may not have)
   DM_HIP(dm_join_pass_stream(g));
+  KernelTimer t;
+  dm_timer_begin(g, "recount", &t);  // k_recount and the tile list's rebuild
   DM_LAUNCH(k_recount, dim3((unsigned)g->NT), dim3(256), 0, g->stream, ge, g->state,
                      g->tile_free, g->fmask, g->fedge, g->tile_seen);
-  DM_HIP(hipGetLastError());
-  if (int rc = dm_launch_relist(g, false)) return rc;
+  const hipError_t e = hipGetLastError();
+  const int rc = e == hipSuccess ? dm_launch_relist(g, false) : DM_OK;
+  dm_timer_end(g, &t);  // on every path: the timer's events are handed over
+  DM_HIP(e);
+  if (rc) return rc;
   g->fmask_valid = true;
   return DM_OK;
 }
 
 int dm_launch_state_from_logodds(dm_grid* g) {
   const int64_t cells = g->R * g->W;
+  KernelTimer t;
+  dm_timer_begin(g, "state_from_l", &t);
   DM_LAUNCH(k_state_from_l, dim3(grid_for(cells, 256)), dim3(256), 0, g->stream,
                      make_apply(g), cells, g->L, g->state);
-  DM_HIP(hipGetLastError());
+  const hipError_t e = hipGetLastError();
+  dm_timer_end(g, &t);
+  DM_HIP(e);
   return dm_launch_recount(g);
 }
 

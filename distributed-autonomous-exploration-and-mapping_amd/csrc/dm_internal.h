@@ -130,6 +130,26 @@ __host__ __device__ inline double dm_centroid(double origin, long long sum, long
   return origin + (m + 0.5) * res;
 }
 
+// SPEC a7: L == 0 -> -1, else L >= occ_t -> 100, else L <= free_t -> 0, else
+// -1, as selects, lowest priority first (thresholds without signed zeros).
+// The one statement of a7 on the device: the map update's state_of
+// (dm_integrate.hip) and the fusion (dm_fuse.hip) both call it.
+__host__ __device__ inline int8_t dm_state_a7(float L, float occ_t, float free_t) {
+  int32_t r = -1;
+  r = L <= free_t ? 0 : r;
+  r = L >= occ_t ? 100 : r;
+  r = L == 0.0f ? -1 : r;
+  return (int8_t)r;
+}
+// SPEC a6's clamp as the SPEC writes it (bounds without signed zeros): what
+// the map update's v_med3 form (apply_one, dm_integrate.hip) computes for
+// finite L and l_min <= l_max, spelled out for callers outside that loop.
+__host__ __device__ inline float dm_clamp_a6(float L, float l_min, float l_max) {
+  if (L < l_min) L = l_min;
+  if (L > l_max) L = l_max;
+  return L;
+}
+
 struct dm_grid;
 // async D2H of both shard-counter blocks into g->h_sh (pinned)
 hipError_t dm_copy_shards(dm_grid* g);
@@ -251,9 +271,16 @@ struct dm_grid {
   // writes `state` either sets tile_seen[tile] = 1 for the tiles it wrote
   // (k_tile_accum: light / medium items, the heavy finisher, sparse items)
   // or is followed by k_recount over the map (dm_launch_recount: dm_reset,
-  // dm_set_state, dm_set_logodds, dm_load).  A new state writer must do one
+  // dm_set_state, dm_set_logodds, dm_load, the dm_fuse_* calls).  A new state writer must do one
   // of the two; tests/test_gpu_tile_seen.py fails against a library whose
   // bit rows trust a stale flag (mutation-checked in round 5).
+  // INVARIANT 2 (k_fuse, dm_fuse.hip, is wrong without it): in every cell
+  // state == dm_state_a7(L) with the handle's thresholds.  Every state writer
+  // derives the byte from the L it stores (k_tile_accum's apply,
+  // k_state_from_l, k_set_state, dm_reset's L = 0 / state = -1).  The fusion
+  // does not read the old state byte: it recomputes it from the old L, for
+  // its "state changed" count and to store the byte only where it differs.  A
+  // writer that stores a state not derived from L would break both.
   uint8_t* tile_seen = nullptr;
   bool fmask_on = false, fmask_valid = false;
   int fmask_mode = 0;  // DM_FMASK=auto|on|off (read at dm_create; tests / A/B): 0 auto, 1 on, 2 off
@@ -582,6 +609,9 @@ struct dm_grid {
   uint32_t* gain_claimed = nullptr;
   bool gain_claimed_valid = false;    // one of the two calls has run (dm_gain_claimed)
 
+  // map fusion (dm_fuse.hip): covered, contributing, state-changed cells of the call, allocated on first use
+  unsigned long long* fuse_stats = nullptr;
+
   // profiling
   bool profile = false;
   std::vector<KernelTimer> pending;
@@ -763,6 +793,9 @@ int dm_sh_get_state(dm_grid* g, int8_t* out);
 int dm_sh_get_logodds(dm_grid* g, float* out);
 int dm_sh_set_logodds(dm_grid* g, const float* in);
 int dm_sh_set_state(dm_grid* g, const int8_t* in);
+// dm_fuse_* on a sharded parent: one_band(band, ctx, stats[3]) on every band, stats summed
+typedef int (*dm_fuse_band_fn)(dm_grid* band, void* ctx, uint64_t* stats);
+int dm_sh_fuse(dm_grid* g, int same_device, uint64_t* out_stats, dm_fuse_band_fn one_band, void* ctx);
 int dm_sh_frontiers(dm_grid* g, uint8_t* mask, int64_t* labels, dm_cluster* out, int64_t cap, int64_t* n_out);
 int dm_sh_frontiers_begin(dm_grid* g);
 int dm_sh_frontiers_end(dm_grid* g, dm_cluster* out, int64_t cap, int64_t* n_out);

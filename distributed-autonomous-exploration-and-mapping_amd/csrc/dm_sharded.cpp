@@ -548,6 +548,31 @@ int dm_sh_set_logodds(dm_grid* g, const float* in) {
   return DM_OK;
 }
 
+// Map fusion (dm_fuse.hip): every band fuses its own rows of the same global
+// picture, one_band(band, ctx, stats) being the single-handle call on it (from
+// its own upload of the source); the stats add up to one handle's, each
+// destination cell belonging to one band.  Band 0 validates the arguments
+// before any band is written.  same_device >= 0 (dm_fuse_grid: the source
+// handle's device): all or nothing, no band is written when one is elsewhere.
+// The calls themselves stay in dm_fuse.hip: this file names none of them, so a
+// build without that file (tests/native: the sanitized host library) links.
+int dm_sh_fuse(dm_grid* g, int same_device, uint64_t* out_stats, dm_fuse_band_fn one_band, void* ctx) {
+  dm_shard_set* s = g->sh;
+  for (int r = 0; same_device >= 0 && r < s->P; ++r)
+    if (s->dev[(size_t)r] != same_device)
+      return dm_set_error(DM_ERR_INVALID_ARG, "src_grid is on device %d, band %d on %d", same_device, r,
+                          s->dev[(size_t)r]);
+  uint64_t sum[3] = {0, 0, 0};
+  for (int r = 0; r < s->P; ++r) {
+    uint64_t one[3] = {0, 0, 0};
+    if (int rc = one_band(s->band[(size_t)r], ctx, one)) return rc;
+    for (int i = 0; i < 3; ++i) sum[i] += one[i];
+  }
+  if (out_stats)
+    for (int i = 0; i < 3; ++i) out_stats[i] = sum[i];
+  return DM_OK;
+}
+
 int dm_sh_set_state(dm_grid* g, const int8_t* in) {
   dm_shard_set* s = g->sh;
   for (int r = 0; r < s->P; ++r)

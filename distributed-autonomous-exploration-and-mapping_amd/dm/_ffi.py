@@ -103,6 +103,22 @@ class DmLd06Point(ctypes.Structure):
 LD06_POINT_DTYPE = [("angle_deg", "<f4"), ("distance_mm", "<u2"), ("intensity", "u1"), ("pad", "u1")]
 
 
+class DmFuseSource(ctypes.Structure):
+    """Mirror of ``dm_fuse_source`` (include/dm.h)."""
+
+    _fields_ = [
+        ("width", ctypes.c_int64),
+        ("height", ctypes.c_int64),
+        ("resolution", ctypes.c_double),
+        ("origin_x", ctypes.c_double),
+        ("origin_y", ctypes.c_double),
+    ]
+
+
+DM_FUSE_ADD = 0
+DM_FUSE_FILL = 1
+
+
 class DmKernelStat(ctypes.Structure):
     _fields_ = [
         ("name", ctypes.c_char * 32),
@@ -194,6 +210,11 @@ SIGNATURES = {
                        _vp, _vp, _vp, _vp, _vp],
     "dm_match_global": [_vp, _i32, _vp, _i32, _vp, _f32, _f32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
                         _vp, _vp, _vp, _vp, _vp],
+    "dm_fuse_logodds": [_vp, ctypes.POINTER(DmFuseSource), _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                        _i32, _vp],
+    "dm_fuse_state": [_vp, ctypes.POINTER(DmFuseSource), _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                      _i32, _vp],
+    "dm_fuse_grid": [_vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, _i32, _vp],
 }
 # functions returning const char*
 STRING_FUNCS = ("dm_last_error", "dm_version")

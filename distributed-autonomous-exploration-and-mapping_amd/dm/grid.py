@@ -239,6 +239,51 @@ class OccupancyMapper:
         with self._lock:
             check(self._lib.dm_set_state(self._handle(), _vp(st)))
 
+    # -- map fusion -------------------------------------------------------
+    FUSE_STAT_NAMES = ("covered", "contributing", "changed")
+
+    def _fuse(self, fn, values, dtype, geom, transform, mode):
+        from . import fuse
+
+        g = geom if isinstance(geom, dict) else fuse.geom_of(geom)
+        src = _ffi.DmFuseSource(int(g["width"]), int(g["height"]), float(g["resolution"]), float(g["origin_x"]),
+                                float(g["origin_y"]))
+        values = np.ascontiguousarray(values, dtype=dtype)
+        if values.size != src.width * src.height:
+            raise DmError(_ffi.DM_ERR_SHAPE, f"source has {values.size} cells, geometry {src.width} x {src.height}")
+        tx, ty, yaw = (float(v) for v in transform)
+        out = (ctypes.c_uint64 * 3)()
+        with self._lock:
+            check(fn(self._handle(), ctypes.byref(src), _vp(values), tx, ty, yaw, fuse.mode_code(mode), out))
+        return {k: int(out[i]) for i, k in enumerate(self.FUSE_STAT_NAMES)}
+
+    def fuse_logodds(self, L, geom, transform, mode="add") -> dict:
+        """Fold a peer's log-odds map (float32 [h, w], geometry `geom`: a dict
+        width / height / resolution / origin_x / origin_y or dm_params, in the
+        peer's frame) into this map under transform = (tx, ty, yaw), peer frame
+        -> ours (dm_fuse_logodds).  mode "add": log-odds add; "fill": only cells
+        this map does not know yet.  Returns {"covered", "contributing",
+        "changed"}.  Same result as dm.fuse.fuse_map, bit for bit."""
+        return self._fuse(self._lib.dm_fuse_logodds, L, np.float32, geom, transform, mode)
+
+    def fuse_state(self, st, geom, transform, mode="add") -> dict:
+        """The same from an OccupancyGrid.data image (int8 -1 / 0 / 100):
+        100 adds l_occ, 0 adds l_free (dm_fuse_state)."""
+        return self._fuse(self._lib.dm_fuse_state, st, np.int8, geom, transform, mode)
+
+    def fuse_from(self, other_mapper, transform, mode="add") -> dict:
+        """The same from another mapper's log-odds, device to device
+        (dm_fuse_grid): `other_mapper` is a whole-map mapper on this device."""
+        from . import fuse
+
+        tx, ty, yaw = (float(v) for v in transform)
+        out = (ctypes.c_uint64 * 3)()
+        first, second = sorted((self, other_mapper), key=id)  # one lock order for a pair of mappers
+        with first._lock, second._lock:
+            check(self._lib.dm_fuse_grid(self._handle(), other_mapper._handle(), tx, ty, yaw, fuse.mode_code(mode),
+                                         out))
+        return {k: int(out[i]) for i, k in enumerate(self.FUSE_STAT_NAMES)}
+
     def reset(self):
         with self._lock:
             check(self._lib.dm_reset(self._handle()))

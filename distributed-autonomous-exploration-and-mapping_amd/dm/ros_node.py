@@ -46,6 +46,12 @@ callback signatures:
   (``geometry_msgs/PoseArray``: the goals the other robots hold) and scores its
   own goal by what it would see that those goals do not
   (``dm_assign_goals_coord``);
+* with ``dm_peer_map_topic`` set (default off), subscribes a peer's
+  ``nav_msgs/OccupancyGrid`` in the peer's own map frame and folds it into this
+  map on the device (``dm_fuse_state``; the merge step of a multi-robot stack,
+  multirobot_map_merge) under the frame transform given as
+  ``dm_peer_map_transform`` or found by ``align_peer`` (a peer's scan
+  relocalised in this map, ``dm_match_global``);
 * with ``dm_devices`` naming several GPUs, the map is one sharded handle
   (``dm_create_sharded``: row bands over those devices, the exchange inside
   libdm) behind the same calls.
@@ -250,6 +256,15 @@ class SlamParams:
     # dm_goal_information_gain; off: as before
     dm_goal_coordinate: bool = False
     dm_peer_goals_topic: str = "/peer_goals"
+    # a peer's map (nav_msgs/OccupancyGrid in the peer's map frame) folded into
+    # this one on the device (dm_fuse_state); "": off.  Mode "fill" writes only
+    # cells this map does not know yet, so a peer republishing its map every
+    # map_update_interval does not count its evidence twice; "add" adds log-odds.
+    # dm_peer_map_transform: "x,y,yaw" of the peer's frame in ours; "": unknown
+    # until MappingNode.align_peer finds it, peer maps are dropped meanwhile.
+    dm_peer_map_topic: str = ""
+    dm_peer_map_mode: str = "fill"
+    dm_peer_map_transform: str = ""
     # correct every accepted scan's pose against the map on the device
     # (dm_match_scans) and keep the correction as map -> odom; off: the pose
     # provider's pose is taken as it is, as before.  Needs use_scan_matching
@@ -410,6 +425,22 @@ def parse_devices(spec) -> list[int]:
     return [int(d) for d in str(spec).replace(" ", "").split(",") if d != ""]
 
 
+def parse_transform(spec):
+    """dm_peer_map_transform: "x,y,yaw" (or three numbers) -> (x, y, yaw); "" -> None."""
+    if isinstance(spec, (list, tuple)):
+        parts = list(spec)
+    else:
+        parts = [v for v in str(spec).replace(" ", "").split(",") if v != ""]
+    if not parts:
+        return None
+    if len(parts) != 3:
+        raise ValueError(f"dm_peer_map_transform needs x,y,yaw, got {spec!r}")
+    x, y, yaw = (float(v) for v in parts)
+    if not (math.isfinite(x) and math.isfinite(y) and math.isfinite(yaw)):
+        raise ValueError(f"dm_peer_map_transform must be finite, got {spec!r}")
+    return (x, y, yaw)
+
+
 class MappingNode:
     """GPU mapping stage: /scan (+TF) -> /map + /frontiers (+ /goal_pose).
 
@@ -478,6 +509,16 @@ class MappingNode:
         self.relocalizing = bool(p.dm_relocalize) and self.map_loaded
         self.relocalize_rejected = 0
         self.last_relocalize = None        # mapper.relocalize's result of the last attempt
+        # dm_peer_map_topic: the peer's frame in ours (x, y, yaw), None until
+        # configured or found by align_peer
+        if str(p.dm_peer_map_mode) not in ("fill", "add"):
+            raise ValueError(f"dm_peer_map_mode must be 'fill' or 'add', got {p.dm_peer_map_mode!r}")
+        self.peer_transform = parse_transform(p.dm_peer_map_transform)
+        self.peer_maps_fused = 0
+        self.peer_maps_dropped = 0
+        self.peer_align_rejected = 0
+        self.last_peer_align = None        # mapper.relocalize's result of the last align_peer
+        self.last_peer_fuse = None         # the stats of the last fused peer map
 
     # main.py:77-78 keeps the signature scan_cb(self, msg)
     def scan_cb(self, msg):
@@ -511,6 +552,49 @@ class MappingNode:
         """dm_peer_goals_topic: the goals the other robots hold now; the next
         choose_goal with dm_goal_coordinate discounts what they will see."""
         self.peer_goals = [(float(p.position.x), float(p.position.y)) for p in msg.poses]
+
+    def align_peer(self, scan_msg, peer_pose) -> bool:
+        """Find the peer's frame in ours from one of its scans: `scan_msg` was
+        taken at `peer_pose` (x, y, yaw) in the peer's map frame; relocalised in
+        this map (OccupancyMapper.relocalize, the whole map) it gives the
+        transform matched o peer_pose^-1 that peer_map_cb then uses.  A rejected
+        match is counted and leaves the transform as it was."""
+        from . import fuse
+
+        res = self.mapper.relocalize(scan_msg, None, self.slam)
+        self.last_peer_align = res
+        if not res["accepted"]:
+            self.peer_align_rejected += 1
+            return False
+        self.peer_transform = fuse.peer_transform(tuple(float(v) for v in res["pose"]),
+                                                  tuple(float(v) for v in peer_pose))
+        return True
+
+    def peer_map_cb(self, msg):
+        """dm_peer_map_topic: a peer's nav_msgs/OccupancyGrid in its own frame,
+        folded into this map on the device (OccupancyMapper.fuse_state,
+        dm_fuse_state) in mode dm_peer_map_mode.  The geometry is msg.info's;
+        a turned origin is composed into the transform (the grid turns about
+        its origin corner).  Without a known transform the message is counted
+        in peer_maps_dropped and ignored."""
+        if self.peer_transform is None:
+            self.peer_maps_dropped += 1
+            return None
+        info = msg.info
+        ox, oy = float(info.origin.position.x), float(info.origin.position.y)
+        geom = {"width": int(info.width), "height": int(info.height), "resolution": float(info.resolution),
+                "origin_x": ox, "origin_y": oy}
+        transform = self.peer_transform
+        oyaw = yaw_from_quaternion(info.origin.orientation)
+        if oyaw != 0.0:
+            # p_frame = O + R(oyaw) (p - O) for a point p of the unturned grid
+            c, s = math.cos(oyaw), math.sin(oyaw)
+            transform = se2_compose(transform, (ox - (c * ox - s * oy), oy - (s * ox + c * oy), oyaw))
+        data = np.asarray(msg.data, dtype=np.int8)
+        stats = self.mapper.fuse_state(data, geom, transform, str(self.slam.dm_peer_map_mode))
+        self.last_peer_fuse = stats
+        self.peer_maps_fused += 1
+        return stats
 
     def _match(self, msg, odom, prior):
         """Correct an accepted scan's prior against the map (the device's
@@ -798,6 +882,8 @@ def main(args=None):  # pragma: no cover - needs ROS 2
     node.create_subscription(RosLaserScan, sp.scan_topic, mn.scan_cb, 10)
     if sp.dm_goal_coordinate:
         node.create_subscription(RosPoseArray, sp.dm_peer_goals_topic, mn.peer_goals_cb, 10)
+    if sp.dm_peer_map_topic:
+        node.create_subscription(RosGrid, sp.dm_peer_map_topic, mn.peer_map_cb, 10)
     # slam_toolbox publishes the map on its own period, not per scan
     node.create_timer(sp.map_update_interval, mn.timer_cb)
     node.create_timer(0.01, mn.poll_frontiers)  # frontiers go out as soon as the GPU pass is done

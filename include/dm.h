@@ -721,6 +721,78 @@ int dm_match_global(dm_grid* g, int32_t S, const double* poses, int32_t N, const
                     int32_t* out_best /*[S][3] k,i,j*/, uint32_t* out_score, int32_t* out_n_used,
                     double* out_pose /*[S][3]*/, uint64_t* out_stats /*[S][4], may be NULL*/);
 
+/* ---- map fusion: merge a peer's occupancy map under a rigid transform ----
+ *
+ * WHAT THIS REPLACES
+ *   Nothing in the reference: its robots share no map (ThymioBrain.map_cb,
+ *   server/thymio_project/thymio_project/main.py:80-81, keeps the one /map it
+ *   is sent).  It is the merge step of a multi-robot ROS stack
+ *   (multirobot_map_merge): a peer's map is placed in our frame by a rigid
+ *   transform and folded into ours, here on the device-resident map instead of
+ *   dm_get_logodds -> host loop -> dm_set_logodds.
+ *
+ * Geometry of the source map, in ITS frame. */
+typedef struct dm_fuse_source {
+  int64_t width, height;     /* cells; each in [1, 32768] */
+  double resolution;         /* metres per cell, finite, > 0 (may differ from the destination's) */
+  double origin_x, origin_y; /* world coords of the lower-left corner of cell (0,0), finite */
+} dm_fuse_source;
+
+#define DM_FUSE_ADD 0  /* independent evidence: log-odds add */
+#define DM_FUSE_FILL 1 /* only cells the destination does not know yet; idempotent */
+
+/* (tx, ty, yaw) maps source-frame points into the destination frame:
+ * p_dst = R(yaw) p_src + t.  c = cos(yaw) and s = sin(yaw) are evaluated on
+ * the host with the C library, as in dm_integrate.  Everything below is
+ * integers and separately rounded IEEE doubles / floats (no FMA), so every
+ * result is unique and bit-exact (dm/fuse.py restates it in NumPy).
+ *   For every destination cell (cx, cy) the handle owns, in global cell
+ *   coordinates (a band handle: its rows only), with the destination's params:
+ *     wx = origin_x + ((double)cx + 0.5) * resolution, wy likewise from cy;
+ *     dx = wx - tx, dy = wy - ty;
+ *     sx = c*dx + s*dy, sy = c*dy - s*dx   (two products, one sum / difference,
+ *                                           each rounded);
+ *     qx = floor((sx - src.origin_x) / src.resolution), qy likewise.
+ *   The cell is COVERED iff sx, sy are finite and 0 <= qx < src.width,
+ *   0 <= qy < src.height (compared as doubles): nearest-neighbour sampling of
+ *   the source at the destination cell's centre.
+ *   l = the source value at (qx, qy).  dm_fuse_logodds / dm_fuse_grid: the float
+ *   there, a non-finite one reads as 0.  dm_fuse_state: dm_set_state's mapping
+ *   with the DESTINATION's parameters: 100 -> l_occ, 0 -> l_free, else 0.
+ *   A covered cell CONTRIBUTES iff l != 0 and, in DM_FUSE_FILL, the
+ *   destination's L == 0.
+ *   A contributing cell gets L' = clamp(L + l) (DM_FUSE_ADD: one float add) or
+ *   L' = clamp(l) (DM_FUSE_FILL), clamp = SPEC a6's to the destination's
+ *   [l_min, l_max] (if (L' < l_min) L' = l_min; if (L' > l_max) L' = l_max,
+ *   zero bounds read as +0), then state = SPEC a7 of L'.  Every other cell
+ *   keeps its L and state bit for bit.
+ * out_stats (may be NULL): uint64[3] = covered cells, contributing cells,
+ * cells whose state byte changed.
+ * Synchronous, ordered after everything enqueued on the handle (all its
+ * streams are joined, as by dm_set_logodds).  On success the map version is
+ * bumped exactly as by dm_set_logodds: the dm_plan_* readers return
+ * DM_ERR_STATE until dm_plan_field runs again, the matcher's field, the pooled
+ * field and the claimed set are rebuilt on next use; the tile summaries the
+ * frontier pass reads are rebuilt.  Whole-map handles, band handles (a band
+ * fuses its own rows of the same global picture) and dm_create_sharded handles
+ * (every band; stats summed) all work.
+ * Errors: DM_ERR_INVALID_ARG for NULL pointers, geometry outside the limits
+ * above, non-finite tx, ty or yaw, an unknown mode; DM_ERR_OOM if the staging
+ * buffer of the source cannot be allocated; the map and its version are then
+ * untouched.  A source that covers no destination cell is DM_OK with stats
+ * 0, 0, 0. */
+int dm_fuse_logodds(dm_grid* g, const dm_fuse_source* src, const float* L_src, double tx, double ty, double yaw,
+                    int32_t mode, uint64_t* out_stats /*[3], may be NULL*/);
+int dm_fuse_state(dm_grid* g, const dm_fuse_source* src, const int8_t* state_src, double tx, double ty, double yaw,
+                  int32_t mode, uint64_t* out_stats /*[3], may be NULL*/);
+/* The same from another handle's log-odds, read on the device with no host
+ * round trip.  src_grid must be a whole-map dm_create handle (no band, not
+ * sharded) on the same HIP device as g (a sharded g: as all its bands) and not
+ * g itself; anything else is DM_ERR_INVALID_ARG.  Its stream is synchronised
+ * first; the source geometry comes from its params. */
+int dm_fuse_grid(dm_grid* g, dm_grid* src_grid, double tx, double ty, double yaw, int32_t mode,
+                 uint64_t* out_stats /*[3], may be NULL*/);
+
 /* Measured uncontended atomic throughput of HIP device `device` (the
  * north star's "atomic throughput against MI355X peak": no vendor figure
  * exists for integer atomics, so the peak is measured in-harness,
