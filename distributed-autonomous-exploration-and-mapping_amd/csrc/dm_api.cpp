@@ -23,7 +23,8 @@
 
 // Wait for all four streams; nothing of this handle is in flight afterwards.
 hipError_t dm_sync_all(dm_grid* g) {
-  for (hipStream_t s : {g->stream, g->fe_stream, g->pass_stream, g->big_stream}) {
+  const hipStream_t streams[] = {g->stream, g->fe_stream, g->pass_stream, g->big_stream};
+  for (hipStream_t s : streams) {
     if (!s) continue;
     const hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
@@ -101,9 +102,9 @@ int grow_integrate(dm_grid* g, int32_t S, int32_t N) {
     const int64_t bc = std::max<int64_t>(blocks, g->blk_cap);
     int rc = 0;
     for (auto& w : g->iw) {
-      if (!rc) rc = dev_alloc(&w.beams, nbc, "beams");
-      if (!rc) rc = dev_alloc(&w.blk_hist, bc * 1024, "per-block tile histograms");
-      if (!rc) rc = dev_alloc(&w.blk_n, bc, "per-block histogram sizes");
+      if (!rc) rc = w.beams.alloc(nbc, "beams");
+      if (!rc) rc = w.blk_hist.alloc(bc * 1024, "per-block tile histograms");
+      if (!rc) rc = w.blk_n.alloc(bc, "per-block histogram sizes");
     }
     if (rc) { g->beams_cap = g->blk_cap = 0; return rc; }
     g->beams_cap = nbc;
@@ -112,7 +113,7 @@ int grow_integrate(dm_grid* g, int32_t S, int32_t N) {
   const int64_t segs = nb * per_beam;
   if (segs > g->segs_cap) {
     for (auto& w : g->iw) {
-      int rc = dev_alloc(&w.pieces, segs, "ray pieces");
+      int rc = w.pieces.alloc(segs, "ray pieces");
       if (rc) { g->segs_cap = 0; return rc; }
     }
     g->segs_cap = segs;
@@ -123,8 +124,8 @@ int grow_integrate(dm_grid* g, int32_t S, int32_t N) {
   if (act > g->act_cap) {
     int rc = 0;
     for (auto& w : g->iw) {
-      if (!rc) rc = dev_alloc(&w.act_raw, act * kShards, "first-touch lists");
-      if (!rc) rc = dev_alloc(&w.litems, act, "light work items");
+      if (!rc) rc = w.act_raw.alloc(act * kShards, "first-touch lists");
+      if (!rc) rc = w.litems.alloc(act, "light work items");
     }
     if (rc) { g->act_cap = 0; return rc; }
     g->act_cap = act;
@@ -137,26 +138,25 @@ int grow_integrate(dm_grid* g, int32_t S, int32_t N) {
   const int64_t hitems = segs / chunk + segs / (chunk + 1) + 2;
   if (hitems > g->hitem_cap) {
     for (auto& w : g->iw) {
-      int rc = dev_alloc(&w.hitems, hitems, "heavy work items");
+      int rc = w.hitems.alloc(hitems, "heavy work items");
       if (rc) { g->hitem_cap = 0; return rc; }
     }
     g->hitem_cap = hitems;
   }
   if (heavy > g->heavy_cap) {
     for (auto& w : g->iw) {
-      int rc = dev_alloc(&w.heavy_list, heavy, "heavy tiles");
-      if (!rc) rc = dev_alloc(&w.slabs, heavy * 2 * DM_TILE * DM_TILE, "heavy-tile slabs");
-      if (!rc) rc = dev_alloc(&w.heavy_done, heavy, "heavy-tile item tickets");
+      int rc = w.heavy_list.alloc(heavy, "heavy tiles");
+      if (!rc) rc = w.slabs.alloc(heavy * 2 * DM_TILE * DM_TILE, "heavy-tile slabs");
+      if (!rc) rc = w.heavy_done.alloc(heavy, "heavy-tile item tickets");
       if (rc) { g->heavy_cap = 0; return rc; }
       DM_HIP(hipMemset(w.slabs, 0, sizeof(uint32_t) * (size_t)(heavy * 2 * DM_TILE * DM_TILE)));
       DM_HIP(hipMemset(w.heavy_done, 0, sizeof(int32_t) * (size_t)heavy));
     }
     g->heavy_cap = heavy;
   }
-  if (2 * (int64_t)N > g->trig_cap) {
-    int rc = dev_alloc(&g->trig, 2 * (int64_t)N, "trig table");
+  if (2 * (int64_t)N > g->trig.size()) {
+    int rc = g->trig.alloc(2 * (int64_t)N, "trig table");
     if (rc) return rc;
-    g->trig_cap = 2 * (int64_t)N;
     g->trig_n = -1;
   }
   return DM_OK;
@@ -185,14 +185,14 @@ int ensure_trig(dm_grid* g, int32_t N, float amin, float inc) {
 // sort may be asked to order (band slot_cap, merge m_cap).
 int dm_grow_bucket_sort(dm_grid* g, int64_t n) {
   if (n <= g->bs_cap) return DM_OK;
-  int rc = dev_alloc(&g->bs_key, n, "row-sort keys");
-  if (!rc) rc = dev_alloc(&g->bs_key2, n, "row-sort keys");
-  if (!rc) rc = dev_alloc(&g->bs_idx, n, "row-sort indices");
-  if (!rc) rc = dev_alloc(&g->bs_idx2, n, "row-sort indices");
+  int rc = g->bs_key.alloc(n, "row-sort keys");
+  if (!rc) rc = g->bs_key2.alloc(n, "row-sort keys");
+  if (!rc) rc = g->bs_idx.alloc(n, "row-sort indices");
+  if (!rc) rc = g->bs_idx2.alloc(n, "row-sort indices");
   if (!rc && g->rs_rows < g->H) {  // rows of the whole map (merges sort over H rows)
-    rc = dev_alloc(&g->rs_cnt, g->H, "row-sort counters");
-    if (!rc) rc = dev_alloc(&g->rs_off, g->H + 1, "row-sort offsets");
-    if (!rc) rc = dev_alloc(&g->rs_status, g->H / 8192 + 2, "row-sort workgroup totals");
+    rc = g->rs_cnt.alloc(g->H, "row-sort counters");
+    if (!rc) rc = g->rs_off.alloc(g->H + 1, "row-sort offsets");
+    if (!rc) rc = g->rs_status.alloc(g->H / 8192 + 2, "row-sort workgroup totals");
     if (!rc) {
       DM_HIP(hipMemset(g->rs_cnt, 0, sizeof(int32_t) * (size_t)g->H));
       g->rs_rows = g->H;
@@ -209,23 +209,20 @@ int grow_slots(dm_grid* g, int64_t need) {
   int64_t cap = std::max<int64_t>(need, 2 * g->slot_cap);
   if (cap < (1 << 16)) cap = 1 << 16;
   cap = ceil_div(cap, kShards) * kShards;  // kShards equal regions (k_frontier_tile)
-  int rc = dev_alloc(&g->slot_label, cap, "slot labels");
+  int rc = g->slot_label.alloc(cap, "slot labels");
   for (auto& f : g->fw)
-    if (!rc) rc = dev_alloc(&f.slot_parent, cap, "slot parents");
+    if (!rc) rc = f.slot_parent.alloc(cap, "slot parents");
   g->slot_parent = g->fw[g->fparity].slot_parent;
-  if (!rc) rc = dev_alloc(&g->slot_root, cap, "slot roots");
-  if (!rc) rc = dev_alloc(&g->slot_own, 3 * cap, "slot sums");
-  if (!rc) rc = dev_alloc(&g->slot_acc, 3 * cap, "slot totals");
-  if (!rc) rc = dev_alloc(&g->clusters, 4 * cap, "clusters");
-  for (int sl = 0; sl <= dm_grid::kRbSlots && !rc; ++sl) {  // one per readback slot
-    dm_cluster* base = g->rb[sl].out_clu ? g->rb[sl].out_clu - kRbRecords : nullptr;
-    rc = dev_alloc(&base, cap + kRbRecords, "sorted clusters");
-    g->rb[sl].out_clu = base ? base + kRbRecords : nullptr;
-  }
+  if (!rc) rc = g->slot_root.alloc(cap, "slot roots");
+  if (!rc) rc = g->slot_own.alloc(3 * cap, "slot sums");
+  if (!rc) rc = g->slot_acc.alloc(3 * cap, "slot totals");
+  if (!rc) rc = g->clusters.alloc(4 * cap, "clusters");
+  for (int sl = 0; sl <= dm_grid::kRbSlots && !rc; ++sl)  // one per readback slot
+    rc = g->rb[sl].out_clu.alloc(cap, "sorted clusters");
   ++g->rb_gen;
-  g->out_clu = g->rb[g->rb_head].out_clu;
-  if (!rc) rc = dev_alloc(&g->slot_k, cap, "slot cluster index");
-  if (!rc) rc = dev_alloc(&g->rank_of, cap, "cluster sorted position");
+  g->out_clu = g->rb[g->rb_head].out_clu.records();
+  if (!rc) rc = g->slot_k.alloc(cap, "slot cluster index");
+  if (!rc) rc = g->rank_of.alloc(cap, "cluster sorted position");
   if (!rc) rc = dm_grow_bucket_sort(g, cap);
   if (rc) return rc;
   g->slot_cap = cap;
@@ -235,27 +232,12 @@ int grow_slots(dm_grid* g, int64_t need) {
 // Grow readback slot `slot`'s mapped buffer (no pass of that slot in flight).
 int grow_host_out(dm_grid* g, int slot, int64_t need) {
   dm_grid::RbSlot& r = g->rb[slot];
-  if (need <= r.h_out_cap) return DM_OK;
-  int64_t cap = std::max<int64_t>(need, 2 * r.h_out_cap);
-  if (r.h_out) (void)hipHostFree(r.h_out - kRbHostRecords);
-  r.h_out = nullptr;
-  r.h_out_cap = 0;
+  if (need <= r.h_out.capacity()) return DM_OK;
   // mapped + coherent: k_rank_sort writes the readback header and the first
   // records (32 bytes each) straight into it over PCIe (no D2H copy command
   // per call)
-  dm_raw_record* base = nullptr;
-  DM_HIP(hipHostMalloc((void**)&base, sizeof(dm_raw_record) * (size_t)(cap + kRbHostRecords),
-                       hipHostMallocMapped | hipHostMallocCoherent));
-  dm_raw_record* dbase = nullptr;
-  const hipError_t e = hipHostGetDevicePointer((void**)&dbase, base, 0);
-  if (e != hipSuccess) {
-    (void)hipHostFree(base);
-    return dm_hip_check(e, "hipHostGetDevicePointer(cluster readback)");
-  }
-  r.h_out = base + kRbHostRecords;
-  r.h_out_dev = dbase + kRbHostRecords;
-  r.h_out_cap = cap;
-  return DM_OK;
+  return r.h_out.alloc(std::max<int64_t>(need, 2 * r.h_out.capacity()), hipHostMallocMapped | hipHostMallocCoherent,
+                       "cluster readback");
 }
 
 // Copy nw sorted cluster records to `out`: the first `have` are already in
@@ -310,12 +292,12 @@ void note_goal_source(dm_grid* g, int slot, int kind, int64_t n) {
 
 int grow_merge(dm_grid* g, int64_t n) {
   if (n <= g->m_cap) return DM_OK;
-  int rc = dev_alloc(&g->m_parent, n, "merge parents");
-  if (!rc) rc = dev_alloc(&g->m_label, n, "merge labels");
-  if (!rc) rc = dev_alloc(&g->m_acc, 3 * n, "merge sums");
-  if (!rc) rc = dev_alloc(&g->m_clu, 4 * n, "merged clusters");
+  int rc = g->m_parent.alloc(n, "merge parents");
+  if (!rc) rc = g->m_label.alloc(n, "merge labels");
+  if (!rc) rc = g->m_acc.alloc(3 * n, "merge sums");
+  if (!rc) rc = g->m_clu.alloc(4 * n, "merged clusters");
   for (int sl = 0; sl <= dm_grid::kRbSlots && !rc; ++sl)
-    rc = dev_alloc(&g->rb[sl].m_out, n, "merged clusters (sorted)");
+    rc = g->rb[sl].m_out.alloc(n, "merged clusters (sorted)");
   ++g->rb_gen;
   if (!rc) rc = dm_grow_bucket_sort(g, n);
   if (rc) { g->m_cap = 0; return rc; }
@@ -496,20 +478,20 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
     dm_destroy(g);
     return code;
   };
-  if ((rc = dev_alloc(&g->L, cells, "log-odds"))) return fail(rc);
-  if ((rc = dev_alloc(&g->state, cells, "state"))) return fail(rc);
+  if ((rc = g->L.alloc(cells, "log-odds"))) return fail(rc);
+  if ((rc = g->state.alloc(cells, "state"))) return fail(rc);
   for (auto& w : g->iw) {
-    if ((rc = dev_alloc(&w.tile_count, g->NT, "tile counts"))) return fail(rc);
-    if ((rc = dev_alloc(&w.tile_cur, g->NT, "tile bin cursors"))) return fail(rc);
-    if ((rc = dev_alloc(&w.cnt, CNT_N, "integrate counters"))) return fail(rc);
-    if ((rc = dev_alloc(&w.sh, kShards * kShardWords, "integrate shard counters"))) return fail(rc);
+    if ((rc = w.tile_count.alloc(g->NT, "tile counts"))) return fail(rc);
+    if ((rc = w.tile_cur.alloc(g->NT, "tile bin cursors"))) return fail(rc);
+    if ((rc = w.cnt.alloc(CNT_N, "integrate counters"))) return fail(rc);
+    if ((rc = w.sh.alloc(kShards * kShardWords, "integrate shard counters"))) return fail(rc);
     DM_HIP(hipMemset(w.cnt, 0, sizeof(unsigned long long) * CNT_N));
     DM_HIP(hipMemset(w.sh, 0, sizeof(unsigned long long) * kShards * kShardWords));
   }
-  if ((rc = dev_alloc(&g->tile_free, g->NT, "tile free counts"))) return fail(rc);
-  if ((rc = dev_alloc(&g->fmask, g->NT * DM_TILE * 16, "tile free / unknown bit rows"))) return fail(rc);
-  if ((rc = dev_alloc(&g->fedge, g->NT * 4, "tile unknown edge words"))) return fail(rc);
-  if ((rc = dev_alloc(&g->tile_seen, g->NT, "tile seen flags"))) return fail(rc);
+  if ((rc = g->tile_free.alloc(g->NT, "tile free counts"))) return fail(rc);
+  if ((rc = g->fmask.alloc(g->NT * DM_TILE * 16, "tile free / unknown bit rows"))) return fail(rc);
+  if ((rc = g->fedge.alloc(g->NT * 4, "tile unknown edge words"))) return fail(rc);
+  if ((rc = g->tile_seen.alloc(g->NT, "tile seen flags"))) return fail(rc);
   // The run-time switches (read once, here): DM_SPARSE_PIECES (0: no
   // sparse work items), DM_FMASK=on|off (fmask maintenance forced either way),
   // DM_FRONTIER_CACHE=on|off (the label cache of the workgroup tile kernel),
@@ -536,36 +518,36 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   if (const char* mb = getenv("DM_MATCH_GLOBAL_BATCH"))
     g->mg_batch = std::min<int64_t>(std::max<int64_t>(1, atoll(mb)), dm_grid::kMgExhaustiveBatch);
   for (auto& f : g->fw) {
-    e = hipEventCreateWithFlags(&f.ev_split, hipEventDisableTiming | hipEventDisableSystemFence);
+    e = hipEventCreateWithFlags(f.ev_split.put(), hipEventDisableTiming | hipEventDisableSystemFence);
     if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
-    if ((rc = dev_alloc(&f.cnt, CNT_N, "frontier counters"))) return fail(rc);
+    if ((rc = f.cnt.alloc(CNT_N, "frontier counters"))) return fail(rc);
     DM_HIP(hipMemset(f.cnt, 0, sizeof(unsigned long long) * CNT_N));
-    if ((rc = dev_alloc(&f.fsh, kShards * kShardWords, "frontier shard counters"))) return fail(rc);
+    if ((rc = f.fsh.alloc(kShards * kShardWords, "frontier shard counters"))) return fail(rc);
     DM_HIP(hipMemset(f.fsh, 0, sizeof(unsigned long long) * kShards * kShardWords));
-    if ((rc = dev_alloc(&f.big_tiles, g->NT, "frontier big tiles"))) return fail(rc);
-    if ((rc = dev_alloc(&f.fbits, g->NT * DM_TILE, "frontier bit rows"))) return fail(rc);
-    if ((rc = dev_alloc(&f.edge_slot, 2 * g->W, "edge slots"))) return fail(rc);
+    if ((rc = f.big_tiles.alloc(g->NT, "frontier big tiles"))) return fail(rc);
+    if ((rc = f.fbits.alloc(g->NT * DM_TILE, "frontier bit rows"))) return fail(rc);
+    if ((rc = f.edge_slot.alloc(2 * g->W, "edge slots"))) return fail(rc);
   }
-  if ((rc = dev_alloc(&g->fl_n, 48, "frontier list lengths"))) return fail(rc);
+  if ((rc = g->fl_n.alloc(48, "frontier list lengths"))) return fail(rc);
   for (int i = 0; i < 2; ++i) {
-    if ((rc = dev_alloc(&g->flist[i], g->NT, "frontier tile list"))) return fail(rc);
-    if ((rc = dev_alloc(&g->flist_n[i], 16, "frontier tile list length"))) return fail(rc);
+    if ((rc = g->flist[i].alloc(g->NT, "frontier tile list"))) return fail(rc);
+    if ((rc = g->flist_n[i].alloc(16, "frontier tile list length"))) return fail(rc);
     DM_HIP(hipMemset(g->flist_n[i], 0, sizeof(unsigned long long) * 16));
   }
   g->ftiles = g->flist[0];
   g->ftiles_n = g->flist_n[0];
   DM_HIP(hipMemset(g->fl_n, 0, sizeof(unsigned long long) * 48));
-  if ((rc = dev_alloc(&g->bits_flag, 16, "bit-row hand-off word"))) return fail(rc);
+  if ((rc = g->bits_flag.alloc(16, "bit-row hand-off word"))) return fail(rc);
   DM_HIP(hipMemset(g->bits_flag, 0, sizeof(unsigned long long) * 16));
-  if ((rc = dev_alloc(&g->fe_flag, 16, "front-end completion words"))) return fail(rc);
+  if ((rc = g->fe_flag.alloc(16, "front-end completion words"))) return fail(rc);
   DM_HIP(hipMemset(g->fe_flag, 0, sizeof(unsigned long long) * 16));
-  if ((rc = dev_alloc(&g->border, g->NT * 256, "frontier borders"))) return fail(rc);
+  if ((rc = g->border.alloc(g->NT * 256, "frontier borders"))) return fail(rc);
   // [0, 4 NT): the dense passes' pair hand-off words; [4 NT, 8 NT): the
   // sparse passes' per-edge stamps (dm_frontier.hip, EDGE tile kernels)
-  if ((rc = dev_alloc(&g->rel, 8 * g->NT, "tile-edge hand-off words"))) return fail(rc);
+  if ((rc = g->rel.alloc(8 * g->NT, "tile-edge hand-off words"))) return fail(rc);
   DM_HIP(hipMemset(g->rel, 0, sizeof(unsigned long long) * 8 * (size_t)g->NT));
-  if ((rc = dev_alloc(&g->edge_label, 2 * g->W, "edge labels"))) return fail(rc);
-  if ((rc = dev_alloc(&g->halo, 2 * g->W, "halo rows"))) return fail(rc);
+  if ((rc = g->edge_label.alloc(2 * g->W, "edge labels"))) return fail(rc);
+  if ((rc = g->halo.alloc(2 * g->W, "halo rows"))) return fail(rc);
   // slot arrays sized for the map up front (a pass that overflows them has
   // no result and must be rerun): kSlotsPerTile tile-local components per
   // tile, ~276 B each (C3: 72 MB; a 65536^2 map: 1.2 GB of its 288 GB).  A
@@ -576,19 +558,12 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   for (int sl = 0; sl <= dm_grid::kRbSlots; ++sl)
     if ((rc = grow_host_out(g, sl, 1 << 14))) return fail(rc);
   dm_select_slot(g, 0);
-  e = hipHostMalloc((void**)&g->h_cnt, sizeof(unsigned long long) * (2 * CNT_N + 1), hipHostMallocDefault);
-  if (e != hipSuccess) return fail(dm_hip_check(e, "hipHostMalloc(counters)"));
-  e = hipHostMalloc((void**)&g->h_sh, sizeof(unsigned long long) * 2 * kShards * kShardWords,
-                    hipHostMallocDefault);
-  if (e != hipSuccess) return fail(dm_hip_check(e, "hipHostMalloc(shard counters)"));
-  if ((rc = dev_alloc(&g->m_cnt, 4, "merge counters"))) return fail(rc);
-  e = hipHostMalloc((void**)&g->h_mcnt, sizeof(unsigned long long) * 4, hipHostMallocDefault);
-  if (e != hipSuccess) return fail(dm_hip_check(e, "hipHostMalloc(merge counters)"));
-  e = hipHostMalloc((void**)&g->h_hint, sizeof(unsigned long long) * 16, hipHostMallocMapped | hipHostMallocCoherent);
-  if (e != hipSuccess) return fail(dm_hip_check(e, "hipHostMalloc(work hint)"));
+  if ((rc = g->h_cnt.alloc(2 * CNT_N + 1, hipHostMallocDefault, "counters"))) return fail(rc);
+  if ((rc = g->h_sh.alloc(2 * kShards * kShardWords, hipHostMallocDefault, "shard counters"))) return fail(rc);
+  if ((rc = g->m_cnt.alloc(4, "merge counters"))) return fail(rc);
+  if ((rc = g->h_mcnt.alloc(4, hipHostMallocDefault, "merge counters"))) return fail(rc);
+  if ((rc = g->h_hint.alloc(16, hipHostMallocMapped | hipHostMallocCoherent, "work hint"))) return fail(rc);
   memset(g->h_hint, 0, sizeof(unsigned long long) * 16);
-  e = hipHostGetDevicePointer((void**)&g->d_hint, g->h_hint, 0);
-  if (e != hipSuccess) return fail(dm_hip_check(e, "hipHostGetDevicePointer(work hint)"));
   e = hipDeviceGetAttribute(&g->n_cu, hipDeviceAttributeMultiprocessorCount, device);
   if (e != hipSuccess) return fail(dm_hip_check(e, "hipDeviceGetAttribute(multiprocessor count)"));
   // Stream priorities: the map chain (accumulation, frontier bit rows) and
@@ -601,27 +576,27 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   e = hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, prio_hi);
   if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate"));
   g->own_stream = true;
-  e = hipStreamCreateWithPriority(&g->fe_stream, hipStreamNonBlocking, prio_lo);
+  e = hipStreamCreateWithPriority(g->fe_stream.put(), hipStreamNonBlocking, prio_lo);
   if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate(front-end)"));
-  e = hipStreamCreateWithPriority(&g->pass_stream, hipStreamNonBlocking, prio_hi);
+  e = hipStreamCreateWithPriority(g->pass_stream.put(), hipStreamNonBlocking, prio_hi);
   if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate(pass)"));
-  e = hipStreamCreateWithPriority(&g->big_stream, hipStreamNonBlocking, prio_hi);
+  e = hipStreamCreateWithPriority(g->big_stream.put(), hipStreamNonBlocking, prio_hi);
   if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate(big)"));
   // ev_fe / ev_free only order the two streams on the device: no system-
   // scope fence (no host-visible cache writeback at every step).  The host
   // waits on a readback slot's event and then reads mapped host memory:
   // default fences.
-  for (hipEvent_t* ev : {&g->ev_fe, &g->ev_bits[0], &g->ev_bits[1], &g->iw[0].ev_free, &g->iw[1].ev_free,
+  for (DevEvent* ev : {&g->ev_fe, &g->ev_bits[0], &g->ev_bits[1], &g->iw[0].ev_free, &g->iw[1].ev_free,
                          &g->ev_bigfork, &g->ev_big, &g->flist_ev[0], &g->flist_ev[1]}) {
-    e = hipEventCreateWithFlags(ev, hipEventDisableTiming | hipEventDisableSystemFence);
+    e = hipEventCreateWithFlags(ev->put(), hipEventDisableTiming | hipEventDisableSystemFence);
     if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
   }
   for (auto& r : g->rb) {
-    e = hipEventCreateWithFlags(&r.ev, hipEventDisableTiming);
+    e = hipEventCreateWithFlags(r.ev.put(), hipEventDisableTiming);
     if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
   }
-  for (hipEvent_t& ev : g->ev_pose) {  // host waits on these before reusing a staging buffer
-    e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  for (DevEvent& ev : g->ev_pose) {  // host waits on these before reusing a staging buffer
+    e = hipEventCreateWithFlags(ev.put(), hipEventDisableTiming);
     if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
   }
 
@@ -636,66 +611,6 @@ int dm_destroy(dm_grid* g) {
   (void)hipSetDevice(g->device);
   (void)dm_sync_all(g);
   for (auto& t : g->pending) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
-  for (hipEvent_t ev : {g->ev_fe, g->ev_bits[0], g->ev_bits[1], g->iw[0].ev_free, g->iw[1].ev_free,
-                        g->ev_bigfork, g->ev_big, g->flist_ev[0], g->flist_ev[1]})
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto& r : g->rb) {
-    if (r.ev) (void)hipEventDestroy(r.ev);
-    if (r.out_clu) (void)hipFree(r.out_clu - kRbRecords);
-    if (r.h_out) (void)hipHostFree(r.h_out - kRbHostRecords);
-    dev_free(r.m_out);
-  }
-  if (g->fe_stream) (void)hipStreamDestroy(g->fe_stream);
-  if (g->pass_stream) (void)hipStreamDestroy(g->pass_stream);
-  if (g->big_stream) (void)hipStreamDestroy(g->big_stream);
-  for (auto& f : g->fw) {
-    if (f.ev_split) (void)hipEventDestroy(f.ev_split);
-    dev_free(f.cnt); dev_free(f.fsh); dev_free(f.big_tiles); dev_free(f.fbits);
-    dev_free(f.edge_slot); dev_free(f.slot_parent);
-  }
-  dev_free(g->fl_n); dev_free(g->bits_flag); dev_free(g->fcache);
-  for (int i = 0; i < 2; ++i) { dev_free(g->flist[i]); dev_free(g->flist_n[i]); }
-  for (int b = 0; b < 2; ++b) { dev_free(g->goal_k[b]); dev_free(g->goal_i[b]); }
-  dev_free(g->goal_io); dev_free(g->goal_idx);
-  dev_free(g->plan_cost); dev_free(g->plan_trav); dev_free(g->plan_travs); dev_free(g->plan_list[0]);
-  dev_free(g->plan_list[1]); dev_free(g->plan_stamp); dev_free(g->plan_len); dev_free(g->plan_stat);
-  dev_free(g->plan_src); dev_free(g->plan_qxy); dev_free(g->plan_qcost); dev_free(g->plan_qcell);
-  dev_free(g->plan_path);
-  if (g->h_plan) (void)hipHostFree(g->h_plan);
-  dev_free(g->match_V); dev_free(g->match_kern); dev_free(g->match_tiles); dev_free(g->match_pose4);
-  dev_free(g->match_trig); dev_free(g->match_ranges); dev_free(g->match_q); dev_free(g->match_vol);
-  dev_free(g->match_out);
-  dev_free(g->mg_pool); dev_free(g->mg_ptiles); dev_free(g->mg_bound); dev_free(g->mg_hist); dev_free(g->mg_ctl);
-  dev_free(g->mg_list); dev_free(g->mg_nused); dev_free(g->mg_cand); dev_free(g->mg_best);
-  if (g->h_mg) (void)hipHostFree(g->h_mg);
-  dev_free(g->gain_xy); dev_free(g->gain_cell); dev_free(g->gain_out); dev_free(g->gain_skip);
-  dev_free(g->gain_memo_cell); dev_free(g->gain_memo_gain); dev_free(g->gain_claimed);
-  dev_free(g->fuse_stats);
-  for (auto& w : g->iw) {
-    dev_free(w.pieces); dev_free(w.hitems); dev_free(w.litems); dev_free(w.heavy_list); dev_free(w.slabs);
-    dev_free(w.heavy_done); dev_free(w.tile_count); dev_free(w.tile_cur); dev_free(w.cnt); dev_free(w.sh);
-    dev_free(w.ranges);
-    dev_free(w.beams); dev_free(w.blk_hist); dev_free(w.blk_n); dev_free(w.act_raw);
-  }
-  dev_free(g->L); dev_free(g->state); dev_free(g->fmask); dev_free(g->fedge); dev_free(g->tile_seen);
-  dev_free(g->tile_free);
-  dev_free(g->trig);
-  dev_free(g->bs_key); dev_free(g->bs_key2); dev_free(g->bs_idx); dev_free(g->bs_idx2);
-  dev_free(g->rs_cnt); dev_free(g->rs_off); dev_free(g->rs_status);
-  dev_free(g->border); dev_free(g->rel); dev_free(g->slot_label); dev_free(g->slot_root);
-  dev_free(g->slot_own); dev_free(g->slot_acc); dev_free(g->clusters); dev_free(g->cell_slot);
-  dev_free(g->edge_label); dev_free(g->mask); dev_free(g->labels);
-  dev_free(g->halo); dev_free(g->fe_flag);
-  dev_free(g->slot_k); dev_free(g->rank_of); dev_free(g->m_parent); dev_free(g->m_label);
-  dev_free(g->m_acc); dev_free(g->m_clu); dev_free(g->m_cnt);
-  if (g->h_mcnt) (void)hipHostFree(g->h_mcnt);
-  if (g->h_hint) (void)hipHostFree(g->h_hint);
-  if (g->h_cnt) (void)hipHostFree(g->h_cnt);
-  if (g->h_sh) (void)hipHostFree(g->h_sh);
-  for (int i = 0; i < dm_grid::kPoseRing; ++i) {
-    if (g->h_pose4[i]) (void)hipHostFree(g->h_pose4[i]);
-    if (g->ev_pose[i]) (void)hipEventDestroy(g->ev_pose[i]);
-  }
   if (g->stream && g->own_stream) (void)hipStreamDestroy(g->stream);
   delete g;
   return DM_OK;
@@ -756,31 +671,22 @@ int enqueue_host_integrate(dm_grid* g, int32_t S, const double* poses, int32_t N
     DM_HIP(dm_mark_ws_free(g));
     DM_HIP(hipStreamWaitEvent(fs, w.free_wait ? w.free_wait : w.ev_free, 0));
   }
-  if (nb > w.ranges_cap || (int64_t)S * 4 > g->h_pose_cap) {
+  // both staging buffers of the ring have one size: the last one's says it
+  const bool grow_poses = (int64_t)S * 4 > g->h_pose4[dm_grid::kPoseRing - 1].size();
+  if (nb > w.ranges.size() || grow_poses) {
     // the buffers may still feed an in-flight call
     DM_HIP(dm_sync_all(g));
   }
-  if (nb > w.ranges_cap) {
-    if ((rc = dev_alloc(&w.ranges, nb, "ranges"))) return rc;
-    w.ranges_cap = nb;
-  }
-  if ((int64_t)S * 4 > g->h_pose_cap) {
-    for (int i = 0; i < dm_grid::kPoseRing; ++i) {
-      if (g->h_pose4[i]) (void)hipHostFree(g->h_pose4[i]);
-      g->h_pose4[i] = nullptr;
-    }
-    g->h_pose_cap = 0;
-    for (int i = 0; i < dm_grid::kPoseRing; ++i) {
-      // Coherent: k_beam_prep reads the slot through its device address and
-      // the slot is rewritten every kPoseRing calls at the same address, so
-      // the GPU must not keep it in L2 (non-coherent host memory may be
-      // cached there; the other mapped buffers the device reads are
-      // Mapped | Coherent too)
-      DM_HIP(hipHostMalloc((void**)&g->h_pose4[i], sizeof(double) * 4 * (size_t)std::max(S, 1),
-                           hipHostMallocMapped | hipHostMallocCoherent));
-      DM_HIP(hipHostGetDevicePointer((void**)&g->h_pose4_dev[i], g->h_pose4[i], 0));
-    }
-    g->h_pose_cap = (int64_t)std::max(S, 1) * 4;
+  if ((rc = w.ranges.ensure(nb, "ranges"))) return rc;
+  if (grow_poses) {
+    for (auto& h : g->h_pose4) h.reset();
+    // Coherent: k_beam_prep reads the slot through its device address and
+    // the slot is rewritten every kPoseRing calls at the same address, so
+    // the GPU must not keep it in L2 (non-coherent host memory may be
+    // cached there; the other mapped buffers the device reads are
+    // Mapped | Coherent too)
+    for (auto& h : g->h_pose4)
+      if ((rc = h.alloc((int64_t)S * 4, hipHostMallocMapped | hipHostMallocCoherent, "pose staging"))) return rc;
   }
   const int slot = g->pose_head;
   g->pose_head = (g->pose_head + 1) % dm_grid::kPoseRing;
@@ -800,7 +706,7 @@ int enqueue_host_integrate(dm_grid* g, int32_t S, const double* poses, int32_t N
   // accumulation's CUs and adds a compute -> copy-engine hand-off)
   if (nb > 0)
     DM_HIP(hipMemcpyAsync(w.ranges, ranges, sizeof(float) * (size_t)nb, hipMemcpyHostToDevice, fs));
-  if ((rc = dm_launch_integrate(g, S, g->h_pose4_dev[slot], N, w.ranges, g->trig))) return rc;
+  if ((rc = dm_launch_integrate(g, S, g->h_pose4[slot].dev(), N, w.ranges, g->trig))) return rc;
   // after the front-end (which read the staging buffer) and so after the
   // ranges copy: two calls later this event proves the caller's ranges
   // buffer has been read too (dm.h: reusable after the second call that follows)
@@ -937,16 +843,13 @@ int dm_set_state(dm_grid* g, const int8_t* in) {
   if (rc || (rc = use_device(g))) return rc;
   if (!in) return dm_set_error(DM_ERR_INVALID_ARG, "in is NULL");
   const int64_t cells = g->W * g->R;
-  int8_t* d = nullptr;
-  if ((rc = dev_alloc(&d, cells, "state staging"))) return rc;
+  DevBuf<int8_t> d;
+  if ((rc = d.alloc(cells, "state staging"))) return rc;
   DM_HIP(hipStreamSynchronize(g->stream));
   hipError_t e = hipMemcpy(d, in, (size_t)cells, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    rc = dm_launch_set_state(g, d);
-    if (!rc) e = hipStreamSynchronize(g->stream);
-  }
-  (void)hipFree(d);
   if (e != hipSuccess) return dm_hip_check(e, "dm_set_state");
+  rc = dm_launch_set_state(g, d);
+  if (!rc && (e = hipStreamSynchronize(g->stream)) != hipSuccess) return dm_hip_check(e, "dm_set_state");
   g->frontier_valid = false;
   ++g->integrate_seq;
   return rc;
@@ -959,10 +862,10 @@ int dm_frontiers(dm_grid* g, uint8_t* mask, int64_t* labels, dm_cluster* out, in
   if (rc || (rc = use_device(g))) return rc;
   if (cap < 0 || (cap > 0 && !out)) return dm_set_error(DM_ERR_INVALID_ARG, "bad cluster buffer");
   const int64_t cells = g->W * g->R;
-  if (mask && !g->mask && (rc = dev_alloc(&g->mask, cells, "dense mask"))) return rc;
+  if (mask && !g->mask && (rc = g->mask.alloc(cells, "dense mask"))) return rc;
   if (labels && !g->cell_slot) {
-    if ((rc = dev_alloc(&g->cell_slot, cells, "dense cell slots"))) return rc;
-    if ((rc = dev_alloc(&g->labels, cells, "dense labels"))) return rc;
+    if ((rc = g->cell_slot.alloc(cells, "dense cell slots"))) return rc;
+    if ((rc = g->labels.alloc(cells, "dense labels"))) return rc;
   }
   // its own readback slot: asynchronous passes may be in flight (this pass
   // runs after them in stream order and sees the map as it is now)
@@ -1392,17 +1295,14 @@ int dm_ld06_to_scans(dm_grid* g, int32_t S, const dm_ld06_point* points, const i
   if (np < 0 || offsets[0] != 0) return dm_set_error(DM_ERR_SHAPE, "offsets must start at 0");
   for (int32_t s = 0; s < S; ++s)
     if (offsets[s + 1] < offsets[s]) return dm_set_error(DM_ERR_SHAPE, "offsets must be non-decreasing");
-  dm_ld06_point* dp = nullptr;
-  int64_t* doff = nullptr;
-  float* dr = nullptr;
-  float* di = nullptr;
-  auto cleanup = [&]() { dev_free(dp); dev_free(doff); dev_free(dr); dev_free(di); };
-  if ((rc = dev_alloc(&dp, np, "ld06 points")) || (rc = dev_alloc(&doff, S + 1, "ld06 offsets")) ||
-      (rc = dev_alloc(&dr, (int64_t)S * N, "ld06 ranges")) ||
-      (intensities_out && (rc = dev_alloc(&di, (int64_t)S * N, "ld06 intensities")))) {
-    cleanup();
+  DevBuf<dm_ld06_point> dp;
+  DevBuf<int64_t> doff;
+  DevBuf<float> dr, di;
+  if ((rc = dp.alloc(np, "ld06 points")) || (rc = doff.alloc(S + 1, "ld06 offsets")) ||
+      (rc = dr.alloc((int64_t)S * N, "ld06 ranges")) ||
+      (intensities_out && (rc = di.alloc((int64_t)S * N, "ld06 intensities"))))
     return rc;
-  }
+  // no early return from here on: what was enqueued is waited for before the buffers go
   hipError_t e = hipMemcpyAsync(dp, points, sizeof(dm_ld06_point) * (size_t)np, hipMemcpyHostToDevice, g->stream);
   if (e == hipSuccess)
     e = hipMemcpyAsync(doff, offsets, sizeof(int64_t) * (size_t)(S + 1), hipMemcpyHostToDevice, g->stream);
@@ -1412,7 +1312,6 @@ int dm_ld06_to_scans(dm_grid* g, int32_t S, const dm_ld06_point* points, const i
   if (e == hipSuccess && !rc && intensities_out)
     e = hipMemcpyAsync(intensities_out, di, sizeof(float) * (size_t)S * N, hipMemcpyDeviceToHost, g->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-  cleanup();
   if (e != hipSuccess) return dm_hip_check(e, "dm_ld06_to_scans");
   return rc;
 }
@@ -1536,15 +1435,13 @@ int dm_map_image(dm_grid* g, uint8_t* out) {
   if (rc || (rc = use_device(g))) return rc;
   if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
   const int64_t cells = g->W * g->R;
-  uint8_t* d = nullptr;
-  if ((rc = dev_alloc(&d, cells, "image"))) return rc;
-  rc = dm_launch_map_image(g, d);
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(out, d, (size_t)cells, hipMemcpyDeviceToHost, g->stream);
-  if (!rc && e == hipSuccess) e = hipStreamSynchronize(g->stream);
-  (void)hipFree(d);
+  DevBuf<uint8_t> d;
+  if ((rc = d.alloc(cells, "image"))) return rc;
+  if ((rc = dm_launch_map_image(g, d))) return rc;
+  hipError_t e = hipMemcpyAsync(out, d, (size_t)cells, hipMemcpyDeviceToHost, g->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
   if (e != hipSuccess) return dm_hip_check(e, "dm_map_image");
-  return rc;
+  return DM_OK;
 }
 
 }  // extern "C"

@@ -1996,13 +1996,11 @@ int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool spli
   // the label cache, with the first pass that launches the workgroup kernel
   // (every pass does); without the memory the passes run uncached
   if (g->fcache_mode == 1 && !g->fcache) {
-    void* p = nullptr;
-    const size_t bytes = sizeof(uint64_t) * kFcWords * (size_t)g->NT;
-    if (hipMalloc(&p, bytes) == hipSuccess && hipMemsetAsync(p, 0, bytes, g->stream) == hipSuccess) {
-      g->fcache = (uint64_t*)p;
-    } else {
+    const int64_t words = kFcWords * g->NT;
+    if (g->fcache.alloc(words, "label cache") != DM_OK ||
+        hipMemsetAsync(g->fcache, 0, sizeof(uint64_t) * (size_t)words, g->stream) != hipSuccess) {
       (void)hipGetLastError();
-      if (p) (void)hipFree(p);
+      g->fcache.reset();
       g->fcache_mode = 0;
     }
   }

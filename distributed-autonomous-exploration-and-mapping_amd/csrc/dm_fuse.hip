@@ -191,7 +191,7 @@ int fuse_device(dm_grid* g, const dm_fuse_source& src, const T* d_src, double tx
                 int32_t mode, uint64_t* out_stats) {
   const double c = cos(yaw), s = sin(yaw);
   // three device words kept in the handle: no allocation (and no hipFree, which waits for the whole device) per call
-  int rc = g->fuse_stats ? DM_OK : dev_alloc(&g->fuse_stats, 3, "fuse stats");
+  int rc = g->fuse_stats.ensure(3, "fuse stats");
   if (rc) return rc;
   unsigned long long* d_stats = g->fuse_stats;
   unsigned long long h_stats[3] = {0ull, 0ull, 0ull};
@@ -249,12 +249,11 @@ int fuse_host(dm_grid* g, const dm_fuse_source* src, const T* h_src, double tx, 
   if ((rc = check_transform(tx, ty, yaw, mode))) return rc;
   if ((rc = use_device(g))) return rc;
   const int64_t cells = src->width * src->height;
-  T* d = nullptr;
-  if ((rc = dev_alloc(&d, cells, "fuse source staging"))) return rc;
+  DevBuf<T> d;
+  if ((rc = d.alloc(cells, "fuse source staging"))) return rc;
   const hipError_t e = hipMemcpy(d, h_src, sizeof(T) * (size_t)cells, hipMemcpyHostToDevice);
-  rc = e == hipSuccess ? fuse_device(g, *src, d, tx, ty, yaw, mode, out_stats) : dm_hip_check(e, "fuse source upload");
-  (void)hipFree(d);
-  return rc;
+  if (e != hipSuccess) return dm_hip_check(e, "fuse source upload");
+  return fuse_device(g, *src, d.get(), tx, ty, yaw, mode, out_stats);
 }
 
 

@@ -175,19 +175,12 @@ static int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, 
                                const uint32_t* d_gain = nullptr, int64_t min_gain = 0) {
   const int64_t nch = (K + kGoalN - 1) / kGoalN;
   const int64_t need = (int64_t)R * std::max<int64_t>(nch, 1) * T;
-  if (need > g->goal_cap) {
+  if (need > g->goal_i[1].size()) {  // the four lists have one size; goal_i[1] is allocated last
+    for (int b = 0; b < 2; ++b) { g->goal_k[b].reset(); g->goal_i[b].reset(); }
     for (int b = 0; b < 2; ++b) {
-      if (g->goal_k[b]) (void)hipFree(g->goal_k[b]);
-      if (g->goal_i[b]) (void)hipFree(g->goal_i[b]);
-      g->goal_k[b] = nullptr;
-      g->goal_i[b] = nullptr;
+      int rc = g->goal_k[b].alloc(need, "goal keys");
+      if (rc || (rc = g->goal_i[b].alloc(need, "goal indices"))) return rc;
     }
-    g->goal_cap = 0;
-    for (int b = 0; b < 2; ++b) {
-      DM_HIP(hipMalloc((void**)&g->goal_k[b], sizeof(unsigned long long) * (size_t)need));
-      DM_HIP(hipMalloc((void**)&g->goal_i[b], sizeof(uint32_t) * (size_t)need));
-    }
-    g->goal_cap = need;
   }
   int cur = 0;
   KernelTimer t;
@@ -293,7 +286,7 @@ static int dm_plan_run_field(dm_grid* g, const int64_t* cells, int32_t n, const 
     for (int64_t k = 0; k < nb; ++k, ++done) {
       hipLaunchKernelGGL(k_plan_relax, dim3(grid), dim3(kThreads), 0, s, g->plan_cost, g->plan_travs, g->W, g->H,
                          g->TX, g->TY, max_cost, g->plan_list[done & 1], g->plan_list[(done + 1) & 1], g->plan_len,
-                         g->plan_stamp, (uint32_t)done, g->plan_stat, g->h_plan_dev);
+                         g->plan_stamp, (uint32_t)done, g->plan_stat, g->h_plan.dev());
       DM_HIP(hipGetLastError());
     }
     dm_timer_end(g, &t);
@@ -457,34 +450,28 @@ static int ensure_plan(dm_grid* g) {
   if (g->plan_cost) return DM_OK;  // allocated last: everything else is there too
   int rc = DM_OK;
   if (!g->h_plan) {
-    hipError_t e = hipHostMalloc((void**)&g->h_plan, sizeof(unsigned long long) * 16,
-                                 hipHostMallocMapped | hipHostMallocCoherent);
-    if (e != hipSuccess) {
-      g->h_plan = nullptr;
-      return dm_hip_check(e, "hipHostMalloc(plan rounds)");
-    }
+    if ((rc = g->h_plan.alloc(16, hipHostMallocMapped | hipHostMallocCoherent, "plan rounds"))) return rc;
     memset(g->h_plan, 0, sizeof(unsigned long long) * 16);
-    DM_HIP(hipHostGetDevicePointer((void**)&g->h_plan_dev, g->h_plan, 0));
   }
   const int64_t rows = g->NT * DM_TILE;
-  if ((rc = dev_alloc(&g->plan_trav, rows, "traversable bit rows"))) return rc;
-  if ((rc = dev_alloc(&g->plan_travs, rows, "traversable bit rows with sources"))) return rc;
-  if ((rc = dev_alloc(&g->plan_list[0], g->NT, "plan tile list"))) return rc;
-  if ((rc = dev_alloc(&g->plan_list[1], g->NT, "plan tile list"))) return rc;
-  if ((rc = dev_alloc(&g->plan_stamp, g->NT, "plan tile stamps"))) return rc;
-  if ((rc = dev_alloc(&g->plan_len, 4, "plan list lengths"))) return rc;
-  if ((rc = dev_alloc(&g->plan_stat, 8, "plan statistics"))) return rc;
+  if ((rc = g->plan_trav.alloc(rows, "traversable bit rows"))) return rc;
+  if ((rc = g->plan_travs.alloc(rows, "traversable bit rows with sources"))) return rc;
+  if ((rc = g->plan_list[0].alloc(g->NT, "plan tile list"))) return rc;
+  if ((rc = g->plan_list[1].alloc(g->NT, "plan tile list"))) return rc;
+  if ((rc = g->plan_stamp.alloc(g->NT, "plan tile stamps"))) return rc;
+  if ((rc = g->plan_len.alloc(4, "plan list lengths"))) return rc;
+  if ((rc = g->plan_stat.alloc(8, "plan statistics"))) return rc;
   DM_HIP(hipMemset(g->plan_stat, 0, sizeof(unsigned long long) * 8));
-  if ((rc = dev_alloc(&g->plan_src, 256, "plan sources"))) return rc;
-  return dev_alloc(&g->plan_cost, g->W * g->H, "distance field");
+  if ((rc = g->plan_src.alloc(256, "plan sources"))) return rc;
+  return g->plan_cost.alloc(g->W * g->H, "distance field");
 }
 
 static int grow_plan_query(dm_grid* g, int64_t n) {
   if (n <= g->plan_qcap) return DM_OK;
   g->plan_qcap = 0;
-  int rc = dev_alloc(&g->plan_qxy, 2 * n, "plan query targets");
-  if (!rc) rc = dev_alloc(&g->plan_qcost, n, "plan query costs");
-  if (!rc) rc = dev_alloc(&g->plan_qcell, n, "plan query cells");
+  int rc = g->plan_qxy.alloc(2 * n, "plan query targets");
+  if (!rc) rc = g->plan_qcost.alloc(n, "plan query costs");
+  if (!rc) rc = g->plan_qcell.alloc(n, "plan query cells");
   if (!rc) g->plan_qcap = n;
   return rc;
 }
@@ -547,16 +534,13 @@ int dm_plan_traversable(dm_grid* g, int32_t inflate_cells, uint8_t* out) {
   if ((rc = plan_check_inflate(inflate_cells)) || (rc = ensure_plan(g))) return rc;
   DM_HIP(dm_join_pass_stream(g));
   const int64_t cells = g->W * g->H;
-  uint8_t* d = nullptr;
-  if ((rc = dev_alloc(&d, cells, "traversable image"))) return rc;
-  rc = dm_plan_launch_travers(g, inflate_cells);
-  if (!rc) rc = dm_plan_launch_expand(g, d);
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(out, d, (size_t)cells, hipMemcpyDeviceToHost, g->stream);
-  if (!rc && e == hipSuccess) e = hipStreamSynchronize(g->stream);
-  (void)hipFree(d);
+  DevBuf<uint8_t> d;
+  if ((rc = d.alloc(cells, "traversable image"))) return rc;
+  if ((rc = dm_plan_launch_travers(g, inflate_cells)) || (rc = dm_plan_launch_expand(g, d))) return rc;
+  hipError_t e = hipMemcpyAsync(out, d, (size_t)cells, hipMemcpyDeviceToHost, g->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
   if (e != hipSuccess) return dm_hip_check(e, "dm_plan_traversable");
-  return rc;
+  return DM_OK;
 }
 
 int dm_plan_field(dm_grid* g, const double* sources_xy, int32_t n_sources, int32_t inflate_cells,
@@ -612,11 +596,7 @@ int dm_plan_path(dm_grid* g, double tx, double ty, int32_t snap_cells, int64_t* 
   if ((rc = grow_plan_query(g, 1))) return rc;
   // a path visits no cell twice: H * W entries hold any
   const int64_t dcap = std::max<int64_t>(1, std::min<int64_t>(cap, g->W * g->H));
-  if (dcap > g->plan_pathcap) {
-    g->plan_pathcap = 0;
-    if ((rc = dev_alloc(&g->plan_path, dcap, "path cells"))) return rc;
-    g->plan_pathcap = dcap;
-  }
+  if ((rc = g->plan_path.ensure(dcap, "path cells"))) return rc;
   const double txy[2] = {tx, ty};
   DM_HIP(hipMemcpyAsync(g->plan_qxy, txy, sizeof txy, hipMemcpyHostToDevice, g->stream));
   if ((rc = dm_plan_launch_query(g, g->plan_qxy, 2, 1, snap_cells, g->plan_qcost, g->plan_qcell))) return rc;
@@ -645,12 +625,12 @@ int dm_plan_path(dm_grid* g, double tx, double ty, int32_t snap_cells, int64_t* 
 static int grow_gain(dm_grid* g, int64_t n) {
   if (n <= g->gain_cap) return DM_OK;
   g->gain_cap = 0;
-  int rc = dev_alloc(&g->gain_xy, 2 * n, "view points");
-  if (!rc) rc = dev_alloc(&g->gain_cell, n, "view cells");
-  if (!rc) rc = dev_alloc(&g->gain_out, n, "view gains");
-  if (!rc) rc = dev_alloc(&g->gain_skip, n, "view skip flags");
-  if (!rc) rc = dev_alloc(&g->gain_memo_cell, n, "gain memo cells");
-  if (!rc) rc = dev_alloc(&g->gain_memo_gain, n, "gain memo gains");
+  int rc = g->gain_xy.alloc(2 * n, "view points");
+  if (!rc) rc = g->gain_cell.alloc(n, "view cells");
+  if (!rc) rc = g->gain_out.alloc(n, "view gains");
+  if (!rc) rc = g->gain_skip.alloc(n, "view skip flags");
+  if (!rc) rc = g->gain_memo_cell.alloc(n, "gain memo cells");
+  if (!rc) rc = g->gain_memo_gain.alloc(n, "gain memo gains");
   if (!rc) g->gain_cap = n;
   return rc;
 }
@@ -687,7 +667,7 @@ static int64_t claimed_words(const dm_grid* g) { return g->H * ((g->W + 31) / 32
 
 static int ensure_claimed(dm_grid* g) {
   if (g->gain_claimed) return DM_OK;
-  return dev_alloc(&g->gain_claimed, claimed_words(g), "claimed set");
+  return g->gain_claimed.alloc(claimed_words(g), "claimed set");
 }
 
 // n points (metres) to g->gain_xy and their cells to g->gain_cell.
@@ -728,15 +708,12 @@ int dm_gain_claimed(dm_grid* g, uint8_t* out) {
     return dm_set_error(DM_ERR_STATE, "dm_gain_claimed: no claimed set (call dm_gain_views_joint or "
                         "dm_assign_goals_coord first)");
   const int64_t cells = g->W * g->H;
-  uint8_t* d = nullptr;
-  if ((rc = dev_alloc(&d, cells, "claimed image"))) return rc;
-  rc = dm_gain_launch_expand(g, d);
-  hipError_t e = hipSuccess;
-  if (!rc) e = hipMemcpyAsync(out, d, (size_t)cells, hipMemcpyDeviceToHost, g->stream);
-  if (!rc && e == hipSuccess) e = hipStreamSynchronize(g->stream);
-  (void)hipFree(d);
+  DevBuf<uint8_t> d;
+  if ((rc = d.alloc(cells, "claimed image")) || (rc = dm_gain_launch_expand(g, d))) return rc;
+  hipError_t e = hipMemcpyAsync(out, d, (size_t)cells, hipMemcpyDeviceToHost, g->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
   if (e != hipSuccess) return dm_hip_check(e, "dm_gain_claimed");
-  return rc;
+  return DM_OK;
 }
 
 // ---- goal assignment: dm_assign_goals (Euclidean distance to the centroid)
@@ -767,7 +744,7 @@ static int goal_source(const dm_grid* g, const dm_cluster** recs, int64_t* K) {
     return dm_set_error(DM_ERR_INVALID_ARG, "no collected frontier result on the device (call dm_frontiers, "
                                             "dm_frontiers_end or dm_merge_bands first; a later pass may have "
                                             "reused its readback slot)");
-  *recs = g->goal_kind == 1 ? g->rb[s].out_clu : g->rb[s].m_out;
+  *recs = g->goal_kind == 1 ? g->rb[s].out_clu.records() : g->rb[s].m_out.get();
   *K = g->goal_n;
   return DM_OK;
 }
@@ -804,9 +781,9 @@ int dm_assign_goals(dm_grid* g, const double* robots_xy, int32_t n_robots, int64
   int64_t K = 0;
   if ((rc = goal_source(g, &recs, &K))) return rc;
   if (n_robots == 0) return DM_OK;
-  if (!g->goal_io) {
-    DM_HIP(hipMalloc((void**)&g->goal_io, sizeof(double) * 4 * 256));
-    DM_HIP(hipMalloc((void**)&g->goal_idx, sizeof(int64_t) * 256));
+  if (!g->goal_io) {  // allocated last: goal_idx is there too
+    if ((rc = g->goal_idx.alloc(256, "goal indices out")) || (rc = g->goal_io.alloc(4 * 256, "goal robots and centroids")))
+      return rc;
   }
   DM_HIP(dm_join_pass_stream(g));
   const int32_t R = n_robots, T = n_robots;

@@ -1656,7 +1656,7 @@ int dm_launch_integrate(dm_grid* g, int32_t S, const double* d_pose4, int32_t N,
                      dim3(kQuarter), 0,
                      g->stream, ge, make_apply(g), w.hitems, (int)CNT_ITEMS, w.litems, (int)CNT_LITEMS,
                      (int)CNT_SITEMS, w.pieces, w.tile_count, g->tile_free, w.slabs, g->L, g->state, w.cnt, w.sh, vec_ok,
-                     w.heavy_list, w.heavy_done, g->ftiles, g->ftiles_n, g->d_hint, g->fe_flag + kHaltWord,
+                     w.heavy_list, w.heavy_done, g->ftiles, g->ftiles_n, g->h_hint.dev(), g->fe_flag + kHaltWord,
                      g->tile_seen);
   dm_timer_end(g, &t);
   DM_HIP(hipGetLastError());

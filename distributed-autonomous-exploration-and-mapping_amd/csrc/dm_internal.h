@@ -22,6 +22,7 @@
 
 #include "../../include/dm.h"
 
+#include "dm_buf.h"
 #include "dm_ray.h"
 
 
@@ -167,6 +168,10 @@ struct KernelTimer {
 
 struct dm_shard_set;  // dm_sharded.cpp
 
+// Every allocation, event and stream of a handle is a member that owns it
+// (dm_buf.h) and goes with the handle: dm_destroy has no list of them.  The
+// raw pointers and hipEvent_t's left in it are views of one of those owners,
+// each said so where it is declared.
 struct dm_grid {
   dm_params p;
   // non-null: a sharded parent (dm_create_sharded); every call runs on its
@@ -188,11 +193,11 @@ struct dm_grid {
   // other.  Two alternating streams (so call k+1's front-end could start
   // before call k's finished) left the full step where it was and slowed
   // C1 / C5: DESIGN.md §3.3.3, §5.7.
-  hipStream_t fe_stream = nullptr;
-  hipEvent_t ev_fe = nullptr;
+  DevStream fe_stream;
+  DevEvent ev_fe;
   // front-end completion word (k_fe_signal / k_fe_gate, dm_integrate.hip):
   // the sequence number of the last call whose front-end finished
-  unsigned long long* fe_flag = nullptr;  // [kSigWord] / [kGateWord] hand-off counts, [kHaltWord] sticky error
+  DevBuf<unsigned long long> fe_flag;  // [kSigWord] / [kGateWord] hand-off counts, [kHaltWord] sticky error
   // DM_FAULT_GATE=1 (read at dm_create; fault-injection tests only): the
   // front-end gate waits for a sequence number that never comes, ~10 us
   bool fault_gate = false;
@@ -200,21 +205,19 @@ struct dm_grid {
   // stream waits for it); it also frees the integrate workspaces whose
   // accumulations are ahead of it (dm_mark_ws_free), so the next front-end
   // using them can start right away instead of after the whole pass
-  hipEvent_t ev_bits[2] = {nullptr, nullptr};
+  DevEvent ev_bits[2];
   uint64_t integrate_seq = 0;  // map changes so far
   // Asynchronous passes (dm_frontiers_begin / dm_merge_bands_begin) use a
   // ring of kRbSlots readback slots, so a pass can be started before the
   // previous one was collected.  Each slot owns what its _end reads: the
   // mapped readback buffer (header + first records), the device sorted
   // records, the event marking the pass's end.  out_clu / h_out / h_out_dev /
-  // h_out_cap / m_out below point at the slot in use (dm_select_slot).
+  // h_out_cap / m_out below are views of the slot in use (dm_select_slot).
   struct RbSlot {
-    dm_cluster* out_clu = nullptr;    // device sorted band records (after kRbRecords header records)
-    dm_raw_record* h_out = nullptr;      // mapped host readback (after the header), 32-byte records
-    dm_raw_record* h_out_dev = nullptr;  // its device address
-    int64_t h_out_cap = 0;
-    dm_cluster* m_out = nullptr;      // device sorted merged records
-    hipEvent_t ev = nullptr;
+    Headed<DevBuf<dm_cluster>, kRbRecords> out_clu;         // device sorted band records behind the header
+    Headed<HostBuf<dm_raw_record>, kRbHostRecords> h_out;   // mapped host readback behind the header, 32-byte records
+    DevBuf<dm_cluster> m_out;      // device sorted merged records
+    DevEvent ev;
     int kind = 0;                     // pending pass: 0 none, 1 band frontiers, 2 band merge
     uint64_t seq = 0;                 // integrate_seq at the pass's start
     uint64_t gen = 0;                 // rb_gen at the pass's start
@@ -239,11 +242,11 @@ struct dm_grid {
   int64_t TX = 0, TY = 0, NT = 0;
   int32_t nmax = 0;  // max ray length (cells) bound
 
-  float* L = nullptr;
-  int8_t* state = nullptr;
+  DevBuf<float> L;
+  DevBuf<int8_t> state;
   // free cells per tile (bits 0..29) | kTileListed: the tile is on the
   // persistent frontier tile list (ftiles / ftiles_n below)
-  int32_t* tile_free = nullptr;
+  DevBuf<int32_t> tile_free;
   // [NT][64 rows][16] per tile: byte j of row y holds the free bits of cells
   // 4j..4j+3 (low nibble) and their unknown bits (high nibble); out-of-grid
   // cells are neither.  Kept in step with `state` by every kernel that writes
@@ -255,12 +258,12 @@ struct dm_grid {
   // latency-bound either way and the per-call update would only add a
   // kernel.  fmask_valid: the records match the state (a full rebuild,
   // k_recount, precedes switching on otherwise).
-  uint8_t* fmask = nullptr;
+  DevBuf<uint8_t> fmask;
   // fedge: per tile 4 words, the unknown bits of its column 0, column 63
   // (bit = row), row 0 and row 63 (bit = column), written with fmask by the
   // same kernels: a pass reads its neighbours' edges from these 32 B instead
   // of from their 1 KB records (one byte of every 16 B row: all 8 lines)
-  uint64_t* fedge = nullptr;
+  DevBuf<uint64_t> fedge;
   // tile_seen: 0 while every cell of the tile is still unknown (since the
   // last bulk write: k_recount sets it from the state), 1 once an
   // integrate item applied the tile (k_tile_accum).  The frontier bit rows
@@ -281,7 +284,7 @@ struct dm_grid {
   // does not read the old state byte: it recomputes it from the old L, for
   // its "state changed" count and to store the byte only where it differs.  A
   // writer that stores a state not derived from L would break both.
-  uint8_t* tile_seen = nullptr;
+  DevBuf<uint8_t> tile_seen;
   bool fmask_on = false, fmask_valid = false;
   int fmask_mode = 0;  // DM_FMASK=auto|on|off (read at dm_create; tests / A/B): 0 auto, 1 on, 2 off
   // Label cache of the workgroup tile kernel: [NT][kFcWords], one entry per
@@ -290,17 +293,22 @@ struct dm_grid {
   // leave it alone).  Allocated zero-filled with the first frontier pass;
   // fcache_mode: DM_FRONTIER_CACHE=on|off (read at dm_create; tests / A/B),
   // 1 on, 0 off -- also after a failed allocation, which is no error.
-  uint64_t* fcache = nullptr;
+  DevBuf<uint64_t> fcache;
   int fcache_mode = 1;
   // hits and misses of the last collected pass (readback header), or of the
   // last export pass (fc_collected false: read from its shards on demand)
   unsigned long long fc_hits = 0, fc_misses = 0;
   bool fc_collected = true;
-  unsigned long long* cnt = nullptr;    // CNT_N device counters (frontier fields)
-  unsigned long long* h_cnt = nullptr;  // pinned mirror: [CNT_N] frontier counters, [CNT_N] integrate counters
-  unsigned long long* fsh = nullptr;    // [kShards][kShardWords] frontier shards
-  unsigned long long* h_sh = nullptr;   // pinned mirror of the last call's integrate shards, then fsh
+  unsigned long long* cnt = nullptr;    // CNT_N device counters (frontier fields): a view of fw[]
+  HostBuf<unsigned long long> h_cnt;  // pinned mirror: [CNT_N] frontier counters, [CNT_N] integrate counters
+  unsigned long long* fsh = nullptr;    // [kShards][kShardWords] frontier shards: a view of fw[]
+  HostBuf<unsigned long long> h_sh;   // pinned mirror of the last call's integrate shards, then fsh
 
+  // The capacities kept beside the buffers (these, slot_cap, bs_cap, rs_rows,
+  // m_cap, plan_qcap, gain_cap) are not one buffer's size, which the buffer
+  // knows (size()): each is a bound the kernels are told, or covers a group of
+  // arrays that grow together.  It is set only once every array of its group
+  // is allocated and is 0 after a failed growth.
   // integrate workspace capacities (the arrays are per set, IntWs)
   int64_t beams_cap = 0;
   int64_t blk_cap = 0;            // workgroups blk_hist / blk_n hold
@@ -313,48 +321,44 @@ struct dm_grid {
     // the front-end's own scratch (k_beam_prep -> k_plan / k_scatter): per
     // set, like everything it hands over: call k+1's front-end overlaps call
     // k's accumulation
-    Beam* beams = nullptr;          // [beams_cap]
-    int2* blk_hist = nullptr;       // [beam blocks][1024] k_beam_prep's (tile, pieces | hash slot << 16) histogram
-    int32_t* blk_n = nullptr;       // [beam blocks] its entries
-    int32_t* act_raw = nullptr;     // [kShards][act_cap] first-touch lists per shard
-    PackedPiece* pieces = nullptr;    // [segs_cap] ray pieces binned by tile
-    int4* hitems = nullptr;           // heavy work items {tile, first piece, pieces, heavy ordinal}
-    int4* litems = nullptr;           // light work items {tile, first piece, pieces, -1} [act_cap]
-    int32_t* heavy_list = nullptr;    // heavy ordinal -> tile
-    uint32_t* slabs = nullptr;        // [heavy][2][64*64] merged hit / miss counts
-    int32_t* heavy_done = nullptr;    // [heavy] items finished this call (the last one applies the slab)
-    int32_t* tile_count = nullptr;    // [NT] pieces per tile (zeroed again by the accumulation)
-    int32_t* tile_cur = nullptr;      // [NT] k_scatter's bin cursor per active tile (k_plan)
-    unsigned long long* cnt = nullptr;  // [CNT_N] the integrate counters (kIntegrateCounters)
-    unsigned long long* sh = nullptr;   // [kShards][kShardWords] integrate shards
+    DevBuf<Beam> beams;          // [beams_cap]
+    DevBuf<int2> blk_hist;       // [beam blocks][1024] k_beam_prep's (tile, pieces | hash slot << 16) histogram
+    DevBuf<int32_t> blk_n;       // [beam blocks] its entries
+    DevBuf<int32_t> act_raw;     // [kShards][act_cap] first-touch lists per shard
+    DevBuf<PackedPiece> pieces;    // [segs_cap] ray pieces binned by tile
+    DevBuf<int4> hitems;           // heavy work items {tile, first piece, pieces, heavy ordinal}
+    DevBuf<int4> litems;           // light work items {tile, first piece, pieces, -1} [act_cap]
+    DevBuf<int32_t> heavy_list;    // heavy ordinal -> tile
+    DevBuf<uint32_t> slabs;        // [heavy][2][64*64] merged hit / miss counts
+    DevBuf<int32_t> heavy_done;    // [heavy] items finished this call (the last one applies the slab)
+    DevBuf<int32_t> tile_count;    // [NT] pieces per tile (zeroed again by the accumulation)
+    DevBuf<int32_t> tile_cur;      // [NT] k_scatter's bin cursor per active tile (k_plan)
+    DevBuf<unsigned long long> cnt;  // [CNT_N] the integrate counters (kIntegrateCounters)
+    DevBuf<unsigned long long> sh;   // [kShards][kShardWords] integrate shards
     // device copy of the host ranges (dm_integrate / _async) of the calls
     // using this set, reused only when the set is (free_wait)
-    float* ranges = nullptr;
-    int64_t ranges_cap = 0;
+    DevBuf<float> ranges;
     // the next front-end using this set waits for free_wait: an event on
     // `stream` after the set's last accumulation, recorded lazily (at the next
     // frontier pass or integrate call) -- ev_free, or the readback-slot event
     // of an asynchronous frontier pass enqueued after that accumulation
     // (dm_frontiers_begin records one anyway: no extra marker)
-    hipEvent_t ev_free = nullptr;
-    hipEvent_t free_wait = nullptr;
+    DevEvent ev_free;
+    hipEvent_t free_wait = nullptr;  // a view: ev_free or a readback slot's ev
     bool free_owed = false;
   };
   // calls alternate between the two sets
   static constexpr int kIntSets = 2;
   IntWs iw[kIntSets];
   int iw_cur = 0;                // set of the last integrate call
-  double* trig = nullptr; int32_t trig_n = -1; float trig_amin = 0, trig_inc = 0;
-  int64_t trig_cap = 0;
+  DevBuf<double> trig; int32_t trig_n = -1; float trig_amin = 0, trig_inc = 0;
   // pinned, mapped (x, y, cos, sin) staging of host poses: a ring of two, each
   // reusable once the front-end that read it (k_beam_prep, through the device
   // address) is done (ev_pose), so a host-input call never waits for the
   // previous call (dm_integrate_async)
   static constexpr int kPoseRing = 2;
-  double* h_pose4[kPoseRing] = {nullptr, nullptr};
-  hipEvent_t ev_pose[kPoseRing] = {nullptr, nullptr};
-  double* h_pose4_dev[kPoseRing] = {nullptr, nullptr};  // their device addresses (mapped)
-  int64_t h_pose_cap = 0;
+  HostBuf<double> h_pose4[kPoseRing];
+  DevEvent ev_pose[kPoseRing];
   int pose_head = 0;
   int32_t last_S = 0, last_N = 0;
 
@@ -367,34 +371,34 @@ struct dm_grid {
   // previous pass must be done by then (busy: the event that pass recorded,
   // waited on by `stream` unless the host already saw it complete).
   struct FrWs {
-    unsigned long long* cnt = nullptr;  // [CNT_N]
-    unsigned long long* fsh = nullptr;  // [kShards][kShardWords]
-    int32_t* big_tiles = nullptr;       // [NT]
-    uint64_t* fbits = nullptr;          // [NT][64]
-    int32_t* edge_slot = nullptr;       // [2][W]
-    int32_t* slot_parent = nullptr;     // [slot_cap]
-    hipEvent_t busy = nullptr;          // the last pass's end (an alias of its readback event or ev_split)
-    hipEvent_t ev_split = nullptr;      // end of a split export pass on the pass stream (owned)
+    DevBuf<unsigned long long> cnt;  // [CNT_N]
+    DevBuf<unsigned long long> fsh;  // [kShards][kShardWords]
+    DevBuf<int32_t> big_tiles;       // [NT]
+    DevBuf<uint64_t> fbits;          // [NT][64]
+    DevBuf<int32_t> edge_slot;       // [2][W]
+    DevBuf<int32_t> slot_parent;     // [slot_cap]
+    hipEvent_t busy = nullptr;          // the last pass's end (a view of its readback event or ev_split)
+    DevEvent ev_split;                  // end of a split export pass on the pass stream
     bool busy_pending = false;
     uint64_t busy_pass = 0;             // fr_pass of that pass
   };
   FrWs fw[2];
   // the pass's list lengths (snapshots of *ftiles_n taken by k_frontier_bits),
   // a ring of three on separate lines: pass n uses fl_n[16 * (n % 3)]
-  unsigned long long* fl_n = nullptr;
+  DevBuf<unsigned long long> fl_n;
   // pass_stream (dm_set_overlap + dm_frontiers_begin): the labelling half of
   // a pass (tile kernels, resolve, sort) runs there, after the bit-row
   // kernel on `stream` (which alone reads the map), so the next
   // batch's map update overlaps it.  bits_flag / bits_seq: the bit rows'
   // hand-off (k_seq_signal on `stream`, k_seq_gate on pass_stream).
-  hipStream_t pass_stream = nullptr;
+  DevStream pass_stream;
   // big_stream: k_frontier_tile_big over the tiles k_frontier_bits listed as
   // too run-rich for a tile-wave, beside the wave kernel on the pass stream
   // (forked after the bit rows, joined before the resolve)
-  hipStream_t big_stream = nullptr;
-  hipEvent_t ev_bigfork = nullptr, ev_big = nullptr;
-  unsigned long long* bits_flag = nullptr;  // [kSigWord] / [kGateWord] counts, [kStampWord] pass stamp
-  hipEvent_t p_tail = nullptr;        // the last pass_stream pass's end (alias)
+  DevStream big_stream;
+  DevEvent ev_bigfork, ev_big;
+  DevBuf<unsigned long long> bits_flag;  // [kSigWord] / [kGateWord] counts, [kStampWord] pass stamp
+  hipEvent_t p_tail = nullptr;        // the last pass_stream pass's end (a view)
   bool p_pending = false;             // pass_stream work `stream` has not been ordered after
   uint64_t p_tail_pass = 0;
   // The persistent frontier tile list: every tile that has held a free cell
@@ -405,63 +409,65 @@ struct dm_grid {
   // bulk writes (dm_launch_recount: k_list_tiles).  Append-only between
   // rebuilds, so a pass reads the first *ftiles_n entries (its snapshot, taken
   // on the map stream after its batch) while later batches append behind them.
-  int32_t* ftiles = nullptr;               // [NT] the current list (one of flist)
-  unsigned long long* ftiles_n = nullptr;  // [16]: [0] its length
+  int32_t* ftiles = nullptr;               // [NT] the current list (a view of one of flist)
+  unsigned long long* ftiles_n = nullptr;  // [16]: [0] its length (a view of flist_n)
   // Two lists: the periodic rebuild in tile order (dm_launch_relist) writes
   // the other one and switches, so passes still labelling go on reading the
   // old one (nothing appends to it after the switch) and the map stream never
   // waits for them; flist_ev[i]: the pass stream's position when list i was
   // left, which a rebuild into list i waits for (long done 16 passes later)
-  int32_t* flist[2] = {nullptr, nullptr};
-  unsigned long long* flist_n[2] = {nullptr, nullptr};
-  hipEvent_t flist_ev[2] = {nullptr, nullptr};
+  DevBuf<int32_t> flist[2];
+  DevBuf<unsigned long long> flist_n[2];
+  DevEvent flist_ev[2];
   bool flist_ev_set[2] = {false, false};
   int flist_cur = 0;
   int relist_age = 0;     // passes since the list was last put in tile order
   int relist_period = 1;  // passes between those rebuilds: 1, 2, 4, ... up to kRelistPasses
                           // (a fresh map's list grows fastest in its first passes)
+  // big_tiles, fbits, slot_parent, edge_slot: views of fw[] (dm_select_fw)
   int32_t* big_tiles = nullptr;  // [NT] per list position: 1 = too many runs for a tile-wave (k_frontier_bits)
   uint64_t* fbits = nullptr;   // [NT][64] frontier bit rows of the listed tiles (k_frontier_bits)
-  int32_t* border = nullptr;   // [tile][4][64] slot ids of a tile's edges (published sides only)
+  DevBuf<int32_t> border;   // [tile][4][64] slot ids of a tile's edges (published sides only)
   // tile-edge hand-off words of k_frontier_tile, [4][NT]: horizontal (t, t+1),
   // vertical (t, t+TX), diagonal (t, t+TX+1), anti-diagonal (t, t+TX-1) pairs,
   // each (pass stamp << 2 | arrived sides); never reset (stamped)
-  unsigned long long* rel = nullptr;
+  DevBuf<unsigned long long> rel;
   int32_t fparity = 0;         // workspace set (fw) of the last frontier pass
   int64_t border_cap = 0;      // in tiles
   int64_t slot_cap = 0;
-  long long* slot_label = nullptr;
+  DevBuf<long long> slot_label;
   int32_t* slot_parent = nullptr;
-  int32_t* slot_root = nullptr;
-  long long* slot_own = nullptr;  // [slot][3] size, sum_x, sum_y
-  long long* slot_acc = nullptr;  // [slot][3]
-  long long* clusters = nullptr;  // [cap][4] label,size,sum_x,sum_y (unsorted)
-  int32_t* slot_k = nullptr;      // [slot_cap] root slot -> compact cluster index
-  int32_t* rank_of = nullptr;     // [slot_cap] compact cluster index -> sorted position
+  DevBuf<int32_t> slot_root;
+  DevBuf<long long> slot_own;  // [slot][3] size, sum_x, sum_y
+  DevBuf<long long> slot_acc;  // [slot][3]
+  DevBuf<long long> clusters;  // [cap][4] label,size,sum_x,sum_y (unsorted)
+  DevBuf<int32_t> slot_k;      // [slot_cap] root slot -> compact cluster index
+  DevBuf<int32_t> rank_of;     // [slot_cap] compact cluster index -> sorted position
+  // out_clu, h_out, h_out_dev, h_out_cap, m_out: views of rb[] (dm_select_slot)
   dm_cluster* out_clu = nullptr;  // [slot_cap] sorted cluster records (k_rank_sort)
   dm_raw_record* h_out = nullptr;  // pinned (mapped, coherent) readback: header + sorted 32-byte records
   dm_raw_record* h_out_dev = nullptr;  // its device address
   int64_t h_out_cap = 0;
-  int32_t* cell_slot = nullptr;   // dense [R][W] (only when labels requested)
+  DevBuf<int32_t> cell_slot;   // dense [R][W] (only when labels requested)
   int32_t* edge_slot = nullptr;   // [2][W] slots of the band's first / last row
-  long long* edge_label = nullptr;// [2][W]
-  uint8_t* mask = nullptr;        // dense [R][W] (only when mask requested)
-  long long* labels = nullptr;    // dense [R][W] int64 (only when requested)
-  int8_t* halo = nullptr;         // [2][W]: row before band, row after band
+  DevBuf<long long> edge_label;// [2][W]
+  DevBuf<uint8_t> mask;        // dense [R][W] (only when mask requested)
+  DevBuf<long long> labels;    // dense [R][W] int64 (only when requested)
+  DevBuf<int8_t> halo;         // [2][W]: row before band, row after band
   int has_halo[2] = {0, 0};
   bool frontier_valid = false;
 
   // large-K cluster sort (row buckets, dm_frontier.hip k_rs_*): used when
   // the last collected pass of its kind had more than sort_min clusters
-  unsigned long long* bs_key = nullptr;   // [bs_cap] sort keys (label - base), two buffers
-  unsigned long long* bs_key2 = nullptr;
-  int32_t* bs_idx = nullptr;      // [bs_cap] their record indices, two buffers
-  int32_t* bs_idx2 = nullptr;
+  DevBuf<unsigned long long> bs_key;   // [bs_cap] sort keys (label - base), two buffers
+  DevBuf<unsigned long long> bs_key2;
+  DevBuf<int32_t> bs_idx;      // [bs_cap] their record indices, two buffers
+  DevBuf<int32_t> bs_idx2;
   int64_t bs_cap = 0;
   // per-row counters (zero between sorts) and offsets
-  int32_t* rs_cnt = nullptr;      // [rs_rows]
-  int32_t* rs_off = nullptr;      // [rs_rows + 1]
-  unsigned long long* rs_status = nullptr;  // [rs_rows / 8192 + 2] k_rs_scan's workgroup totals + failure word
+  DevBuf<int32_t> rs_cnt;      // [rs_rows]
+  DevBuf<int32_t> rs_off;      // [rs_rows + 1]
+  DevBuf<unsigned long long> rs_status;  // [rs_rows / 8192 + 2] k_rs_scan's workgroup totals + failure word
   int64_t rs_rows = 0;
   int64_t sort_hint = 0, msort_hint = 0;  // clusters of the last band / merge readback
   int64_t ftile_hint = 0;                 // listed tiles of the last collected frontier pass
@@ -486,20 +492,19 @@ struct dm_grid {
 
   // cross-band merge workspace (dm_merge.hip), sized nranks * rec_cap
   int64_t m_cap = 0;
-  int32_t* m_parent = nullptr;
-  long long* m_label = nullptr;
-  long long* m_acc = nullptr;     // [m_cap][3] size, sum_x, sum_y
-  long long* m_clu = nullptr;     // [m_cap][4] merged records (unsorted)
+  DevBuf<int32_t> m_parent;
+  DevBuf<long long> m_label;
+  DevBuf<long long> m_acc;     // [m_cap][3] size, sum_x, sum_y
+  DevBuf<long long> m_clu;     // [m_cap][4] merged records (unsorted)
   dm_cluster* m_out = nullptr;    // [m_cap] merged records, sorted
-  unsigned long long* m_cnt = nullptr;    // [4] device: K, flags, sorted, max band K
-  unsigned long long* h_mcnt = nullptr;   // pinned mirror
+  DevBuf<unsigned long long> m_cnt;    // [4] device: K, flags, sorted, max band K
+  HostBuf<unsigned long long> h_mcnt;   // pinned mirror
   // [0] workgroups the last accumulation needed (dense items + sparse items
   // / 4), [1] its work items: written by k_tile_accum's workgroup 0 into
   // mapped host memory, read without a wait when the next call is enqueued
   // (a finished earlier call's value; 0 until one finished) to size the
   // accumulation and fmask grids to the work instead of to the capacity
-  unsigned long long* h_hint = nullptr;
-  unsigned long long* d_hint = nullptr;   // its device address
+  HostBuf<unsigned long long> h_hint;
 
   // goal selection (dm_goals.hip): the last collected sorted result on the
   // device (a readback slot's out_clu / m_out while that slot's epoch is
@@ -507,33 +512,30 @@ struct dm_grid {
   int goal_slot = -1, goal_kind = 0;  // kind 1: band frontiers (out_clu), 2: merge (m_out)
   uint64_t goal_epoch = 0, goal_gen = 0;
   int64_t goal_n = 0;
-  unsigned long long* goal_k[2] = {nullptr, nullptr};
-  uint32_t* goal_i[2] = {nullptr, nullptr};
-  int64_t goal_cap = 0;
-  double* goal_io = nullptr;          // [4 * 256] robots xy, then centroids xy
-  int64_t* goal_idx = nullptr;        // [256]
+  DevBuf<unsigned long long> goal_k[2];
+  DevBuf<uint32_t> goal_i[2];
+  DevBuf<double> goal_io;          // [4 * 256] robots xy, then centroids xy
+  DevBuf<int64_t> goal_idx;        // [256]
 
   // path planning (dm_plan.h; dm_plan_* and dm_assign_goals_path), allocated
   // on first use (ensure_plan).  The field is valid for the map version it was
   // computed on: integrate_seq + reset_seq, which every state writer bumps
   // (the integrate calls, dm_set_state, dm_set_logodds and through it dm_load:
   // integrate_seq; dm_reset: reset_seq).
-  uint32_t* plan_cost = nullptr;      // [H][W] row-major field
-  uint64_t* plan_trav = nullptr;      // [NT][64] traversable bit rows of the last inflation
-  uint64_t* plan_travs = nullptr;     // [NT][64] the same with the field's source cells set
-  int32_t* plan_list[2] = {nullptr, nullptr};  // [NT] active tiles of even / odd rounds
-  uint32_t* plan_stamp = nullptr;     // [NT] round + 2 of the list the tile was last put on
-  unsigned int* plan_len = nullptr;   // [3] list lengths (k_plan_relax)
-  unsigned long long* plan_stat = nullptr;    // [4] reached, traversable, rounds, tile relaxations; [4..5] path length, error
-  unsigned long long* h_plan = nullptr;       // mapped: the last round's list length, rounds, relaxations, traversable
-  unsigned long long* h_plan_dev = nullptr;   // its device address
-  int64_t* plan_src = nullptr;        // [256] source cells
-  double* plan_qxy = nullptr;         // [plan_qcap][2] query targets
-  uint32_t* plan_qcost = nullptr;     // [plan_qcap]
-  int64_t* plan_qcell = nullptr;      // [plan_qcap]
+  DevBuf<uint32_t> plan_cost;      // [H][W] row-major field
+  DevBuf<uint64_t> plan_trav;      // [NT][64] traversable bit rows of the last inflation
+  DevBuf<uint64_t> plan_travs;     // [NT][64] the same with the field's source cells set
+  DevBuf<int32_t> plan_list[2];  // [NT] active tiles of even / odd rounds
+  DevBuf<uint32_t> plan_stamp;     // [NT] round + 2 of the list the tile was last put on
+  DevBuf<unsigned int> plan_len;   // [3] list lengths (k_plan_relax)
+  DevBuf<unsigned long long> plan_stat;    // [4] reached, traversable, rounds, tile relaxations; [4..5] path length, error
+  HostBuf<unsigned long long> h_plan;       // mapped: the last round's list length, rounds, relaxations, traversable
+  DevBuf<int64_t> plan_src;        // [256] source cells
+  DevBuf<double> plan_qxy;         // [plan_qcap][2] query targets
+  DevBuf<uint32_t> plan_qcost;     // [plan_qcap]
+  DevBuf<int64_t> plan_qcell;      // [plan_qcap]
   int64_t plan_qcap = 0;
-  int64_t* plan_path = nullptr;       // [plan_pathcap] a path, target first
-  int64_t plan_pathcap = 0;
+  DevBuf<int64_t> plan_path;       // a path, target first
   bool plan_valid = false;
   uint64_t plan_version = 0;
   uint64_t reset_seq = 0;             // dm_reset calls so far
@@ -546,26 +548,20 @@ struct dm_grid {
   // on map version match_version, built for the tiles flagged in match_built
   // only: a call builds the tiles its search windows reach and are not built
   // yet, so the fine stage of a two-stage match reuses the coarse stage's.
-  uint8_t* match_V = nullptr;         // [H][W] row-major
-  uint8_t* match_kern = nullptr;      // [16 * 16 + 1] the smear table
-  int32_t* match_tiles = nullptr;     // [NT] tiles to build
+  DevBuf<uint8_t> match_V;         // [H][W] row-major
+  DevBuf<uint8_t> match_kern;      // [16 * 16 + 1] the smear table
+  DevBuf<int32_t> match_tiles;     // [NT] tiles to build
   std::vector<uint8_t> match_built;   // [NT] host flags
   std::vector<uint8_t> match_kern_h;  // the table match_V was built from
   int32_t match_r = -1;
   uint64_t match_version = 0;
   // per-call scratch, grown on demand
-  double* match_pose4 = nullptr;      // [S * A][4] x, y, cos, sin of every candidate yaw
-  int64_t match_pose_cap = 0;
-  double* match_trig = nullptr;       // [N][2] cos, sin of the beam angles
-  int64_t match_trig_cap = 0;
-  float* match_ranges = nullptr;      // [S][N]
-  int64_t match_ranges_cap = 0;
-  int2* match_q = nullptr;            // [S * A][N] fine coordinates
-  int64_t match_q_cap = 0;
-  uint32_t* match_vol = nullptr;      // [S][A][2 half + 1][2 half + 1] scores
-  int64_t match_vol_cap = 0;
-  int32_t* match_out = nullptr;       // [S][4] k, i, j, score, then [S] used beams
-  int64_t match_out_cap = 0;
+  DevBuf<double> match_pose4;      // [S * A][4] x, y, cos, sin of every candidate yaw
+  DevBuf<double> match_trig;       // [N][2] cos, sin of the beam angles
+  DevBuf<float> match_ranges;      // [S][N]
+  DevBuf<int2> match_q;            // [S * A][N] fine coordinates
+  DevBuf<uint32_t> match_vol;      // [S][A][2 half + 1][2 half + 1] scores
+  DevBuf<int32_t> match_out;       // [S][4] k, i, j, score, then [S] used beams
   uint64_t match_epoch = 0;           // bumped whenever match_built is dropped (new table or map version)
 
   // whole-window relocalisation (dm_match_global.h; dm_match_global), allocated
@@ -573,23 +569,19 @@ struct dm_grid {
   // size mg_pool_block, decimated by phase, built for the 64 x 64 tiles of
   // extended coordinates flagged in mg_pool_built; it is dropped with the
   // field (mg_pool_epoch != match_epoch) and on another block size.
-  uint8_t* mg_pool = nullptr;         // [B][B][EHB][EWB]
-  int64_t mg_pool_cap = 0;
-  int32_t* mg_ptiles = nullptr;       // pool tiles to build
-  int64_t mg_ptiles_cap = 0;
+  DevBuf<uint8_t> mg_pool;         // [B][B][EHB][EWB]
+  DevBuf<int32_t> mg_ptiles;       // pool tiles to build
   std::vector<uint8_t> mg_pool_built; // [PTY][PTX] host flags
   int32_t mg_pool_block = 0;
   uint64_t mg_pool_epoch = 0;
-  uint32_t* mg_bound = nullptr;       // [A][nby][nbx] bounds of one scan; 0 once refined
-  int64_t mg_bound_cap = 0;
-  uint32_t* mg_hist = nullptr;        // [kBins]
-  uint32_t* mg_ctl = nullptr;         // [C_WORDS] the round's count, bin and cap
-  int32_t* mg_list = nullptr;         // [mg_batch] the round's blocks
-  int4* mg_cand = nullptr;            // [kMgExhaustiveBatch >= mg_batch] dm_mg::Cand (16 bytes)
-  int4* mg_best = nullptr;            // dm_mg::Cand, the running best
-  int32_t* mg_nused = nullptr;        // the scan's used beams
-  uint32_t* h_mg = nullptr;           // mapped [8]: score, k, i, j, blocks of the round, used beams
-  uint32_t* h_mg_dev = nullptr;       // its device address
+  DevBuf<uint32_t> mg_bound;       // [A][nby][nbx] bounds of one scan; 0 once refined
+  DevBuf<uint32_t> mg_hist;        // [kBins]
+  DevBuf<uint32_t> mg_ctl;         // [C_WORDS] the round's count, bin and cap
+  DevBuf<int32_t> mg_list;         // [mg_batch] the round's blocks
+  DevBuf<int4> mg_cand;            // [kMgExhaustiveBatch >= mg_batch] dm_mg::Cand (16 bytes)
+  DevBuf<int4> mg_best;            // dm_mg::Cand, the running best
+  DevBuf<int32_t> mg_nused;        // the scan's used beams
+  HostBuf<uint32_t> h_mg;           // mapped [8]: score, k, i, j, blocks of the round, used beams
   // DM_MATCH_GLOBAL_BATCH (read at dm_create): the most blocks one round
   // refines; any value gives the same result
   int64_t mg_batch = 4096;
@@ -597,20 +589,20 @@ struct dm_grid {
 
   // information gain (dm_gain.h; dm_gain_views and dm_assign_goals_gain),
   // grown on demand
-  double* gain_xy = nullptr;          // [gain_cap][2] view points
-  int64_t* gain_cell = nullptr;       // [gain_cap] view cells
-  uint32_t* gain_out = nullptr;       // [gain_cap] gains (dm_assign_goals_gain: one robot's row)
-  uint8_t* gain_skip = nullptr;       // [gain_cap] views not to cast
-  int64_t* gain_memo_cell = nullptr;  // [gain_cap] per cluster: the cell of its last cast (one call)
-  uint32_t* gain_memo_gain = nullptr; // [gain_cap] and its gain
+  DevBuf<double> gain_xy;          // [gain_cap][2] view points
+  DevBuf<int64_t> gain_cell;       // [gain_cap] view cells
+  DevBuf<uint32_t> gain_out;       // [gain_cap] gains (dm_assign_goals_gain: one robot's row)
+  DevBuf<uint8_t> gain_skip;       // [gain_cap] views not to cast
+  DevBuf<int64_t> gain_memo_cell;  // [gain_cap] per cluster: the cell of its last cast (one call)
+  DevBuf<uint32_t> gain_memo_gain; // [gain_cap] and its gain
   int64_t gain_cap = 0;
   // the claimed set of dm_gain_views_joint / dm_assign_goals_coord: H rows of
   // ceil(W / 32) words, allocated by the first of the two calls
-  uint32_t* gain_claimed = nullptr;
+  DevBuf<uint32_t> gain_claimed;
   bool gain_claimed_valid = false;    // one of the two calls has run (dm_gain_claimed)
 
   // map fusion (dm_fuse.hip): covered, contributing, state-changed cells of the call, allocated on first use
-  unsigned long long* fuse_stats = nullptr;
+  DevBuf<unsigned long long> fuse_stats;
 
   // profiling
   bool profile = false;
@@ -623,10 +615,10 @@ struct dm_grid {
 inline void dm_select_slot(dm_grid* g, int slot) {
   const dm_grid::RbSlot& r = g->rb[slot];
   g->cur_slot = slot;
-  g->out_clu = r.out_clu;
-  g->h_out = r.h_out;
-  g->h_out_dev = r.h_out_dev;
-  g->h_out_cap = r.h_out_cap;
+  g->out_clu = r.out_clu.records();
+  g->h_out = r.h_out.records();
+  g->h_out_dev = r.h_out.records_dev();
+  g->h_out_cap = r.h_out.capacity();
   g->m_out = r.m_out;
 }
 
@@ -838,36 +830,6 @@ int dm_check_whole_map(const dm_grid* g, const char* what);
 // What a field, a response field or a claimed set was computed for: any map
 // change moves it.
 inline uint64_t dm_map_version(const dm_grid* g) { return g->integrate_seq + g->reset_seq; }
-
-template <class T>
-int dev_alloc(T** p, int64_t count, const char* what) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  if (count <= 0) count = 1;
-  hipError_t e = hipMalloc((void**)p, sizeof(T) * (size_t)count);
-  if (e != hipSuccess) {
-    *p = nullptr;
-    return dm_set_error(e == hipErrorOutOfMemory ? DM_ERR_OOM : DM_ERR_HIP,
-                        "hipMalloc(%s, %lld bytes): %s", what,
-                        (long long)(sizeof(T) * (size_t)count), hipGetErrorString(e));
-  }
-  return DM_OK;
-}
-
-template <class T>
-void dev_free(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-// grow-on-demand scratch: (re)allocate *p to n elements when *cap is smaller
-template <class T>
-int dev_grow(T** p, int64_t* cap, int64_t n, const char* what) {
-  if (n <= *cap) return DM_OK;
-  *cap = 0;
-  const int rc = dev_alloc(p, n, what);
-  if (!rc) *cap = n;
-  return rc;
-}
 
 // Kernel launch.
 #define DM_LAUNCH(kernel, grid, block, shmem, stream, ...) \

@@ -100,8 +100,8 @@ static int dm_mg_run_scan(dm_grid* g, const MgShape& sh, const double* d_pose4, 
                    uint64_t* stats) {
   using namespace dm_mg;
   hipStream_t s = g->stream;
-  Cand* best = (Cand*)g->mg_best;
-  Cand* cand = (Cand*)g->mg_cand;
+  Cand* best = (Cand*)g->mg_best.get();
+  Cand* cand = (Cand*)g->mg_cand.get();
   const int32_t N = sh.N, A = sh.A, nb = sh.nbx * sh.nby;
   const int64_t blocks = (int64_t)A * nb;
   KernelTimer t;
@@ -134,7 +134,7 @@ static int dm_mg_run_scan(dm_grid* g, const MgShape& sh, const double* d_pose4, 
       dm_timer_end(g, &t);
       dm_timer_begin(g, "mg_fold", &t);
       hipLaunchKernelGGL(k_mg_fold, dim3(1), dim3(kThreads), 0, s, cand, (const uint32_t*)nullptr, n, sh.k0, best,
-                         g->mg_nused, g->h_mg_dev);
+                         g->mg_nused, g->h_mg.dev());
       DM_HIP(hipGetLastError());
       dm_timer_end(g, &t);
       refined += (uint64_t)n;
@@ -172,7 +172,7 @@ static int dm_mg_run_scan(dm_grid* g, const MgShape& sh, const double* d_pose4, 
       dm_timer_end(g, &t);
       dm_timer_begin(g, "mg_fold", &t);
       hipLaunchKernelGGL(k_mg_fold, dim3(1), dim3(kThreads), 0, s, cand, g->mg_ctl, 0, sh.k0, best, g->mg_nused,
-                         g->h_mg_dev);
+                         g->h_mg.dev());
       DM_HIP(hipGetLastError());
       dm_timer_end(g, &t);
       DM_HIP(hipStreamSynchronize(s));
@@ -212,9 +212,9 @@ static int match_check_table(int32_t smear_cells, const uint8_t* kern) {
 static int match_set_table(dm_grid* g, int32_t r, const uint8_t* kern) {
   int rc = DM_OK;
   if (!g->match_V) {
-    if ((rc = dev_alloc(&g->match_kern, 16 * 16 + 1, "smear table"))) return rc;
-    if ((rc = dev_alloc(&g->match_tiles, g->NT, "match tile list"))) return rc;
-    if ((rc = dev_alloc(&g->match_V, g->W * g->H, "response field"))) return rc;
+    if ((rc = g->match_kern.alloc(16 * 16 + 1, "smear table"))) return rc;
+    if ((rc = g->match_tiles.alloc(g->NT, "match tile list"))) return rc;
+    if ((rc = g->match_V.alloc(g->W * g->H, "response field"))) return rc;
     g->match_r = -1;
   }
   const size_t n = (size_t)r * r + 1;
@@ -265,10 +265,10 @@ static void match_want_cells(const dm_grid* g, double fx0, double fx1, double fy
 // beam-angle table, the ranges, and n_q fine coordinates.
 static int match_grow_inputs(dm_grid* g, int32_t S, int32_t N, int32_t A, int64_t n_q) {
   int rc = DM_OK;
-  if ((rc = dev_grow(&g->match_pose4, &g->match_pose_cap, 4 * (int64_t)S * A, "candidate poses")) ||
-      (rc = dev_grow(&g->match_trig, &g->match_trig_cap, 2 * (int64_t)N, "beam angle table")) ||
-      (rc = dev_grow(&g->match_ranges, &g->match_ranges_cap, (int64_t)S * N, "ranges")) ||
-      (rc = dev_grow(&g->match_q, &g->match_q_cap, n_q, "fine coordinates")))
+  if ((rc = g->match_pose4.ensure(4 * (int64_t)S * A, "candidate poses")) ||
+      (rc = g->match_trig.ensure(2 * (int64_t)N, "beam angle table")) ||
+      (rc = g->match_ranges.ensure((int64_t)S * N, "ranges")) ||
+      (rc = g->match_q.ensure(n_q, "fine coordinates")))
     return rc;
   return DM_OK;
 }
@@ -343,8 +343,8 @@ int dm_match_scans(dm_grid* g, int32_t S, const double* poses, int32_t N, const 
 
   const int64_t SA = (int64_t)S * A, T1 = 2 * half + 1, T = T1 * T1;
   if ((rc = match_grow_inputs(g, S, N, A, SA * N)) ||
-      (rc = dev_grow(&g->match_vol, &g->match_vol_cap, SA * T, "score volume")) ||
-      (rc = dev_grow(&g->match_out, &g->match_out_cap, 5 * (int64_t)S, "match results")))
+      (rc = g->match_vol.ensure(SA * T, "score volume")) ||
+      (rc = g->match_out.ensure(5 * (int64_t)S, "match results")))
     return rc;
 
   // the tiles the search windows reach: every used beam ends within range_max
@@ -392,21 +392,16 @@ int dm_match_scans(dm_grid* g, int32_t S, const double* poses, int32_t N, const 
 static int ensure_match_global(dm_grid* g) {
   int rc = DM_OK;
   if (!g->h_mg) {
-    hipError_t e = hipHostMalloc((void**)&g->h_mg, sizeof(uint32_t) * 8, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e != hipSuccess) {
-      g->h_mg = nullptr;
-      return dm_hip_check(e, "hipHostMalloc(relocalisation rounds)");
-    }
+    if ((rc = g->h_mg.alloc(8, hipHostMallocMapped | hipHostMallocCoherent, "relocalisation rounds"))) return rc;
     memset(g->h_mg, 0, sizeof(uint32_t) * 8);
-    DM_HIP(hipHostGetDevicePointer((void**)&g->h_mg_dev, g->h_mg, 0));
   }
   if (g->mg_best) return DM_OK;  // allocated last
-  if ((rc = dev_alloc(&g->mg_hist, 2048, "bound histogram"))) return rc;
-  if ((rc = dev_alloc(&g->mg_ctl, 4, "round control words"))) return rc;
-  if ((rc = dev_alloc(&g->mg_list, dm_grid::kMgExhaustiveBatch, "round block list"))) return rc;
-  if ((rc = dev_alloc(&g->mg_cand, dm_grid::kMgExhaustiveBatch, "round candidates"))) return rc;
-  if ((rc = dev_alloc(&g->mg_nused, 1, "used beams"))) return rc;
-  return dev_alloc(&g->mg_best, 1, "best candidate");
+  if ((rc = g->mg_hist.alloc(2048, "bound histogram"))) return rc;
+  if ((rc = g->mg_ctl.alloc(4, "round control words"))) return rc;
+  if ((rc = g->mg_list.alloc(dm_grid::kMgExhaustiveBatch, "round block list"))) return rc;
+  if ((rc = g->mg_cand.alloc(dm_grid::kMgExhaustiveBatch, "round candidates"))) return rc;
+  if ((rc = g->mg_nused.alloc(1, "used beams"))) return rc;
+  return g->mg_best.alloc(1, "best candidate");
 }
 
 int dm_match_global(dm_grid* g, int32_t S, const double* poses, int32_t N, const float* ranges, float angle_min,
@@ -460,9 +455,9 @@ int dm_match_global(dm_grid* g, int32_t S, const double* poses, int32_t N, const
 
   if ((rc = match_grow_inputs(g, S, N, A, (int64_t)A * N))) return rc;
   if (!exhaustive) {
-    if ((rc = dev_grow(&g->mg_bound, &g->mg_bound_cap, blocks, "block bounds")) ||
-        (rc = dev_grow(&g->mg_pool, &g->mg_pool_cap, (int64_t)block * block * EWB * EHB, "pooled response field")) ||
-        (rc = dev_grow(&g->mg_ptiles, &g->mg_ptiles_cap, PTX * PTY, "pool tile list")))
+    if ((rc = g->mg_bound.ensure(blocks, "block bounds")) ||
+        (rc = g->mg_pool.ensure((int64_t)block * block * EWB * EHB, "pooled response field")) ||
+        (rc = g->mg_ptiles.ensure(PTX * PTY, "pool tile list")))
       return rc;
     if (g->mg_pool_block != block || g->mg_pool_epoch != g->match_epoch ||
         g->mg_pool_built.size() != (size_t)(PTX * PTY)) {

@@ -67,24 +67,16 @@ extern "C" int dm_atomic_peak(int device, double* out, int32_t cap, int32_t* n_o
   DM_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
   const int64_t blocks = 8 * (int64_t)ncu;  // 8 resident 256-thread workgroups per CU
   const int64_t rows = (256ll << 20) / 256;  // 256 MiB of 256-B rows
-  uint32_t* lds_out = nullptr;
-  uint32_t* buf = nullptr;
-  hipStream_t st = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  DevBuf<uint32_t> lds_out, buf;
+  DevStream st;
+  DevEvent e0, e1;
   double v[2] = {0.0, 0.0};
-  auto cleanup = [&]() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (st) (void)hipStreamDestroy(st);
-    if (lds_out) (void)hipFree(lds_out);
-    if (buf) (void)hipFree(buf);
-  };
-  hipError_t e = hipMalloc((void**)&lds_out, sizeof(uint32_t) * (size_t)(blocks * kProbeThreads));
-  if (e == hipSuccess) e = hipMalloc((void**)&buf, sizeof(uint32_t) * (size_t)(rows * 64));
-  if (e == hipSuccess) e = hipMemset(buf, 0, sizeof(uint32_t) * (size_t)(rows * 64));
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreate(&e0);
-  if (e == hipSuccess) e = hipEventCreate(&e1);
+  if (int rc = lds_out.alloc(blocks * kProbeThreads, "probe LDS results")) return rc;
+  if (int rc = buf.alloc(rows * 64, "probe rows")) return rc;
+  hipError_t e = hipMemset(buf, 0, sizeof(uint32_t) * (size_t)(rows * 64));
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipEventCreate(e0.put());
+  if (e == hipSuccess) e = hipEventCreate(e1.put());
   for (int pass = 0; pass < 2 && e == hipSuccess; ++pass) {  // pass 0 warms up
     float ms = 0.0f;
     hipLaunchKernelGGL(k_peak_lds, dim3((unsigned)blocks), dim3(kProbeThreads), 0, st, lds_out, 7u + pass);
@@ -110,7 +102,6 @@ extern "C" int dm_atomic_peak(int device, double* out, int32_t cap, int32_t* n_o
       v[1] = (double)blocks * kProbeThreads * kGlobIters * 4.0 / (ms * 1e-3);
   }
   if (e == hipSuccess) e = hipGetLastError();
-  cleanup();
   if (e != hipSuccess) return dm_hip_check(e, "dm_atomic_peak");
   for (int32_t i = 0; i < cap && i < 2; ++i) out[i] = v[i];
   if (n_out) *n_out = 2;

@@ -42,26 +42,11 @@ namespace {
 constexpr int kSets = 2;
 
 struct Staging {  // pinned host copies of one band's scan subset (a ring of 3)
-  double* poses = nullptr;
-  float* ranges = nullptr;
-  int64_t pose_cap = 0, ranges_cap = 0;
+  HostBuf<double> poses;
+  HostBuf<float> ranges;
 };
 
 int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-template <class T>
-int dev_alloc_on(int dev, T** p, int64_t count, const char* what) {
-  (void)hipSetDevice(dev);
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  if (count <= 0) count = 1;
-  const hipError_t e = hipMalloc((void**)p, sizeof(T) * (size_t)count);
-  if (e != hipSuccess) {
-    *p = nullptr;
-    return dm_set_error(e == hipErrorOutOfMemory ? DM_ERR_OOM : DM_ERR_HIP, "hipMalloc(%s): %s", what,
-                        hipGetErrorString(e));
-  }
-  return DM_OK;
-}
 
 }  // namespace
 
@@ -73,13 +58,13 @@ struct dm_shard_set {
   int64_t W = 0, H = 0;
   int64_t min_size = 1;
   // exchange buffers [set][band] on the band's device
-  std::vector<int8_t*> erows[kSets], halo[kSets];  // [2W]: own first / last rows; neighbours' rows
-  std::vector<uint8_t*> exp[kSets];                 // export record of the band
-  uint8_t* gathered[kSets] = {nullptr, nullptr};    // P records on band 0's device
-  std::vector<hipEvent_t> ev_rows, ev_exp;
+  std::vector<DevBuf<int8_t>> erows[kSets], halo[kSets];  // [2W]: own first / last rows; neighbours' rows
+  std::vector<DevBuf<uint8_t>> exp[kSets];                // export record of the band
+  DevBuf<uint8_t> gathered[kSets];                        // P records on band 0's device
+  std::vector<DevEvent> ev_rows, ev_exp;
   // dm_sh_ld06_to_scans_device writes its scans on band 0's stream: the next
   // dm_sh_integrate_device orders every band's input reads after ev_in
-  hipEvent_t ev_in = nullptr;
+  DevEvent ev_in;
   bool in_pending = false;
   int64_t rec_cap = 0, want_rec_cap = 0, nb = 0;
   bool refresh = false;  // run a synchronous pass on every band before the next exchange
@@ -90,9 +75,8 @@ struct dm_shard_set {
   std::vector<int> stage_head;  // per band: its own calls, so slot j % 3 is free at its call j
   std::vector<char> active;
   // device-input copies for bands on another device than the inputs
-  std::vector<double*> d_pose;
-  std::vector<float*> d_ranges;
-  std::vector<int64_t> d_pose_cap, d_ranges_cap;
+  std::vector<DevBuf<double>> d_pose;
+  std::vector<DevBuf<float>> d_ranges;
 };
 
 namespace {
@@ -100,8 +84,8 @@ namespace {
 int sh_alloc_exchange(dm_shard_set* s, int64_t rec_cap) {
   for (int k = 0; k < kSets; ++k) {
     for (int r = 0; r < s->P; ++r) {
-      int rc = dev_alloc_on(s->dev[r], &s->erows[k][r], 2 * s->W, "sharded edge rows");
-      if (!rc) rc = dev_alloc_on(s->dev[r], &s->halo[k][r], 2 * s->W, "sharded halo rows");
+      int rc = s->erows[k][r].alloc(2 * s->W, "sharded edge rows", s->dev[r]);
+      if (!rc) rc = s->halo[k][r].alloc(2 * s->W, "sharded halo rows", s->dev[r]);
       if (rc) return rc;
     }
   }
@@ -110,8 +94,8 @@ int sh_alloc_exchange(dm_shard_set* s, int64_t rec_cap) {
   if (rc) return rc;
   for (int k = 0; k < kSets; ++k) {
     for (int r = 0; r < s->P; ++r)
-      if ((rc = dev_alloc_on(s->dev[r], &s->exp[k][r], nb, "sharded export record"))) return rc;
-    if ((rc = dev_alloc_on(s->dev[0], &s->gathered[k], nb * s->P, "sharded gathered records"))) return rc;
+      if ((rc = s->exp[k][r].alloc(nb, "sharded export record", s->dev[r]))) return rc;
+    if ((rc = s->gathered[k].alloc(nb * s->P, "sharded gathered records", s->dev[0]))) return rc;
   }
   s->rec_cap = rec_cap;
   s->nb = nb;
@@ -256,28 +240,11 @@ int dm_sh_destroy(dm_grid* g) {
     if (!s->band[r]) continue;
     (void)hipSetDevice(s->dev[r]);
     (void)dm_synchronize(s->band[r]);
-    for (int k = 0; k < kSets; ++k) {
-      if (s->erows[k][r]) (void)hipFree(s->erows[k][r]);
-      if (s->halo[k][r]) (void)hipFree(s->halo[k][r]);
-      if (s->exp[k][r]) (void)hipFree(s->exp[k][r]);
-    }
-    if (s->d_pose[r]) (void)hipFree(s->d_pose[r]);
-    if (s->d_ranges[r]) (void)hipFree(s->d_ranges[r]);
-    if (s->ev_rows[r]) (void)hipEventDestroy(s->ev_rows[r]);
-    if (s->ev_exp[r]) (void)hipEventDestroy(s->ev_exp[r]);
-    for (auto& st : s->stage) {
-      if (st[(size_t)r].poses) (void)hipHostFree(st[(size_t)r].poses);
-      if (st[(size_t)r].ranges) (void)hipHostFree(st[(size_t)r].ranges);
-    }
   }
-  if (s->P > 0 && s->band[0]) {
-    (void)hipSetDevice(s->dev[0]);
-    for (auto* p : s->gathered)
-      if (p) (void)hipFree(p);
-    if (s->ev_in) (void)hipEventDestroy(s->ev_in);
-  }
-  for (int r = 0; r < s->P; ++r) (void)dm_destroy(s->band[r]);
+  // the set's exchange and staging buffers go with it, before the bands
+  const std::vector<dm_grid*> bands = std::move(s->band);
   delete s;
+  for (dm_grid* b : bands) (void)dm_destroy(b);
   g->sh = nullptr;
   delete g;
   return DM_OK;
@@ -324,19 +291,17 @@ extern "C" int dm_create_sharded(dm_grid** out, const dm_params* p, int32_t nran
   s->row0.assign((size_t)nranks, 0);
   s->rows.assign((size_t)nranks, 0);
   for (int k = 0; k < kSets; ++k) {
-    s->erows[k].assign((size_t)nranks, nullptr);
-    s->halo[k].assign((size_t)nranks, nullptr);
-    s->exp[k].assign((size_t)nranks, nullptr);
+    s->erows[k].resize((size_t)nranks);
+    s->halo[k].resize((size_t)nranks);
+    s->exp[k].resize((size_t)nranks);
   }
-  s->ev_rows.assign((size_t)nranks, nullptr);
-  s->ev_exp.assign((size_t)nranks, nullptr);
-  for (auto& st : s->stage) st.assign((size_t)nranks, Staging());
+  s->ev_rows.resize((size_t)nranks);
+  s->ev_exp.resize((size_t)nranks);
+  for (auto& st : s->stage) st.resize((size_t)nranks);
   s->active.assign((size_t)nranks, 0);
   s->stage_head.assign((size_t)nranks, 0);
-  s->d_pose.assign((size_t)nranks, nullptr);
-  s->d_ranges.assign((size_t)nranks, nullptr);
-  s->d_pose_cap.assign((size_t)nranks, 0);
-  s->d_ranges_cap.assign((size_t)nranks, 0);
+  s->d_pose.resize((size_t)nranks);
+  s->d_ranges.resize((size_t)nranks);
   auto fail = [&](int code) {
     dm_sh_destroy(g);
     return code;
@@ -356,14 +321,14 @@ extern "C" int dm_create_sharded(dm_grid** out, const dm_params* p, int32_t nran
     s->row0[(size_t)r] = r0;
     s->rows[(size_t)r] = rows;
     (void)hipSetDevice(devices[r]);
-    for (hipEvent_t* ev : {&s->ev_rows[(size_t)r], &s->ev_exp[(size_t)r]}) {
-      const hipError_t e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+    for (DevEvent* ev : {&s->ev_rows[(size_t)r], &s->ev_exp[(size_t)r]}) {
+      const hipError_t e = hipEventCreateWithFlags(ev->put(), hipEventDisableTiming);
       if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
     }
   }
   (void)hipSetDevice(devices[0]);
   {
-    const hipError_t e = hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming);
+    const hipError_t e = hipEventCreateWithFlags(s->ev_in.put(), hipEventDisableTiming);
     if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
   }
   // peer access between the bands' devices where the platform offers it
@@ -398,21 +363,8 @@ namespace {
 int sh_stage(dm_shard_set* s, const dm_params& p, int r, int32_t S, const double* poses, int32_t N,
              const float* ranges, int32_t* S_out) {
   Staging& st = s->stage[s->stage_head[(size_t)r]][(size_t)r];
-  if ((int64_t)S * 3 > st.pose_cap) {
-    if (st.poses) (void)hipHostFree(st.poses);
-    st.poses = nullptr;
-    st.pose_cap = 0;
-    DM_HIP(hipHostMalloc((void**)&st.poses, sizeof(double) * 3 * (size_t)std::max(S, 1), hipHostMallocDefault));
-    st.pose_cap = (int64_t)std::max(S, 1) * 3;
-  }
-  if ((int64_t)S * N > st.ranges_cap) {
-    if (st.ranges) (void)hipHostFree(st.ranges);
-    st.ranges = nullptr;
-    st.ranges_cap = 0;
-    const int64_t n = std::max<int64_t>((int64_t)S * N, 1);
-    DM_HIP(hipHostMalloc((void**)&st.ranges, sizeof(float) * (size_t)n, hipHostMallocDefault));
-    st.ranges_cap = n;
-  }
+  int rc = st.poses.ensure((int64_t)S * 3, hipHostMallocDefault, "sharded pose staging");
+  if (rc || (rc = st.ranges.ensure((int64_t)S * N, hipHostMallocDefault, "sharded range staging"))) return rc;
   const double reach = (double)p.range_max + 2.0 * p.resolution;
   const double ylo = p.origin_y + (double)s->row0[(size_t)r] * p.resolution - reach;
   const double yhi = p.origin_y + (double)(s->row0[(size_t)r] + s->rows[(size_t)r]) * p.resolution + reach;
@@ -500,18 +452,12 @@ int dm_sh_integrate_device(dm_grid* g, int32_t S, const double* d_pose4, int32_t
     DM_HIP(hipSetDevice(d));
     if (wait_in) DM_HIP(hipStreamWaitEvent(fs, s->ev_in, 0));
     if (nb > 0 && d != src) {  // inputs on another device: a copy the band owns
-      if ((int64_t)S * 4 > s->d_pose_cap[(size_t)r] || nb > s->d_ranges_cap[(size_t)r]) {
+      if ((int64_t)S * 4 > s->d_pose[(size_t)r].size() || nb > s->d_ranges[(size_t)r].size()) {
         // a call in flight may still read the old copy
         if (int rc = dm_synchronize(b)) return rc;
       }
-      if ((int64_t)S * 4 > s->d_pose_cap[(size_t)r]) {
-        if (int rc = dev_alloc_on(d, &s->d_pose[(size_t)r], (int64_t)S * 4, "sharded poses")) return rc;
-        s->d_pose_cap[(size_t)r] = (int64_t)S * 4;
-      }
-      if (nb > s->d_ranges_cap[(size_t)r]) {
-        if (int rc = dev_alloc_on(d, &s->d_ranges[(size_t)r], nb, "sharded ranges")) return rc;
-        s->d_ranges_cap[(size_t)r] = nb;
-      }
+      if (int rc = s->d_pose[(size_t)r].ensure((int64_t)S * 4, "sharded poses", d)) return rc;
+      if (int rc = s->d_ranges[(size_t)r].ensure(nb, "sharded ranges", d)) return rc;
       // on the front-end's stream: after the previous call's front-end read
       // the last copy, before this call's reads it
       DM_HIP(hipMemcpyPeerAsync(s->d_pose[(size_t)r], d, d_pose4, src, sizeof(double) * 4 * (size_t)S, fs));

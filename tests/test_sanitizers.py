@@ -4,6 +4,8 @@
   header csrc/dm_ray.h) and the C oracle, run against each other on seeded
   batches (ragged maps, a band, chunked beams, NaN / 0 / inf ranges) plus an
   oracle frontier pass with halos;
+* the owner types of libdm's allocations, events and streams (csrc/dm_buf.h)
+  against counting fakes of the HIP calls they make (tests/native/buf_main.cpp);
 * libdm's host code built with -Xarch_host -fsanitize=address,undefined,
   driven through its C-ABI by a C program (tests/native/api_san.c): here the
   validation and error paths (no GPU); the product calls run on the GPU box
@@ -27,6 +29,13 @@ def test_emulation_and_oracle_under_asan_ubsan():
                        env=ENV)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.count(": ok,") == 5 and "ERROR" not in r.stderr
+
+
+def test_owner_types_under_asan_ubsan():
+    _build("buf_main")
+    r = subprocess.run([os.path.join(NATIVE, "buf_main")], capture_output=True, text=True, timeout=60, env=ENV)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "buf_main: ok" in r.stdout and "ERROR" not in r.stderr
 
 
 def test_c_abi_error_paths_under_host_asan():
