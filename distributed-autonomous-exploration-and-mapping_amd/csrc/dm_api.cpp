@@ -1002,8 +1002,13 @@ int merge_readback(dm_grid* g, int slot, int64_t n, dm_cluster* out, int64_t cap
   const int64_t K = (int64_t)g->h_mcnt[0];
   g->msort_hint = K;
   if (n_out) *n_out = K;
-  if (K > cap)
+  if (K > cap) {
+    // a synchronous merge is over whatever the caller's buffer holds: its
+    // device records are the last collected result, as dm_frontiers' are (a
+    // pipelined one stays pending and is noted when it is read)
+    if (slot == dm_grid::kRbSync) note_goal_source(g, slot, 2, g->h_mcnt[2] != 0 ? K : -1);
     return dm_set_error(DM_ERR_CAPACITY, "%lld clusters, capacity %lld", (long long)K, (long long)cap);
+  }
   if (K > hint && slot != dm_grid::kRbSync &&
       (g->rb[slot].gen != g->rb_gen || (!g->h_mcnt[2] && g->rb[slot].pass != g->m_pass)))
     return dm_set_error(DM_ERR_INCOMPLETE, "merge result lost to a workspace reallocation or a later "

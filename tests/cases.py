@@ -168,3 +168,20 @@ def blob_state(seed, R, W, n_blobs=20):
     occ = rng.random((R, W)) < 0.03
     st[occ & (st == 0)] = 100
     return st
+
+
+def sparse_state(seed, R, W, step=3, p_free=0.9):
+    """Isolated free cells in unknown space: about R*W/step^2 clusters."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    st = np.full((R, W), -1, np.int8)
+    st[::step, ::step] = np.where(rng.random(st[::step, ::step].shape) < p_free, 0, -1)
+    return st
+
+
+def tiles_with_free(st):
+    """bool [tile rows, tile columns]: the 64 x 64 tiles that hold a free cell."""
+    H, W = st.shape
+    TY, TX = -(-H // 64), -(-W // 64)
+    pad = np.full((TY * 64, TX * 64), 1, np.int8)
+    pad[:H, :W] = st
+    return (pad.reshape(TY, 64, TX, 64) == 0).any(axis=(1, 3))

@@ -56,6 +56,28 @@ def test_sharded_handle_equals_single_handle_and_oracle(oracle_lib, P, W, H, see
         assert sh.assign_goals(robots, min_size=2) == single.assign_goals(robots, min_size=2)
 
 
+def test_sharded_goals_after_a_pass_with_mask_and_labels(oracle_lib):
+    """The bands' own passes behind dm_frontiers(mask, labels) must not stay
+    band 0's goal source: the goals are chosen among the merged clusters,
+    with a cluster that crosses the band edge among them."""
+    from dm.goals import assign_goals
+
+    p = cases.make_params(256, 256)
+    st = np.full((256, 256), -1, np.int8)
+    st[100:160, 40:200] = 0     # a free room across the band edge at row 128
+    st[20:40, 20:60] = 0        # one in band 0 only
+    st[200:230, 150:220] = 0    # one in band 1 only
+    om = oracle_lib.OracleMap(p)
+    om.state[...] = st
+    clusters = om.frontiers(want_mask=False, want_labels=False)[2]
+    assert len(clusters) == 3
+    robots = [(0.0, 0.0), (-5.0, -5.0), (4.0, 4.0), (1.0, 1.0)]
+    with dm.OccupancyMapper(p, devices=[0, 0]) as sh:
+        sh.set_state(st)
+        np.testing.assert_array_equal(sh.frontiers(want_mask=True, want_labels=True).clusters, clusters)
+        assert sh.assign_goals(robots, min_size=1) == assign_goals(clusters, robots, min_size=1)
+
+
 def test_sharded_pipelined_passes_and_poll(oracle_lib):
     p, batches, amin, inc = _world(11, 800, 1100, S=8, N=1024, nb=5)
     om = oracle_lib.OracleMap(p)

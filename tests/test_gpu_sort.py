@@ -12,17 +12,10 @@ import numpy as np
 import pytest
 
 import cases
+from cases import sparse_state
 from test_gpu_parity import assert_frontiers_equal
 
 pytestmark = pytest.mark.gpu
-
-
-def sparse_state(seed, R, W, step=3, p_free=0.9):
-    """Isolated free cells in unknown space: about R*W/step^2 clusters."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    st = np.full((R, W), -1, np.int8)
-    st[::step, ::step] = np.where(rng.random(st[::step, ::step].shape) < p_free, 0, -1)
-    return st
 
 
 def _oracle_clusters(oracle_lib, p, st):

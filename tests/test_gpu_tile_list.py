@@ -14,17 +14,10 @@ import pytest
 
 import cases
 import dm
+from cases import tiles_with_free as _tiles_with_free
 from test_gpu_parity import assert_frontiers_equal, assert_map_equal
 
 pytestmark = pytest.mark.gpu
-
-
-def _tiles_with_free(st):
-    H, W = st.shape
-    TY, TX = -(-H // 64), -(-W // 64)
-    pad = np.full((TY * 64, TX * 64), 1, np.int8)
-    pad[:H, :W] = st
-    return (pad.reshape(TY, 64, TX, 64) == 0).any(axis=(1, 3))
 
 
 def test_list_grows_with_every_tile_that_held_a_free_cell(oracle_lib):
