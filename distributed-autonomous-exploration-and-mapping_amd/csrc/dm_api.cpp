@@ -29,8 +29,8 @@ hipError_t dm_sync_all(dm_grid* g) {
     const hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
   }
-  g->p_pending = false;
-  for (auto& f : g->fw) f.busy_pending = false;
+  g->p_tail.pending = false;
+  for (auto& f : g->fw) f.busy.pending = false;
   return hipSuccess;
 }
 
@@ -38,7 +38,8 @@ hipError_t dm_copy_shards(dm_grid* g) {
   const size_t bytes = sizeof(unsigned long long) * kShards * kShardWords;
   hipError_t e = hipMemcpyAsync(g->h_sh, g->iw[g->iw_cur].sh, bytes, hipMemcpyDeviceToHost, g->stream);
   if (e == hipSuccess)
-    e = hipMemcpyAsync(g->h_sh + kShards * kShardWords, g->fsh, bytes, hipMemcpyDeviceToHost, g->stream);
+    e = hipMemcpyAsync(g->h_sh + kShards * kShardWords, dm_last_fw(g).fsh, bytes, hipMemcpyDeviceToHost,
+                       g->stream);
   return e;
 }
 
@@ -212,7 +213,6 @@ int grow_slots(dm_grid* g, int64_t need) {
   int rc = g->slot_label.alloc(cap, "slot labels");
   for (auto& f : g->fw)
     if (!rc) rc = f.slot_parent.alloc(cap, "slot parents");
-  g->slot_parent = g->fw[g->fparity].slot_parent;
   if (!rc) rc = g->slot_root.alloc(cap, "slot roots");
   if (!rc) rc = g->slot_own.alloc(3 * cap, "slot sums");
   if (!rc) rc = g->slot_acc.alloc(3 * cap, "slot totals");
@@ -220,7 +220,6 @@ int grow_slots(dm_grid* g, int64_t need) {
   for (int sl = 0; sl <= dm_grid::kRbSlots && !rc; ++sl)  // one per readback slot
     rc = g->rb[sl].out_clu.alloc(cap, "sorted clusters");
   ++g->rb_gen;
-  g->out_clu = g->rb[g->rb_head].out_clu.records();
   if (!rc) rc = g->slot_k.alloc(cap, "slot cluster index");
   if (!rc) rc = g->rank_of.alloc(cap, "cluster sorted position");
   if (!rc) rc = dm_grow_bucket_sort(g, cap);
@@ -229,9 +228,8 @@ int grow_slots(dm_grid* g, int64_t need) {
   return DM_OK;
 }
 
-// Grow readback slot `slot`'s mapped buffer (no pass of that slot in flight).
-int grow_host_out(dm_grid* g, int slot, int64_t need) {
-  dm_grid::RbSlot& r = g->rb[slot];
+// Grow readback slot `r`'s mapped buffer (no pass of that slot in flight).
+int grow_host_out(dm_grid::RbSlot& r, int64_t need) {
   if (need <= r.h_out.capacity()) return DM_OK;
   // mapped + coherent: k_rank_sort writes the readback header and the first
   // records (32 bytes each) straight into it over PCIe (no D2H copy command
@@ -241,17 +239,18 @@ int grow_host_out(dm_grid* g, int slot, int64_t need) {
 }
 
 // Copy nw sorted cluster records to `out`: the first `have` are already in
-// g->h_out (32-byte records that arrived with the counters: the centroids
-// are added here, dm_centroid); the rest come from d_sorted.  When the device
-// could not sort (too many records), sort the n raw records of d_raw ([n][4]
-// int64) here and compute the centroids with the same formula.
-int copy_clusters(dm_grid* g, bool sorted, int64_t n, int64_t nw, int64_t have,
+// slot r's h_out (32-byte records that arrived with the counters: the
+// centroids are added here, dm_centroid); the rest come from d_sorted.  When
+// the device could not sort (too many records), sort the n raw records of
+// d_raw ([n][4] int64) here and compute the centroids with the same formula.
+int copy_clusters(const dm_grid* g, const dm_grid::RbSlot& r, bool sorted, int64_t n, int64_t nw, int64_t have,
                   const dm_cluster* d_sorted, const long long* d_raw, dm_cluster* out) {
   if (sorted) {
     have = std::min<int64_t>(have, nw);
     const double ox = g->p.origin_x, oy = g->p.origin_y, res = g->p.resolution;
+    const dm_raw_record* h_out = r.h_out.records();
     for (int64_t i = 0; i < have; ++i) {
-      const dm_raw_record& q = g->h_out[i];
+      const dm_raw_record& q = h_out[i];
       dm_cluster& c = out[i];
       c.label = q.label;
       c.size = q.size;
@@ -280,14 +279,10 @@ int copy_clusters(dm_grid* g, bool sorted, int64_t n, int64_t nw, int64_t have,
   return DM_OK;
 }
 
-// The label-sorted device records of a collected result (slot's out_clu for
+// The label-sorted device records of a collected result (slot r's out_clu for
 // kind 1, m_out for kind 2), n records; n < 0: not sorted on the device.
-void note_goal_source(dm_grid* g, int slot, int kind, int64_t n) {
-  g->goal_slot = n >= 0 ? slot : -1;
-  g->goal_kind = kind;
-  g->goal_n = n;
-  g->goal_epoch = kind == 1 ? g->rb[slot].wepoch : g->rb[slot].mepoch;
-  g->goal_gen = g->rb_gen;
+void note_goal_source(dm_grid* g, const dm_grid::RbSlot& r, int kind, int64_t n) {
+  g->goal = {n >= 0 ? &r : nullptr, kind, kind == 1 ? r.wepoch : r.mepoch, g->rb_gen, n};
 }
 
 int grow_merge(dm_grid* g, int64_t n) {
@@ -354,7 +349,7 @@ int not_on_sharded(const dm_grid* g, const char* what) {
 // both shard blocks into the pinned mirrors and waits for them.
 int read_counters(dm_grid* g) {
   DM_HIP(dm_join_pass_stream(g));
-  DM_HIP(hipMemcpyAsync(g->h_cnt, g->cnt, sizeof(unsigned long long) * CNT_N,
+  DM_HIP(hipMemcpyAsync(g->h_cnt, dm_last_fw(g).cnt, sizeof(unsigned long long) * CNT_N,
                         hipMemcpyDeviceToHost, g->stream));
   DM_HIP(hipMemcpyAsync(g->h_cnt + CNT_N, g->iw[g->iw_cur].cnt, sizeof(unsigned long long) * CNT_N,
                         hipMemcpyDeviceToHost, g->stream));
@@ -534,8 +529,6 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
     if ((rc = g->flist_n[i].alloc(16, "frontier tile list length"))) return fail(rc);
     DM_HIP(hipMemset(g->flist_n[i], 0, sizeof(unsigned long long) * 16));
   }
-  g->ftiles = g->flist[0];
-  g->ftiles_n = g->flist_n[0];
   DM_HIP(hipMemset(g->fl_n, 0, sizeof(unsigned long long) * 48));
   if ((rc = g->bits_flag.alloc(16, "bit-row hand-off word"))) return fail(rc);
   DM_HIP(hipMemset(g->bits_flag, 0, sizeof(unsigned long long) * 16));
@@ -554,10 +547,8 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   // C5 row band under 64 x 4096-beam fans holds 0.81 clusters per tile and
   // more than two slots per tile (test_gpu_c5_full.py).
   if ((rc = grow_slots(g, std::max<int64_t>(1 << 16, kSlotsPerTile * g->NT)))) return fail(rc);
-  dm_select_fw(g, g->fparity);
-  for (int sl = 0; sl <= dm_grid::kRbSlots; ++sl)
-    if ((rc = grow_host_out(g, sl, 1 << 14))) return fail(rc);
-  dm_select_slot(g, 0);
+  for (auto& r : g->rb)
+    if ((rc = grow_host_out(r, 1 << 14))) return fail(rc);
   if ((rc = g->h_cnt.alloc(2 * CNT_N + 1, hipHostMallocDefault, "counters"))) return fail(rc);
   if ((rc = g->h_sh.alloc(2 * kShards * kShardWords, hipHostMallocDefault, "shard counters"))) return fail(rc);
   if ((rc = g->m_cnt.alloc(4, "merge counters"))) return fail(rc);
@@ -791,8 +782,8 @@ int dm_frontier_cache_stats(dm_grid* g, uint64_t* hits, uint64_t* misses) {
   if (!hits || !misses) return dm_set_error(DM_ERR_INVALID_ARG, "hits or misses is NULL");
   if (!g->fc_collected) {  // a band's export pass: its shard counters, once it is done
     DM_HIP(dm_sync_all(g));
-    DM_HIP(hipMemcpy(g->h_sh + kShards * kShardWords, g->fsh, sizeof(unsigned long long) * kShards * kShardWords,
-                     hipMemcpyDeviceToHost));
+    DM_HIP(hipMemcpy(g->h_sh + kShards * kShardWords, dm_last_fw(g).fsh,
+                     sizeof(unsigned long long) * kShards * kShardWords, hipMemcpyDeviceToHost));
     g->fc_hits = dm_shard_sum(g->h_sh + kShards * kShardWords, SH_CHIT);
     g->fc_misses = dm_shard_sum(g->h_sh + kShards * kShardWords, SH_CMISS);
     g->fc_collected = true;
@@ -869,11 +860,10 @@ int dm_frontiers(dm_grid* g, uint8_t* mask, int64_t* labels, dm_cluster* out, in
   }
   // its own readback slot: asynchronous passes may be in flight (this pass
   // runs after them in stream order and sees the map as it is now)
-  const int slot = dm_grid::kRbSync;
-  dm_select_slot(g, slot);
+  dm_grid::RbSlot& r = g->rb[dm_grid::kRbSync];
   int64_t n = 0, copied = 0;
   for (int attempt = 0; attempt < 8; ++attempt) {
-    rc = dm_launch_frontiers(g, mask != nullptr, labels != nullptr, &n, &copied);
+    rc = dm_launch_frontiers(g, r, mask != nullptr, labels != nullptr, &n, &copied);
     if (rc != DM_ERR_CAPACITY) break;
     if ((rc = grow_slots(g, n + n / 2 + 1024))) return rc;
     rc = DM_ERR_CAPACITY;
@@ -881,10 +871,10 @@ int dm_frontiers(dm_grid* g, uint8_t* mask, int64_t* labels, dm_cluster* out, in
   if (rc) return rc == DM_ERR_CAPACITY ? dm_set_error(rc, "frontier slot arrays kept overflowing") : rc;
   g->frontier_valid = true;
   const int64_t nw = std::min<int64_t>(n, cap);
-  note_goal_source(g, slot, 1, g->h_cnt[CNT_SORTED] != 0 ? n : -1);
-  if ((rc = copy_clusters(g, g->h_cnt[CNT_SORTED] != 0, n, nw, copied, g->out_clu, g->clusters, out)))
+  note_goal_source(g, r, 1, g->h_cnt[CNT_SORTED] != 0 ? n : -1);
+  if ((rc = copy_clusters(g, r, g->h_cnt[CNT_SORTED] != 0, n, nw, copied, r.out_clu.records(), g->clusters, out)))
     return rc;
-  if ((rc = grow_host_out(g, slot, n + n / 4 + 64))) return rc;
+  if ((rc = grow_host_out(r, n + n / 4 + 64))) return rc;
   if (mask) DM_HIP(hipMemcpy(mask, g->mask, (size_t)cells, hipMemcpyDeviceToHost));
   if (labels) DM_HIP(hipMemcpy(labels, g->labels, sizeof(int64_t) * (size_t)cells, hipMemcpyDeviceToHost));
   if (n_out) *n_out = n;
@@ -914,25 +904,19 @@ int dm_frontiers_export_device(dm_grid* g, void* d_export, int64_t rec_cap) {
   // the band's sorted records go to a readback slot no pending pass holds
   // (the synchronous slot when the ring is full: a merge of a sharded parent
   // can have every ring slot pending on its band 0)
-  dm_select_slot(g, g->rb_count < dm_grid::kRbSlots ? (g->rb_head + g->rb_count) % dm_grid::kRbSlots
-                                                    : dm_grid::kRbSync);
+  dm_grid::RbSlot& r = g->rb[g->rb_count < dm_grid::kRbSlots ? (g->rb_head + g->rb_count) % dm_grid::kRbSlots
+                                                             : dm_grid::kRbSync];
   // with overlap, split as dm_frontiers_begin: the labelling, sort and
   // export on the pass stream, beside the next batch's map update
   hipStream_t es = g->stream;
-  if ((rc = dm_enqueue_frontiers(g, false, false, g->overlap, &es))) return rc;
-  if ((rc = dm_launch_export(g, es, d_export, rec_cap))) return rc;
+  if ((rc = dm_enqueue_frontiers(g, r, false, false, g->overlap, &es))) return rc;
+  if ((rc = dm_launch_export(g, r, es, d_export, rec_cap))) return rc;
   g->fc_collected = false;  // no readback header: dm_frontier_cache_stats reads the shards
   if (es != g->stream) {
     // the parity set is free again, and the grid stream may use the shared
     // pass arrays, once the pass stream is past this export
-    dm_grid::FrWs& f = g->fw[g->fparity];
-    DM_HIP(hipEventRecord(f.ev_split, es));
-    f.busy = f.ev_split;
-    f.busy_pending = true;
-    f.busy_pass = g->fr_pass;
-    g->p_tail = f.ev_split;
-    g->p_pending = true;
-    g->p_tail_pass = g->fr_pass;
+    dm_grid::FrWs& f = dm_last_fw(g);
+    DM_HIP(dm_note_pass_end(g, &f, f.ev_split, es, g->fr_pass));
   } else {
     DM_HIP(dm_mark_ws_free(g));
   }
@@ -951,28 +935,26 @@ int dm_exchange_stream(dm_grid* g, void** stream) {
 
 namespace {
 
-// Claim the next readback slot for an asynchronous pass (selected as the
-// current slot), or fail if every slot holds a pass not collected yet.
-int claim_slot(dm_grid* g, int* slot) {
+// *slot: the next readback slot of the ring, for an asynchronous pass; fails
+// if every slot holds a pass not collected yet.
+int claim_slot(dm_grid* g, dm_grid::RbSlot** slot) {
   if (g->rb_count == dm_grid::kRbSlots)
     return dm_set_error(DM_ERR_INVALID_ARG, "%d passes in flight: end the oldest first", dm_grid::kRbSlots);
-  *slot = (g->rb_head + g->rb_count) % dm_grid::kRbSlots;
-  dm_select_slot(g, *slot);
+  *slot = &g->rb[(g->rb_head + g->rb_count) % dm_grid::kRbSlots];
   return DM_OK;
 }
 
-// The oldest pending pass, if it is of `kind`: wait for it, select its slot.
-int wait_oldest(dm_grid* g, int kind, const char* what) {
-  if (!g->rb_count || g->rb[g->rb_head].kind != kind)
+// *slot: the oldest pending pass's, waited for, if that pass is of `kind`.
+int wait_oldest(dm_grid* g, int kind, const char* what, dm_grid::RbSlot** slot) {
+  dm_grid::RbSlot& r = g->rb[g->rb_head];
+  if (!g->rb_count || r.kind != kind)
     return dm_set_error(DM_ERR_INVALID_ARG, "the oldest pass in flight is not a %s pass", what);
-  DM_HIP(dm_event_wait(g->rb[g->rb_head].ev));
+  DM_HIP(dm_event_wait(r.ev));
   if (kind == 1) {  // passes end in order: this one and every earlier one are done
-    const uint64_t pass = g->rb[g->rb_head].pass;
-    for (auto& f : g->fw)
-      if (f.busy_pending && f.busy_pass <= pass) f.busy_pending = false;
-    if (g->p_pending && g->p_tail_pass <= pass) g->p_pending = false;
+    for (auto& f : g->fw) f.busy.seen(r.pass);
+    g->p_tail.seen(r.pass);
   }
-  dm_select_slot(g, g->rb_head);
+  *slot = &r;
   return DM_OK;
 }
 
@@ -982,13 +964,13 @@ void retire_oldest(dm_grid* g) {
   --g->rb_count;
 }
 
-// A completed merge in readback slot `slot` (selected): header -> result.
-int merge_readback(dm_grid* g, int slot, int64_t n, dm_cluster* out, int64_t cap, int64_t* n_out) {
-  dm_select_slot(g, slot);
-  // the merge's sort kernel wrote the merge counters and the first h_out_cap
-  // records into the slot's mapped readback buffer: no copy command
-  const int64_t hint = std::min<int64_t>(g->h_out_cap, n);
-  memcpy(g->h_mcnt, dm_rb_header(g->h_out), sizeof(unsigned long long) * 4);
+// A completed merge in readback slot `r`: header -> result.
+int merge_readback(dm_grid* g, dm_grid::RbSlot& r, int64_t n, dm_cluster* out, int64_t cap, int64_t* n_out) {
+  const bool sync = &r == &g->rb[dm_grid::kRbSync];  // dm_merge_bands' own slot, not one of the ring
+  // the merge's sort kernel wrote the merge counters and the first records
+  // (the buffer's capacity) into the slot's mapped readback buffer: no copy command
+  const int64_t hint = std::min<int64_t>(r.h_out.capacity(), n);
+  memcpy(g->h_mcnt, dm_rb_header(r.h_out.records()), sizeof(unsigned long long) * 4);
   // the band exports (dm_frontiers_export_device) never pass through
   // dm_frontiers_readback: the largest band's K hints the next export's sort
   g->sort_hint = (int64_t)g->h_mcnt[3];
@@ -1006,17 +988,16 @@ int merge_readback(dm_grid* g, int slot, int64_t n, dm_cluster* out, int64_t cap
     // a synchronous merge is over whatever the caller's buffer holds: its
     // device records are the last collected result, as dm_frontiers' are (a
     // pipelined one stays pending and is noted when it is read)
-    if (slot == dm_grid::kRbSync) note_goal_source(g, slot, 2, g->h_mcnt[2] != 0 ? K : -1);
+    if (sync) note_goal_source(g, r, 2, g->h_mcnt[2] != 0 ? K : -1);
     return dm_set_error(DM_ERR_CAPACITY, "%lld clusters, capacity %lld", (long long)K, (long long)cap);
   }
-  if (K > hint && slot != dm_grid::kRbSync &&
-      (g->rb[slot].gen != g->rb_gen || (!g->h_mcnt[2] && g->rb[slot].pass != g->m_pass)))
+  if (K > hint && !sync && (r.gen != g->rb_gen || (!g->h_mcnt[2] && r.pass != g->m_pass)))
     return dm_set_error(DM_ERR_INCOMPLETE, "merge result lost to a workspace reallocation or a later "
                                            "unsorted merge: rerun");
-  note_goal_source(g, slot, 2, g->h_mcnt[2] != 0 ? K : -1);
-  int rc = copy_clusters(g, g->h_mcnt[2] != 0, K, K, hint, g->m_out, g->m_clu, out);
+  note_goal_source(g, r, 2, g->h_mcnt[2] != 0 ? K : -1);
+  int rc = copy_clusters(g, r, g->h_mcnt[2] != 0, K, K, hint, r.m_out, g->m_clu, out);
   if (rc) return rc;
-  return grow_host_out(g, slot, K + K / 4 + 64);
+  return grow_host_out(r, K + K / 4 + 64);
 }
 
 }  // namespace
@@ -1030,24 +1011,20 @@ int dm_merge_bands_begin(dm_grid* g, const void* d_gathered, int32_t nranks, int
     return dm_set_error(DM_ERR_INVALID_ARG, "need d_gathered, nranks >= 1, rec_cap >= 1");
   const int64_t n = (int64_t)nranks * rec_cap;
   if (n >= (1ll << 31)) return dm_set_error(DM_ERR_SHAPE, "nranks * rec_cap must be < 2^31");
-  int slot = 0;
+  dm_grid::RbSlot* slot = nullptr;
   if ((rc = grow_merge(g, n)) || (rc = claim_slot(g, &slot))) return rc;
+  dm_grid::RbSlot& r = *slot;
   // on the exchange stream: the grid stream's with overlap off (after the
   // pass stream: the sort workspace is shared with the frontier passes), the
   // pass stream's with overlap on (the exports' own order)
   hipStream_t ms = dm_exchange_stream_of(g);
   if (ms == g->stream) DM_HIP(dm_join_pass_stream(g));
-  if ((rc = dm_launch_merge(g, ms, d_gathered, nranks, rec_cap, min_size))) return rc;
-  dm_grid::RbSlot& r = g->rb[slot];
-  DM_HIP(hipEventRecord(r.ev, ms));
-  if (ms != g->stream) {
-    g->p_tail = r.ev;
-    g->p_pending = true;
-    // no band pass's completion implies this merge's: only an explicit join
-    // (dm_join_pass_stream) clears it, never wait_oldest of a kind-1 pass
-    // (the merge reads the shared sort workspace a later pass would reuse)
-    g->p_tail_pass = UINT64_MAX;
-  }
+  if ((rc = dm_launch_merge(g, r, ms, d_gathered, nranks, rec_cap, min_size))) return rc;
+  // no band pass's completion implies this merge's (UINT64_MAX): only an
+  // explicit join (dm_join_pass_stream) clears it, never wait_oldest of a
+  // kind-1 pass (the merge reads the shared sort workspace a later pass would
+  // reuse)
+  DM_HIP(dm_note_pass_end(g, nullptr, r.ev, ms, UINT64_MAX));
   r.kind = 2;
   r.merge_n = n;
   r.gen = g->rb_gen;
@@ -1061,9 +1038,9 @@ int dm_merge_bands_end(dm_grid* g, dm_cluster* out, int64_t cap, int64_t* n_out)
   int rc = check_grid(g);
   if (rc || (rc = use_device(g))) return rc;
   if (cap < 0 || (cap > 0 && !out)) return dm_set_error(DM_ERR_INVALID_ARG, "bad cluster buffer");
-  if ((rc = wait_oldest(g, 2, "dm_merge_bands_begin"))) return rc;
-  const int slot = g->rb_head;
-  rc = merge_readback(g, slot, g->rb[slot].merge_n, out, cap, n_out);
+  dm_grid::RbSlot* r = nullptr;
+  if ((rc = wait_oldest(g, 2, "dm_merge_bands_begin", &r))) return rc;
+  rc = merge_readback(g, *r, r->merge_n, out, cap, n_out);
   if (rc != DM_ERR_CAPACITY) retire_oldest(g);  // on a capacity error the result stays pending
   return rc;
 }
@@ -1079,12 +1056,12 @@ int dm_merge_bands(dm_grid* g, const void* d_gathered, int32_t nranks, int64_t r
   const int64_t n = (int64_t)nranks * rec_cap;
   if (n >= (1ll << 31)) return dm_set_error(DM_ERR_SHAPE, "nranks * rec_cap must be < 2^31");
   if ((rc = grow_merge(g, n))) return rc;
-  dm_select_slot(g, dm_grid::kRbSync);  // its own slot: asynchronous passes may be in flight
+  dm_grid::RbSlot& r = g->rb[dm_grid::kRbSync];  // its own slot: asynchronous passes may be in flight
   hipStream_t ms = dm_exchange_stream_of(g);  // as dm_merge_bands_begin
   if (ms == g->stream) DM_HIP(dm_join_pass_stream(g));
-  if ((rc = dm_launch_merge(g, ms, d_gathered, nranks, rec_cap, min_size))) return rc;
+  if ((rc = dm_launch_merge(g, r, ms, d_gathered, nranks, rec_cap, min_size))) return rc;
   DM_HIP(hipStreamSynchronize(ms));
-  return merge_readback(g, dm_grid::kRbSync, n, out, cap, n_out);
+  return merge_readback(g, r, n, out, cap, n_out);
 }
 
 int dm_merge_max_band_k(const dm_grid* g, int64_t* max_k) {
@@ -1100,23 +1077,15 @@ int dm_frontiers_begin(dm_grid* g) {
   if (g && g->sh) return dm_sh_frontiers_begin(g);
   int rc = check_grid(g);
   if (rc || (rc = use_device(g))) return rc;
-  int slot = 0;
+  dm_grid::RbSlot* slot = nullptr;
   if ((rc = claim_slot(g, &slot))) return rc;
+  dm_grid::RbSlot& r = *slot;
   // with overlap, the pass's labelling half runs on the pass stream, beside
   // the next batch's map update (dm_enqueue_frontiers)
   hipStream_t es = g->stream;
-  if ((rc = dm_enqueue_frontiers(g, false, false, g->overlap, &es))) return rc;
-  dm_grid::RbSlot& r = g->rb[slot];
-  DM_HIP(hipEventRecord(r.ev, es));
-  dm_grid::FrWs& f = g->fw[g->fparity];
-  f.busy = r.ev;  // the set is free again once this pass ended
-  f.busy_pending = true;
-  f.busy_pass = g->fr_pass;
-  if (es != g->stream) {
-    g->p_tail = r.ev;
-    g->p_pending = true;
-    g->p_tail_pass = g->fr_pass;
-  }
+  if ((rc = dm_enqueue_frontiers(g, r, false, false, g->overlap, &es))) return rc;
+  // the set is free again once this pass ended
+  DM_HIP(dm_note_pass_end(g, &dm_last_fw(g), r.ev, es, g->fr_pass));
   // the integrate workspaces' accumulations are ahead of this event: it
   // frees them (a marker right behind the write-heavy map update would cost
   // the stream several microseconds)
@@ -1134,11 +1103,11 @@ int dm_frontiers_end(dm_grid* g, dm_cluster* out, int64_t cap, int64_t* n_out) {
   int rc = check_grid(g);
   if (rc || (rc = use_device(g))) return rc;
   if (cap < 0 || (cap > 0 && !out)) return dm_set_error(DM_ERR_INVALID_ARG, "bad cluster buffer");
-  if ((rc = wait_oldest(g, 1, "dm_frontiers_begin"))) return rc;
-  const int slot = g->rb_head;
-  const dm_grid::RbSlot& r = g->rb[slot];
+  dm_grid::RbSlot* slot = nullptr;
+  if ((rc = wait_oldest(g, 1, "dm_frontiers_begin", &slot))) return rc;
+  dm_grid::RbSlot& r = *slot;
   int64_t n = 0, copied = 0;
-  rc = dm_frontiers_readback(g, &n, &copied);
+  rc = dm_frontiers_readback(g, r, &n, &copied);
   if (rc == DM_ERR_CAPACITY) {
     retire_oldest(g);
     if ((rc = grow_slots(g, n + n / 2 + 1024))) return rc;
@@ -1164,11 +1133,11 @@ int dm_frontiers_end(dm_grid* g, dm_cluster* out, int64_t cap, int64_t* n_out) {
   // the slot data (dm_get_edge_labels) describes the map only if this was
   // the last pass and no map change came in between
   g->frontier_valid = g->rb_count == 1 && r.seq == g->integrate_seq;
-  note_goal_source(g, slot, 1, sorted ? n : -1);
-  rc = copy_clusters(g, sorted, n, n, copied, g->out_clu, g->clusters, out);
+  note_goal_source(g, r, 1, sorted ? n : -1);
+  rc = copy_clusters(g, r, sorted, n, n, copied, r.out_clu.records(), g->clusters, out);
   retire_oldest(g);
   if (rc) return rc;
-  return grow_host_out(g, slot, n + n / 4 + 64);
+  return grow_host_out(r, n + n / 4 + 64);
 }
 
 int dm_frontiers_poll(dm_grid* g, int32_t* ready) {

@@ -11,7 +11,7 @@
 // Pipeline; tiles are the 64x64 tiles of dm_integrate.hip:
 //   (list)          the persistent tile list: every tile that has held a free
 //                   cell, appended by the integrate apply (dm_internal.h,
-//                   ftiles); only free cells can be frontier cells, so every
+//                   flist); only free cells can be frontier cells, so every
 //                   other tile is skipped without reading it
 //   k_frontier_bits one wave per listed tile: frontier bit rows (the only
 //                   kernel that reads the map), plus the pass's resets
@@ -1865,34 +1865,25 @@ DM_PH_READER(ftile)
 // reads them), from the last frontier call's slots.
 int dm_launch_edge_labels(dm_grid* g) {
   DM_LAUNCH(k_slot_labels, dim3(grid_for(2 * g->W, 256, 1024)), dim3(256), 0, g->stream,
-                     2 * g->W, g->slot_cap, g->edge_slot, g->slot_root, g->slot_label, g->edge_label);
+                     2 * g->W, g->slot_cap, dm_last_fw(g).edge_slot, g->slot_root, g->slot_label, g->edge_label);
   DM_HIP(hipGetLastError());
   return DM_OK;
 }
 
-int dm_launch_rank_sort(hipStream_t stream, long long* clusters, const long long* sums,
-                        const long long* labels, const unsigned long long* d_count,
-                        int64_t max_records, double ox, double oy, double res, dm_cluster* out,
-                        int32_t* rank_of, unsigned long long* d_sorted, const unsigned long long* cnt,
-                        int ncnt, int sorted_idx, const unsigned long long* fsh, dm_raw_record* host_out,
-                        int64_t host_cap, int64_t expect) {
-  const int64_t cap = std::min<int64_t>(max_records, kRankSortCap);
+int dm_launch_rank_sort(const dm_grid* g, hipStream_t stream, const SortArgs& a, int64_t expect) {
+  const int64_t cap = std::min<int64_t>(a.max_records, kRankSortCap);
   // one workgroup per 64 expected records (twice the last pass's count, at
   // least 2048): a thousand idle 1024-thread workgroups cost microseconds
   const int64_t want = dm_quantize_up(std::max<int64_t>(2 * expect, 2048));
   DM_LAUNCH(k_rank_sort, dim3(grid_for(std::min(cap, want), 64, 1 << 20)), dim3(kSortThreads), 0, stream,
-                     ox, oy, res, clusters, sums, labels, d_count, cap, out, rank_of, d_sorted, cnt, ncnt, sorted_idx,
-                     fsh, host_out, host_cap);
+                     g->p.origin_x, g->p.origin_y, g->p.resolution, a.clusters, a.sums, a.labels, a.d_count, cap, a.out,
+                     a.rank_of, a.d_sorted, a.cnt, a.ncnt, a.sorted_idx, a.fsh, a.host_out, a.host_cap);
   DM_HIP(hipGetLastError());
   return DM_OK;
 }
 
-int dm_launch_bucket_sort(dm_grid* g, hipStream_t stream, long long* clusters, const long long* sums,
-                          const long long* labels, const unsigned long long* d_count,
-                          int64_t max_records, int64_t row_base, int64_t rows, dm_cluster* out,
-                          int32_t* rank_of, unsigned long long* d_sorted, const unsigned long long* cnt,
-                          int ncnt, int sorted_idx, const unsigned long long* fsh, dm_raw_record* host_out,
-                          int64_t host_cap) {
+int dm_launch_bucket_sort(dm_grid* g, hipStream_t stream, const SortArgs& a, int64_t row_base, int64_t rows) {
+  const int64_t max_records = a.max_records;
   if (max_records > g->bs_cap || rows > g->rs_rows)
     return dm_set_error(DM_ERR_INVALID_ARG, "row sort: %lld records over %lld rows exceed its workspace",
                         (long long)max_records, (long long)rows);
@@ -1903,18 +1894,18 @@ int dm_launch_bucket_sort(dm_grid* g, hipStream_t stream, long long* clusters, c
   const int64_t expect = std::min<int64_t>(max_records, std::max<int64_t>(2 * g->sort_hint, 4096));
   const int eg = grid_for(expect, 256, 4096);
   const int nsb = (int)((rows + kRsChunk - 1) / kRsChunk);
-  DM_LAUNCH(k_rs_count, dim3(eg), dim3(256), 0, stream, clusters, labels, d_count, max_records, base, g->W,
+  DM_LAUNCH(k_rs_count, dim3(eg), dim3(256), 0, stream, a.clusters, a.labels, a.d_count, max_records, base, g->W,
             g->rs_cnt, g->bs_key, g->bs_idx2, g->rs_status, nsb);
   DM_HIP(hipGetLastError());
-  DM_LAUNCH(k_rs_scan, dim3(nsb), dim3(256), 0, stream, d_count, max_records, rows, g->rs_cnt, g->rs_off,
+  DM_LAUNCH(k_rs_scan, dim3(nsb), dim3(256), 0, stream, a.d_count, max_records, rows, g->rs_cnt, g->rs_off,
             g->rs_status);
   DM_HIP(hipGetLastError());
-  DM_LAUNCH(k_rs_place, dim3(eg), dim3(256), 0, stream, d_count, max_records, g->W, g->bs_key, g->bs_idx2,
+  DM_LAUNCH(k_rs_place, dim3(eg), dim3(256), 0, stream, a.d_count, max_records, g->W, g->bs_key, g->bs_idx2,
             g->rs_off, g->bs_key2, g->bs_idx);
   DM_HIP(hipGetLastError());
-  DM_LAUNCH(k_rs_rank, dim3(eg), dim3(256), 0, stream, g->p.origin_x, g->p.origin_y, g->p.resolution, clusters,
-            sums, labels, d_count, max_records, g->W, g->bs_key2, g->bs_idx, g->rs_off, out, rank_of, d_sorted, cnt,
-            ncnt, sorted_idx, fsh, host_out, host_cap, g->rs_status + nsb);
+  DM_LAUNCH(k_rs_rank, dim3(eg), dim3(256), 0, stream, g->p.origin_x, g->p.origin_y, g->p.resolution, a.clusters,
+            a.sums, a.labels, a.d_count, max_records, g->W, g->bs_key2, g->bs_idx, g->rs_off, a.out, a.rank_of,
+            a.d_sorted, a.cnt, a.ncnt, a.sorted_idx, a.fsh, a.host_out, a.host_cap, g->rs_status + nsb);
   DM_HIP(hipGetLastError());
   return DM_OK;
 }
@@ -1922,28 +1913,29 @@ int dm_launch_bucket_sort(dm_grid* g, hipStream_t stream, long long* clusters, c
 // Enqueues the band pipeline (no synchronisation): tile list, tile CCL,
 // border merge, roots, compaction, sort.  Shared by dm_launch_frontiers and
 // the cross-band export (dm_merge.hip).
-int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool split, hipStream_t* end_stream) {
+int dm_enqueue_frontiers(dm_grid* g, dm_grid::RbSlot& r, bool want_mask, bool want_labels, bool split,
+                         hipStream_t* end_stream) {
   const FGeom fg = make_fgeom(g, want_mask, want_labels);
   const int64_t cells = g->R * g->W;
   // the bit rows run on g->stream after everything shared with
   // the pass stream (labelling of earlier passes) -- except for split passes,
   // which keep that order on the pass stream itself
   if (!split) DM_HIP(dm_join_pass_stream(g));
-  ++g->rb[g->cur_slot].wepoch;  // this pass rewrites the selected slot's records
+  ++r.wepoch;  // this pass rewrites the slot's records
   ++g->fr_pass;
   g->fparity ^= 1;
   dm_grid::FrWs& fw = g->fw[g->fparity];
-  if (fw.busy_pending) {  // the set's previous pass (two passes ago) may still run
-    DM_HIP(hipStreamWaitEvent(g->stream, fw.busy, 0));
-    fw.busy_pending = false;
+  if (fw.busy.pending) {  // the set's previous pass (two passes ago) may still run
+    DM_HIP(hipStreamWaitEvent(g->stream, fw.busy.ev, 0));
+    fw.busy.pending = false;
   }
-  dm_select_fw(g, g->fparity);
   unsigned long long* list_n = g->fl_n + 16 * (g->fr_pass % 3);  // this pass's list length (k_frontier_bits)
   // every relist_period passes (1, 2, 4, ... 16) the tile list goes back into
   // tile order, into the other list (dm_launch_relist: the passes still
   // labelling keep theirs)
   if (++g->relist_age >= g->relist_period)
     if (int rc = dm_launch_relist(g, true)) return rc;
+  int32_t* const tiles = g->flist[g->flist_cur];
   KernelTimer t;
   if (want_mask) DM_HIP(hipMemsetAsync(g->mask, 0, (size_t)cells, g->stream));
   if (want_labels) DM_HIP(hipMemsetAsync(g->cell_slot, 0xFF, sizeof(int32_t) * (size_t)cells, g->stream));
@@ -2006,9 +1998,9 @@ int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool spli
   }
   dm_timer_begin(g, "frontier_bits", &t);
   DM_LAUNCH(k_frontier_bits, dim3(bits_grid), dim3(kFW * 64), 0, g->stream, fg, g->state, g->halo, g->fmask,
-            g->fedge, g->tile_seen, g->ftiles, g->ftiles_n, list_n, g->fbits, g->cnt, g->fmask_on ? 1 : 0,
-            dense ? nullptr : g->big_tiles, g->fsh, g->edge_slot, 2 * g->W, g->slot_parent, g->fe_flag + kHaltWord,
-            g->bits_flag + kStampWord);
+            g->fedge, g->tile_seen, tiles, g->flist_n[g->flist_cur], list_n, fw.fbits, fw.cnt, g->fmask_on ? 1 : 0,
+            dense ? nullptr : fw.big_tiles.get(), fw.fsh, fw.edge_slot, 2 * g->W, fw.slot_parent,
+            g->fe_flag + kHaltWord, g->bits_flag + kStampWord);
   dm_timer_end(g, &t);
   DM_HIP(hipGetLastError());
   // the map has been read: with split, the rest runs on the pass stream,
@@ -2037,18 +2029,18 @@ int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool spli
     DM_HIP(hipEventRecord(g->ev_bigfork, ps));
     DM_HIP(hipStreamWaitEvent(g->big_stream, g->ev_bigfork, 0));
     dm_timer_begin(g, "frontier_big", &t, g->big_stream);
-    DM_LAUNCH(big_kernel, dim3(big_grid), dim3(kFT), 0, g->big_stream, fg, g->fbits,
-              g->big_tiles,
-              g->ftiles, list_n, g->border, g->rel, g->slot_label, g->slot_parent, g->slot_own,
-              g->slot_acc, g->mask, g->cell_slot, g->edge_slot, g->cnt, g->fsh, 0, g->fcache);
+    DM_LAUNCH(big_kernel, dim3(big_grid), dim3(kFT), 0, g->big_stream, fg, fw.fbits,
+              fw.big_tiles,
+              tiles, list_n, g->border, g->rel, g->slot_label, fw.slot_parent, g->slot_own,
+              g->slot_acc, g->mask, g->cell_slot, fw.edge_slot, fw.cnt, fw.fsh, 0, g->fcache);
     dm_timer_end(g, &t);
     DM_HIP(hipGetLastError());
     DM_HIP(hipEventRecord(g->ev_big, g->big_stream));
     dm_timer_begin(g, "frontier_tile", &t, ps);
-    DM_LAUNCH(wave_kernel, dim3(wave_grid), dim3(kFW * 64), 0, ps, fg, g->fbits,
-                       g->ftiles, list_n, g->border, g->rel,
-                       g->slot_label, g->slot_parent, g->slot_own, g->slot_acc, g->mask, g->cell_slot,
-                       g->edge_slot, g->cnt, g->fsh, g->big_tiles);
+    DM_LAUNCH(wave_kernel, dim3(wave_grid), dim3(kFW * 64), 0, ps, fg, fw.fbits,
+                       tiles, list_n, g->border, g->rel,
+                       g->slot_label, fw.slot_parent, g->slot_own, g->slot_acc, g->mask, g->cell_slot,
+                       fw.edge_slot, fw.cnt, fw.fsh, fw.big_tiles);
     dm_timer_end(g, &t);
     DM_HIP(hipGetLastError());
     DM_HIP(hipStreamWaitEvent(ps, g->ev_big, 0));
@@ -2060,10 +2052,10 @@ int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool spli
     // (caps of 256-1024 workgroups, to leave the map update more slots,
     // measured slower: DESIGN.md §3.3.2)
     const int dense_grid = grid_for(std::min<int64_t>(g->NT, g->ftile_hint > 0 ? want_waves : g->NT), 1, 8192);
-    DM_LAUNCH(big_kernel, dim3(dense_grid), dim3(kFT), 0, ps, fg, g->fbits, nullptr,
-              g->ftiles, list_n,
-              g->border, g->rel, g->slot_label, g->slot_parent, g->slot_own, g->slot_acc, g->mask,
-              g->cell_slot, g->edge_slot, g->cnt, g->fsh, 1, g->fcache);
+    DM_LAUNCH(big_kernel, dim3(dense_grid), dim3(kFT), 0, ps, fg, fw.fbits, nullptr,
+              tiles, list_n,
+              g->border, g->rel, g->slot_label, fw.slot_parent, g->slot_own, g->slot_acc, g->mask,
+              g->cell_slot, fw.edge_slot, fw.cnt, fw.fsh, 1, g->fcache);
     dm_timer_end(g, &t);
     DM_HIP(hipGetLastError());
   }
@@ -2071,8 +2063,8 @@ int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool spli
     dm_timer_begin(g, "frontier_edges", &t, ps);
     // one wave per listed tile (the kernel grid-strides)
     DM_LAUNCH(k_frontier_edges, dim3(grid_for(std::min<int64_t>(want_waves, g->NT), kFW, 16384)),
-              dim3(kFW * 64), 0, ps, fg, g->ftiles, list_n, g->border, g->rel,
-              g->slot_parent, g->cnt);
+              dim3(kFW * 64), 0, ps, fg, tiles, list_n, g->border, g->rel,
+              fw.slot_parent, fw.cnt);
     dm_timer_end(g, &t);
     DM_HIP(hipGetLastError());
   }
@@ -2083,14 +2075,14 @@ int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool spli
   const int fuse = g->p.min_frontier_size <= 1 ? 1 : 0;
   // one workgroup per CU: fewer workgroups = fewer per-root flushes
   DM_LAUNCH(k_frontier_resolve, dim3(grid_for(g->slot_cap, 256, g->n_cu)), dim3(256), 0, ps, fg,
-                     g->slot_parent, g->slot_root, g->slot_own, g->slot_acc, g->fsh, fuse, g->slot_label,
-                     g->clusters, g->slot_k, g->cnt);
+                     fw.slot_parent, g->slot_root, g->slot_own, g->slot_acc, fw.fsh, fuse, g->slot_label,
+                     g->clusters, g->slot_k, fw.cnt);
   dm_timer_end(g, &t);
   DM_HIP(hipGetLastError());
   if (!fuse) {
     dm_timer_begin(g, "frontier_compact", &t, ps);
     DM_LAUNCH(k_frontier_compact, dim3(sgrid), dim3(256), 0, ps, fg,
-                       g->slot_root, g->slot_label, g->slot_acc, g->clusters, g->slot_k, g->cnt, g->fsh);
+                       g->slot_root, g->slot_label, g->slot_acc, g->clusters, g->slot_k, fw.cnt, fw.fsh);
     dm_timer_end(g, &t);
     DM_HIP(hipGetLastError());
   }
@@ -2102,28 +2094,24 @@ int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool spli
   dm_timer_begin(g, "sort_clusters", &t, ps);
   // the last collected pass predicts this one's cluster count (either sort
   // is exact for any count; only their speed differs)
-  const int rc = g->sort_hint > g->sort_min
-      ? dm_launch_bucket_sort(g, ps, g->clusters, fuse ? g->slot_acc : nullptr, fuse ? g->slot_label : nullptr,
-                              g->cnt + CNT_CLUSTERS, g->slot_cap, g->row0, g->R, g->out_clu,
-                              g->rank_of, g->cnt + CNT_SORTED, g->cnt, CNT_N, CNT_SORTED, g->fsh,
-                              g->h_out_dev, g->h_out_cap)
-      : dm_launch_rank_sort(ps, g->clusters, fuse ? g->slot_acc : nullptr, fuse ? g->slot_label : nullptr,
-                            g->cnt + CNT_CLUSTERS, g->slot_cap, g->p.origin_x,
-                            g->p.origin_y, g->p.resolution, g->out_clu, g->rank_of, g->cnt + CNT_SORTED,
-                            g->cnt, CNT_N, CNT_SORTED, g->fsh, g->h_out_dev, g->h_out_cap, g->sort_hint);
+  const SortArgs sa = {g->clusters, fuse ? g->slot_acc.get() : nullptr, fuse ? g->slot_label.get() : nullptr,
+                       fw.cnt + CNT_CLUSTERS, g->slot_cap, r.out_clu.records(), g->rank_of, fw.cnt + CNT_SORTED,
+                       fw.cnt, CNT_N, CNT_SORTED, fw.fsh, r.h_out.records_dev(), r.h_out.capacity()};
+  const int rc = g->sort_hint > g->sort_min ? dm_launch_bucket_sort(g, ps, sa, g->row0, g->R)
+                                            : dm_launch_rank_sort(g, ps, sa, g->sort_hint);
   dm_timer_end(g, &t);
   return rc;
 }
 
 // After a frontier pass completed: the counters plus a speculative first
-// chunk of the sorted cluster records are in g->h_out (k_rank_sort wrote the
-// readback header and the first h_out_cap records straight into the mapped
-// host buffer: no copy command).  Returns DM_ERR_CAPACITY (with
-// *n_clusters = slots needed) when the slot arrays overflowed.
-int dm_frontiers_readback(dm_grid* g, int64_t* n_clusters, int64_t* copied) {
-  const unsigned long long* hdr = dm_rb_header(g->h_out);
+// chunk of the sorted cluster records are in slot r's h_out (k_rank_sort wrote
+// the readback header and the first records, as many as it holds, straight
+// into the mapped host buffer: no copy command).  Returns DM_ERR_CAPACITY
+// (with *n_clusters = slots needed) when the slot arrays overflowed.
+int dm_frontiers_readback(dm_grid* g, const dm_grid::RbSlot& r, int64_t* n_clusters, int64_t* copied) {
+  const unsigned long long* hdr = dm_rb_header(r.h_out.records());
   memcpy(g->h_cnt, hdr, sizeof(unsigned long long) * CNT_N);
-  *copied = std::min<int64_t>(g->h_out_cap, g->slot_cap);
+  *copied = std::min<int64_t>(r.h_out.capacity(), g->slot_cap);
   const unsigned long long most = hdr[CNT_N];
   if (g->h_cnt[CNT_OVERFLOW] & kOvPipeline)
     return dm_set_error(DM_ERR_PIPELINE, "the overlapped pipeline's front-end hand-off timed out: a map "
@@ -2149,10 +2137,10 @@ int dm_frontiers_readback(dm_grid* g, int64_t* n_clusters, int64_t* copied) {
 }
 
 // Runs the frontier pipeline with ONE synchronisation (dm_frontiers_readback).
-int dm_launch_frontiers(dm_grid* g, bool want_mask, bool want_labels, int64_t* n_clusters,
+int dm_launch_frontiers(dm_grid* g, dm_grid::RbSlot& r, bool want_mask, bool want_labels, int64_t* n_clusters,
                         int64_t* copied) {
-  int rc = dm_enqueue_frontiers(g, want_mask, want_labels);
+  int rc = dm_enqueue_frontiers(g, r, want_mask, want_labels);
   if (rc) return rc;
   DM_HIP(hipStreamSynchronize(g->stream));
-  return dm_frontiers_readback(g, n_clusters, copied);
+  return dm_frontiers_readback(g, r, n_clusters, copied);
 }

@@ -738,14 +738,13 @@ static int check_goal_args(int32_t n_robots, bool any_null, const char* null_nam
 // The label-sorted device records of the last collected frontier result
 // (dm_api.cpp: note_goal_source), if its readback slot still holds them.
 static int goal_source(const dm_grid* g, const dm_cluster** recs, int64_t* K) {
-  const int s = g->goal_slot;
-  if (s < 0 || g->goal_gen != g->rb_gen ||
-      (g->goal_kind == 1 ? g->rb[s].wepoch : g->rb[s].mepoch) != g->goal_epoch)
+  const dm_grid::GoalSource& s = g->goal;
+  if (!s.slot || s.gen != g->rb_gen || (s.kind == 1 ? s.slot->wepoch : s.slot->mepoch) != s.epoch)
     return dm_set_error(DM_ERR_INVALID_ARG, "no collected frontier result on the device (call dm_frontiers, "
                                             "dm_frontiers_end or dm_merge_bands first; a later pass may have "
                                             "reused its readback slot)");
-  *recs = g->goal_kind == 1 ? g->rb[s].out_clu.records() : g->rb[s].m_out.get();
-  *K = g->goal_n;
+  *recs = s.kind == 1 ? s.slot->out_clu.records() : s.slot->m_out.get();
+  *K = s.n;
   return DM_OK;
 }
 

@@ -770,7 +770,7 @@ __device__ inline PackedPiece no_piece() {
 // A tile's new tile_free word after a net change of dfree free cells from
 // `old` (the item applying the tile is its only writer in the call): a tile
 // whose free count rises from 0 while kTileListed is clear is appended to the
-// persistent frontier tile list (dm_internal.h, ftiles) and flagged.  Tiles
+// persistent frontier tile list (dm_internal.h, flist) and flagged.  Tiles
 // that were listed stay listed (the pass skips tiles without frontier bits).
 __device__ inline int32_t free_update(int32_t old, int32_t dfree, int32_t tile, int32_t* tlist,
                                       unsigned long long* tlist_n) {
@@ -1656,8 +1656,8 @@ int dm_launch_integrate(dm_grid* g, int32_t S, const double* d_pose4, int32_t N,
                      dim3(kQuarter), 0,
                      g->stream, ge, make_apply(g), w.hitems, (int)CNT_ITEMS, w.litems, (int)CNT_LITEMS,
                      (int)CNT_SITEMS, w.pieces, w.tile_count, g->tile_free, w.slabs, g->L, g->state, w.cnt, w.sh, vec_ok,
-                     w.heavy_list, w.heavy_done, g->ftiles, g->ftiles_n, g->h_hint.dev(), g->fe_flag + kHaltWord,
-                     g->tile_seen);
+                     w.heavy_list, w.heavy_done, g->flist[g->flist_cur], g->flist_n[g->flist_cur], g->h_hint.dev(),
+                     g->fe_flag + kHaltWord, g->tile_seen);
   dm_timer_end(g, &t);
   DM_HIP(hipGetLastError());
   if (g->overlap) w.free_owed = true;
@@ -1706,13 +1706,13 @@ int dm_launch_relist(dm_grid* g, bool swap) {
       g->flist_ev_set[g->flist_cur] = true;
     }
     g->flist_cur = x;
-    g->ftiles = g->flist[x];
-    g->ftiles_n = g->flist_n[x];
   }
-  DM_HIP(hipMemsetAsync(g->ftiles_n, 0, sizeof(unsigned long long), g->stream));
+  int32_t* const list = g->flist[g->flist_cur];
+  unsigned long long* const list_len = g->flist_n[g->flist_cur];
+  DM_HIP(hipMemsetAsync(list_len, 0, sizeof(unsigned long long), g->stream));
   const int iters = (int)std::min<int64_t>(kListIters, std::max<int64_t>(1, (g->NT + 65535) / 65536));
   DM_LAUNCH(k_list_tiles, dim3(grid_for((g->NT + iters - 1) / iters, 256, 1024)), dim3(256), 0, g->stream,
-            g->NT, g->tile_free, g->ftiles, g->ftiles_n, iters);
+            g->NT, g->tile_free, list, list_len, iters);
   DM_HIP(hipGetLastError());
   g->relist_age = 0;
   // from a fresh list (bulk writes) the period doubles up to kRelistPasses

@@ -170,8 +170,11 @@ struct dm_shard_set;  // dm_sharded.cpp
 
 // Every allocation, event and stream of a handle is a member that owns it
 // (dm_buf.h) and goes with the handle: dm_destroy has no list of them.  The
-// raw pointers and hipEvent_t's left in it are views of one of those owners,
-// each said so where it is declared.
+// only raw handles left in it are hipEvent_t's that name an event one of those
+// owners holds (PassEnd::ev, IntWs::free_wait), each said so where it is
+// declared.  Nothing in it means "the slot / workspace set / tile list in
+// use": a pass's readback slot is an argument of the functions that write or
+// read it, its workspace set is fw[fparity], the tile list flist[flist_cur].
 struct dm_grid {
   dm_params p;
   // non-null: a sharded parent (dm_create_sharded); every call runs on its
@@ -211,8 +214,10 @@ struct dm_grid {
   // ring of kRbSlots readback slots, so a pass can be started before the
   // previous one was collected.  Each slot owns what its _end reads: the
   // mapped readback buffer (header + first records), the device sorted
-  // records, the event marking the pass's end.  out_clu / h_out / h_out_dev /
-  // h_out_cap / m_out below are views of the slot in use (dm_select_slot).
+  // records, the event marking the pass's end.  The entry point that starts or
+  // collects a pass picks the slot and hands it to everything that writes or
+  // reads it (dm_enqueue_frontiers, dm_launch_merge, dm_launch_export,
+  // dm_frontiers_readback).
   struct RbSlot {
     Headed<DevBuf<dm_cluster>, kRbRecords> out_clu;         // device sorted band records behind the header
     Headed<HostBuf<dm_raw_record>, kRbHostRecords> h_out;   // mapped host readback behind the header, 32-byte records
@@ -232,7 +237,6 @@ struct dm_grid {
   static constexpr int kRbSync = kRbSlots;      // the slot of synchronous calls (dm_frontiers, dm_merge_bands)
   RbSlot rb[kRbSlots + 1];
   int rb_head = 0, rb_count = 0;      // oldest pending slot, pending passes
-  int cur_slot = 0;                   // the slot dm_select_slot selected
   uint64_t rb_gen = 0;                // bumped when device record buffers are reallocated
   // frontier / merge passes enqueued so far: an unsorted result (more
   // clusters than the sort kernel takes) lives in the shared raw arrays
@@ -245,7 +249,7 @@ struct dm_grid {
   DevBuf<float> L;
   DevBuf<int8_t> state;
   // free cells per tile (bits 0..29) | kTileListed: the tile is on the
-  // persistent frontier tile list (ftiles / ftiles_n below)
+  // persistent frontier tile list (flist[flist_cur] below)
   DevBuf<int32_t> tile_free;
   // [NT][64 rows][16] per tile: byte j of row y holds the free bits of cells
   // 4j..4j+3 (low nibble) and their unknown bits (high nibble); out-of-grid
@@ -299,10 +303,8 @@ struct dm_grid {
   // last export pass (fc_collected false: read from its shards on demand)
   unsigned long long fc_hits = 0, fc_misses = 0;
   bool fc_collected = true;
-  unsigned long long* cnt = nullptr;    // CNT_N device counters (frontier fields): a view of fw[]
   HostBuf<unsigned long long> h_cnt;  // pinned mirror: [CNT_N] frontier counters, [CNT_N] integrate counters
-  unsigned long long* fsh = nullptr;    // [kShards][kShardWords] frontier shards: a view of fw[]
-  HostBuf<unsigned long long> h_sh;   // pinned mirror of the last call's integrate shards, then fsh
+  HostBuf<unsigned long long> h_sh;   // pinned mirror of the last call's integrate shards, then the last pass's fsh
 
   // The capacities kept beside the buffers (these, slot_cap, bs_cap, rs_rows,
   // m_cap, plan_qcap, gain_cap) are not one buffer's size, which the buffer
@@ -363,27 +365,33 @@ struct dm_grid {
   int32_t last_S = 0, last_N = 0;
 
   // frontier workspace
+  // Where a pass ended (dm_note_pass_end); pending until the host has seen it
+  // end or `stream` was ordered after it.
+  struct PassEnd {
+    hipEvent_t ev = nullptr;  // names a readback slot's ev or a set's ev_split
+    bool pending = false;
+    uint64_t pass = 0;        // fr_pass of the pass; UINT64_MAX: a merge, which no band pass's end implies
+    // the host saw pass `done` end: passes end in order, so every earlier one has
+    void seen(uint64_t done) { if (pass <= done) pending = false; }
+  };
   // What a pass's bit-row kernel writes on `stream` while the previous
   // pass's labelling may still run on pass_stream is double-buffered by pass
   // parity (fparity): counters, shards, list, frontier bit rows, edge slots,
-  // slot parents.  The current set's arrays are also reachable through the
-  // plain fields below (dm_select_fw).  A set is reused two passes later; its
-  // previous pass must be done by then (busy: the event that pass recorded,
-  // waited on by `stream` unless the host already saw it complete).
+  // slot parents.  The last pass's set is dm_last_fw(g).  A set is reused two
+  // passes later; its previous pass must be done by then (busy: waited on by
+  // `stream` unless the host already saw it complete).
   struct FrWs {
-    DevBuf<unsigned long long> cnt;  // [CNT_N]
-    DevBuf<unsigned long long> fsh;  // [kShards][kShardWords]
-    DevBuf<int32_t> big_tiles;       // [NT]
-    DevBuf<uint64_t> fbits;          // [NT][64]
-    DevBuf<int32_t> edge_slot;       // [2][W]
+    DevBuf<unsigned long long> cnt;  // [CNT_N] device counters (frontier fields)
+    DevBuf<unsigned long long> fsh;  // [kShards][kShardWords] frontier shards
+    DevBuf<int32_t> big_tiles;       // [NT] per list position: 1 = too many runs for a tile-wave (k_frontier_bits)
+    DevBuf<uint64_t> fbits;          // [NT][64] frontier bit rows of the listed tiles (k_frontier_bits)
+    DevBuf<int32_t> edge_slot;       // [2][W] slots of the band's first / last row
     DevBuf<int32_t> slot_parent;     // [slot_cap]
-    hipEvent_t busy = nullptr;          // the last pass's end (a view of its readback event or ev_split)
+    PassEnd busy;                       // the set's last pass
     DevEvent ev_split;                  // end of a split export pass on the pass stream
-    bool busy_pending = false;
-    uint64_t busy_pass = 0;             // fr_pass of that pass
   };
   FrWs fw[2];
-  // the pass's list lengths (snapshots of *ftiles_n taken by k_frontier_bits),
+  // the pass's list lengths (snapshots of the tile list's length taken by k_frontier_bits),
   // a ring of three on separate lines: pass n uses fl_n[16 * (n % 3)]
   DevBuf<unsigned long long> fl_n;
   // pass_stream (dm_set_overlap + dm_frontiers_begin): the labelling half of
@@ -398,35 +406,29 @@ struct dm_grid {
   DevStream big_stream;
   DevEvent ev_bigfork, ev_big;
   DevBuf<unsigned long long> bits_flag;  // [kSigWord] / [kGateWord] counts, [kStampWord] pass stamp
-  hipEvent_t p_tail = nullptr;        // the last pass_stream pass's end (a view)
-  bool p_pending = false;             // pass_stream work `stream` has not been ordered after
-  uint64_t p_tail_pass = 0;
+  PassEnd p_tail;  // the last pass_stream pass or merge; pending: `stream` has not been ordered after it
   // The persistent frontier tile list: every tile that has held a free cell
   // since the last bulk state write, in the order its first free cell
   // appeared (only free cells can be frontier cells).  Appended by the
   // integrate apply (the item that raises a tile's free count above 0 while
   // kTileListed is clear sets it and takes a list position), rebuilt after
   // bulk writes (dm_launch_recount: k_list_tiles).  Append-only between
-  // rebuilds, so a pass reads the first *ftiles_n entries (its snapshot, taken
-  // on the map stream after its batch) while later batches append behind them.
-  int32_t* ftiles = nullptr;               // [NT] the current list (a view of one of flist)
-  unsigned long long* ftiles_n = nullptr;  // [16]: [0] its length (a view of flist_n)
+  // rebuilds, so a pass reads the first flist_n[flist_cur][0] entries (its
+  // snapshot, taken on the map stream after its batch) while later batches
+  // append behind them.
   // Two lists: the periodic rebuild in tile order (dm_launch_relist) writes
   // the other one and switches, so passes still labelling go on reading the
   // old one (nothing appends to it after the switch) and the map stream never
   // waits for them; flist_ev[i]: the pass stream's position when list i was
   // left, which a rebuild into list i waits for (long done 16 passes later)
-  DevBuf<int32_t> flist[2];
-  DevBuf<unsigned long long> flist_n[2];
+  DevBuf<int32_t> flist[2];               // [NT]
+  DevBuf<unsigned long long> flist_n[2];  // [16]: [0] the list's length
   DevEvent flist_ev[2];
   bool flist_ev_set[2] = {false, false};
-  int flist_cur = 0;
+  int flist_cur = 0;      // the current list
   int relist_age = 0;     // passes since the list was last put in tile order
   int relist_period = 1;  // passes between those rebuilds: 1, 2, 4, ... up to kRelistPasses
                           // (a fresh map's list grows fastest in its first passes)
-  // big_tiles, fbits, slot_parent, edge_slot: views of fw[] (dm_select_fw)
-  int32_t* big_tiles = nullptr;  // [NT] per list position: 1 = too many runs for a tile-wave (k_frontier_bits)
-  uint64_t* fbits = nullptr;   // [NT][64] frontier bit rows of the listed tiles (k_frontier_bits)
   DevBuf<int32_t> border;   // [tile][4][64] slot ids of a tile's edges (published sides only)
   // tile-edge hand-off words of k_frontier_tile, [4][NT]: horizontal (t, t+1),
   // vertical (t, t+TX), diagonal (t, t+TX+1), anti-diagonal (t, t+TX-1) pairs,
@@ -436,20 +438,13 @@ struct dm_grid {
   int64_t border_cap = 0;      // in tiles
   int64_t slot_cap = 0;
   DevBuf<long long> slot_label;
-  int32_t* slot_parent = nullptr;
   DevBuf<int32_t> slot_root;
   DevBuf<long long> slot_own;  // [slot][3] size, sum_x, sum_y
   DevBuf<long long> slot_acc;  // [slot][3]
   DevBuf<long long> clusters;  // [cap][4] label,size,sum_x,sum_y (unsorted)
   DevBuf<int32_t> slot_k;      // [slot_cap] root slot -> compact cluster index
   DevBuf<int32_t> rank_of;     // [slot_cap] compact cluster index -> sorted position
-  // out_clu, h_out, h_out_dev, h_out_cap, m_out: views of rb[] (dm_select_slot)
-  dm_cluster* out_clu = nullptr;  // [slot_cap] sorted cluster records (k_rank_sort)
-  dm_raw_record* h_out = nullptr;  // pinned (mapped, coherent) readback: header + sorted 32-byte records
-  dm_raw_record* h_out_dev = nullptr;  // its device address
-  int64_t h_out_cap = 0;
   DevBuf<int32_t> cell_slot;   // dense [R][W] (only when labels requested)
-  int32_t* edge_slot = nullptr;   // [2][W] slots of the band's first / last row
   DevBuf<long long> edge_label;// [2][W]
   DevBuf<uint8_t> mask;        // dense [R][W] (only when mask requested)
   DevBuf<long long> labels;    // dense [R][W] int64 (only when requested)
@@ -496,7 +491,6 @@ struct dm_grid {
   DevBuf<long long> m_label;
   DevBuf<long long> m_acc;     // [m_cap][3] size, sum_x, sum_y
   DevBuf<long long> m_clu;     // [m_cap][4] merged records (unsorted)
-  dm_cluster* m_out = nullptr;    // [m_cap] merged records, sorted
   DevBuf<unsigned long long> m_cnt;    // [4] device: K, flags, sorted, max band K
   HostBuf<unsigned long long> h_mcnt;   // pinned mirror
   // [0] workgroups the last accumulation needed (dense items + sparse items
@@ -509,9 +503,13 @@ struct dm_grid {
   // goal selection (dm_goals.hip): the last collected sorted result on the
   // device (a readback slot's out_clu / m_out while that slot's epoch is
   // unchanged), top-T workspaces, robot / index / centroid staging
-  int goal_slot = -1, goal_kind = 0;  // kind 1: band frontiers (out_clu), 2: merge (m_out)
-  uint64_t goal_epoch = 0, goal_gen = 0;
-  int64_t goal_n = 0;
+  struct GoalSource {
+    const RbSlot* slot = nullptr;  // nullptr: none, or not sorted on the device
+    int kind = 0;                  // 1: band frontiers (out_clu), 2: merge (m_out)
+    uint64_t epoch = 0, gen = 0;   // the slot's wepoch / mepoch and rb_gen when it was collected
+    int64_t n = 0;
+  };
+  GoalSource goal;
   DevBuf<unsigned long long> goal_k[2];
   DevBuf<uint32_t> goal_i[2];
   DevBuf<double> goal_io;          // [4 * 256] robots xy, then centroids xy
@@ -610,17 +608,8 @@ struct dm_grid {
   std::vector<dm_kernel_stat> stats;
 };
 
-// Point the current-slot views (out_clu, h_out, h_out_dev, h_out_cap, m_out)
-// at readback slot `slot`.
-inline void dm_select_slot(dm_grid* g, int slot) {
-  const dm_grid::RbSlot& r = g->rb[slot];
-  g->cur_slot = slot;
-  g->out_clu = r.out_clu.records();
-  g->h_out = r.h_out.records();
-  g->h_out_dev = r.h_out.records_dev();
-  g->h_out_cap = r.h_out.capacity();
-  g->m_out = r.m_out;
-}
+// The workspace set of the last frontier pass.
+inline dm_grid::FrWs& dm_last_fw(dm_grid* g) { return g->fw[g->fparity]; }
 
 // the set the next integrate call will use
 inline int dm_next_set(const dm_grid* g) { return (g->iw_cur + 1) % dm_grid::kIntSets; }
@@ -639,18 +628,6 @@ inline hipError_t dm_mark_ws_free(dm_grid* g, hipEvent_t recorded = nullptr) {
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
-}
-
-// Point the current-set views (cnt, fsh, big_tiles, fbits,
-// edge_slot, slot_parent) at frontier workspace set `s`.
-inline void dm_select_fw(dm_grid* g, int s) {
-  const dm_grid::FrWs& f = g->fw[s];
-  g->cnt = f.cnt;
-  g->fsh = f.fsh;
-  g->big_tiles = f.big_tiles;
-  g->fbits = f.fbits;
-  g->edge_slot = f.edge_slot;
-  g->slot_parent = f.slot_parent;
 }
 
 // Host wait for an event the pipelined caller expects within tens of
@@ -688,9 +665,22 @@ inline hipError_t dm_event_wait(hipEvent_t ev) {
 // Order `stream` after the pass_stream work enqueued so far (the frontier
 // arrays other than the parity sets are shared by all passes).
 inline hipError_t dm_join_pass_stream(dm_grid* g) {
-  if (!g->p_pending) return hipSuccess;
-  g->p_pending = false;
-  return hipStreamWaitEvent(g->stream, g->p_tail, 0);
+  if (!g->p_tail.pending) return hipSuccess;
+  g->p_tail.pending = false;
+  return hipStreamWaitEvent(g->stream, g->p_tail.ev, 0);
+}
+
+// A pass of workspace set `set` (nullptr: a merge, which uses none) with
+// number `pass` ends here on stream `s`: record `ev` there and note it as the
+// set's last pass and, on a stream other than the handle's, as the work
+// `stream` has yet to be ordered after.
+inline hipError_t dm_note_pass_end(dm_grid* g, dm_grid::FrWs* set, hipEvent_t ev, hipStream_t s, uint64_t pass) {
+  const hipError_t e = hipEventRecord(ev, s);
+  if (e != hipSuccess) return e;
+  const dm_grid::PassEnd end{ev, true, pass};
+  if (set) set->busy = end;
+  if (s != g->stream) g->p_tail = end;
+  return hipSuccess;
 }
 
 // A call with too few beams to fill the chip enumerates each beam's pieces
@@ -719,9 +709,10 @@ constexpr int kRelistPasses = 16;
 int dm_launch_state_from_logodds(dm_grid* g);
 int dm_launch_map_image(dm_grid* g, uint8_t* d_img);
 int dm_launch_set_state(dm_grid* g, const int8_t* d_state_in);
-// split: the labelling half on g->pass_stream (dm_frontiers_begin with
-// overlap); *end_stream receives the stream the pass ends on.
-int dm_enqueue_frontiers(dm_grid* g, bool want_mask, bool want_labels, bool split = false,
+// The pass's sorted records and readback go to slot `r`.  split: the labelling
+// half on g->pass_stream (dm_frontiers_begin with overlap); *end_stream
+// receives the stream the pass ends on.
+int dm_enqueue_frontiers(dm_grid* g, dm_grid::RbSlot& r, bool want_mask, bool want_labels, bool split = false,
                          hipStream_t* end_stream = nullptr);
 // Hand-off between streams (dm_integrate.hip): k_seq_signal counts
 // flag[kSigWord] up; k_seq_gate (one lane) counts flag[kGateWord] up and waits
@@ -731,18 +722,29 @@ int dm_launch_signal(hipStream_t s, unsigned long long* flag);
 int dm_launch_gate(hipStream_t s, unsigned long long* flag, unsigned long long* err, unsigned long long err_bit,
                    unsigned long long ticks = 0, unsigned long long fault = 0);
 int dm_launch_edge_labels(dm_grid* g);
-int dm_frontiers_readback(dm_grid* g, int64_t* n_clusters, int64_t* copied);
-int dm_launch_frontiers(dm_grid* g, bool want_mask, bool want_labels, int64_t* n_clusters,
+int dm_frontiers_readback(dm_grid* g, const dm_grid::RbSlot& r, int64_t* n_clusters, int64_t* copied);
+int dm_launch_frontiers(dm_grid* g, dm_grid::RbSlot& r, bool want_mask, bool want_labels, int64_t* n_clusters,
                         int64_t* copied);
-// sums / labels: slot sums (slot_acc) and slot labels when the records were
-// written by the fused compaction (-(slot + 1) in place of the size), else
-// nullptr.
-int dm_launch_rank_sort(hipStream_t stream, long long* clusters, const long long* sums,
-                        const long long* labels, const unsigned long long* d_count,
-                        int64_t max_records, double ox, double oy, double res, dm_cluster* out,
-                        int32_t* rank_of, unsigned long long* d_sorted, const unsigned long long* cnt,
-                        int ncnt, int sorted_idx, const unsigned long long* fsh, dm_raw_record* host_out,
-                        int64_t host_cap, int64_t expect);
+// What both device sorts take (the band pass's and the merge's records).
+struct SortArgs {
+  long long* clusters;  // [max_records][4] raw records
+  // slot sums (slot_acc) and slot labels when the records were written by the
+  // fused compaction (-(slot + 1) in place of the size), else nullptr
+  const long long* sums;
+  const long long* labels;
+  const unsigned long long* d_count;  // device: the record count
+  int64_t max_records;
+  dm_cluster* out;                    // sorted records
+  int32_t* rank_of;                   // record -> sorted position, or nullptr
+  unsigned long long* d_sorted;       // device flag: 1 when `out` holds them sorted
+  const unsigned long long* cnt;      // the counter block copied into the readback header,
+  int ncnt, sorted_idx;               // its length, the flag's index in it
+  const unsigned long long* fsh;      // frontier shards for the header, or nullptr
+  dm_raw_record* host_out;            // mapped readback records (device address) and their capacity
+  int64_t host_cap;
+};
+// expect: the last collected count of its kind (sizes the grid).
+int dm_launch_rank_sort(const dm_grid* g, hipStream_t stream, const SortArgs& a, int64_t expect);
 // Listed tiles from which a frontier pass reads fmask instead of state bytes.
 constexpr int64_t kFmaskOnTiles = 8192;
 // tile_free: the listed flag above the free count (<= 4096)
@@ -753,17 +755,13 @@ constexpr int64_t kSlotsPerTile = 4;
 int dm_grow_bucket_sort(dm_grid* g, int64_t n);
 // Row-bucket sort of the raw records (labels of rows [row_base, row_base +
 // rows)): same outputs, readback header and flags as dm_launch_rank_sort.
-int dm_launch_bucket_sort(dm_grid* g, hipStream_t stream, long long* clusters, const long long* sums,
-                          const long long* labels, const unsigned long long* d_count,
-                          int64_t max_records, int64_t row_base, int64_t rows, dm_cluster* out,
-                          int32_t* rank_of, unsigned long long* d_sorted, const unsigned long long* cnt,
-                          int ncnt, int sorted_idx, const unsigned long long* fsh, dm_raw_record* host_out,
-                          int64_t host_cap);
-// cross-band exchange (dm_merge.hip)
+int dm_launch_bucket_sort(dm_grid* g, hipStream_t stream, const SortArgs& a, int64_t row_base, int64_t rows);
+// cross-band exchange (dm_merge.hip): the export reads the band pass's sorted
+// records from slot `r`, the merge writes its own there
 int64_t dm_export_nbytes(int64_t W, int64_t rec_cap);
-int dm_launch_export(dm_grid* g, hipStream_t s, void* d_export, int64_t rec_cap);
-int dm_launch_merge(dm_grid* g, hipStream_t s, const void* d_gathered, int32_t nranks, int64_t rec_cap,
-                    int64_t min_size);
+int dm_launch_export(dm_grid* g, const dm_grid::RbSlot& r, hipStream_t s, void* d_export, int64_t rec_cap);
+int dm_launch_merge(dm_grid* g, dm_grid::RbSlot& r, hipStream_t s, const void* d_gathered, int32_t nranks,
+                    int64_t rec_cap, int64_t min_size);
 // The stream band exports end on and merges run on (dm_exchange_stream).
 inline hipStream_t dm_exchange_stream_of(const dm_grid* g) { return g->overlap ? g->pass_stream : g->stream; }
 int dm_launch_ld06(dm_grid* g, int32_t S, const dm_ld06_point* d_pts, const int64_t* d_offsets,

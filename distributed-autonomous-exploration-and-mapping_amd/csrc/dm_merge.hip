@@ -244,7 +244,8 @@ int grid_for(int64_t n, int threads, int64_t cap) {
 
 int64_t dm_export_nbytes(int64_t W, int64_t rec_cap) { return export_bytes(W, rec_cap); }
 
-int dm_launch_export(dm_grid* g, hipStream_t s, void* d_export, int64_t rec_cap) {
+int dm_launch_export(dm_grid* g, const dm_grid::RbSlot& r, hipStream_t s, void* d_export, int64_t rec_cap) {
+  const dm_grid::FrWs& fw = dm_last_fw(g);
   ExportView v;
   v.W = g->W;
   v.rec_cap = rec_cap;
@@ -252,17 +253,17 @@ int dm_launch_export(dm_grid* g, hipStream_t s, void* d_export, int64_t rec_cap)
   KernelTimer t;
   dm_timer_begin(g, "export", &t, s);
   hipLaunchKernelGGL(k_export, dim3(grid_for(std::max<int64_t>(2 * g->W, rec_cap), 256, 256)), dim3(256), 0,
-                     s, v, g->row0, g->R, g->edge_slot, g->slot_root, g->slot_k, g->rank_of,
-                     g->out_clu, g->cnt, static_cast<uint8_t*>(d_export));
+                     s, v, g->row0, g->R, fw.edge_slot, g->slot_root, g->slot_k, g->rank_of,
+                     r.out_clu.records(), fw.cnt, static_cast<uint8_t*>(d_export));
   dm_timer_end(g, &t);
   DM_HIP(hipGetLastError());
   return DM_OK;
 }
 
-int dm_launch_merge(dm_grid* g, hipStream_t s, const void* d_gathered, int32_t nranks, int64_t rec_cap,
-                    int64_t min_size) {
+int dm_launch_merge(dm_grid* g, dm_grid::RbSlot& r, hipStream_t s, const void* d_gathered, int32_t nranks,
+                    int64_t rec_cap, int64_t min_size) {
   ++g->m_pass;
-  ++g->rb[g->cur_slot].mepoch;  // this merge rewrites the selected slot's records
+  ++r.mepoch;  // this merge rewrites the slot's records
   MGeom m;
   m.v.W = g->W;
   m.v.rec_cap = rec_cap;
@@ -290,12 +291,10 @@ int dm_launch_merge(dm_grid* g, hipStream_t s, const void* d_gathered, int32_t n
                      g->m_acc, g->m_clu, g->m_cnt);
   DM_HIP(hipGetLastError());
   // merged labels are global row-major indices over the whole map
-  const int rc = g->msort_hint > g->sort_min
-      ? dm_launch_bucket_sort(g, s, g->m_clu, nullptr, nullptr, g->m_cnt + M_K, n, 0, g->H, g->m_out, nullptr, g->m_cnt + M_SORTED,
-                              g->m_cnt, 4, M_SORTED, nullptr, g->h_out_dev, g->h_out_cap)
-      : dm_launch_rank_sort(s, g->m_clu, nullptr, nullptr, g->m_cnt + M_K, n, g->p.origin_x, g->p.origin_y,
-                            g->p.resolution, g->m_out, nullptr, g->m_cnt + M_SORTED, g->m_cnt, 4,
-                            M_SORTED, nullptr, g->h_out_dev, g->h_out_cap, g->msort_hint);
+  const SortArgs sa = {g->m_clu, nullptr, nullptr, g->m_cnt + M_K, n, r.m_out, nullptr, g->m_cnt + M_SORTED,
+                       g->m_cnt, 4, M_SORTED, nullptr, r.h_out.records_dev(), r.h_out.capacity()};
+  const int rc = g->msort_hint > g->sort_min ? dm_launch_bucket_sort(g, s, sa, 0, g->H)
+                                             : dm_launch_rank_sort(g, s, sa, g->msort_hint);
   dm_timer_end(g, &t);
   return rc;
 }

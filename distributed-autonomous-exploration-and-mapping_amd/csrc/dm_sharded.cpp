@@ -139,19 +139,13 @@ int sh_refresh_bands(dm_shard_set* s, bool synced) {
   // band 0's own pass would become its goal source (dm_assign_goals reads
   // the last collected result): keep the last merged result's instead
   dm_grid* b0 = s->band[0];
-  const int goal_slot = b0->goal_slot, goal_kind = b0->goal_kind;
-  const uint64_t goal_epoch = b0->goal_epoch, goal_gen = b0->goal_gen;
-  const int64_t goal_n = b0->goal_n;
+  const dm_grid::GoalSource goal = b0->goal;
   for (int r = 0; r < s->P; ++r) {
     int64_t n = 0;
     const int rc = dm_frontiers(s->band[(size_t)r], nullptr, nullptr, nullptr, 0, &n);
     if (rc && rc != DM_ERR_CAPACITY) return rc;
   }
-  b0->goal_slot = goal_slot;
-  b0->goal_kind = goal_kind;
-  b0->goal_epoch = goal_epoch;
-  b0->goal_gen = goal_gen;
-  b0->goal_n = goal_n;
+  b0->goal = goal;
   s->refresh = false;
   return sh_apply_growth(s, synced);
 }

@@ -195,6 +195,31 @@ def test_goals_after_a_failed_pass(oracle_lib):
         assert m.assign_goals(ROBOTS, min_size=1) == assign_goals(exp, ROBOTS, min_size=1)
 
 
+@pytest.mark.parametrize("cap", [None, 1 << 17])
+def test_goals_after_a_synchronous_overflow_sorted_on_the_device(oracle_lib, monkeypatch, cap):
+    """dm_frontiers overflows the slot arrays, grows them and retries inside
+    one call, and the retry is sorted on the device (DM_SORT_MIN=8: the small
+    pass before it hints the row sort).  cap 1 << 17: the caller's buffer holds
+    the result, so that call's device records are the goal source and
+    dm_assign_goals must read what the retry wrote, in the synchronous call's
+    own readback slot, not in a slot of the ring.  cap None: the wrapper's
+    4096-record buffer does not, it calls dm_frontiers again with a larger one,
+    and the goals read that second pass, which ran on the grown arrays."""
+    monkeypatch.setenv("DM_SORT_MIN", "8")  # read at dm_create
+    big, exp = _case("big")
+    small, exp_small = _case("small")
+    assert len(exp_small) > 8
+    with dm.OccupancyMapper(_params()) as m:
+        m.set_state(small)
+        _exact(m.frontiers(), exp_small)
+        m.set_state(big)
+        _exact(m.frontiers(cap=cap), exp)
+        assert m.assign_goals(ROBOTS, min_size=1) == assign_goals(exp, ROBOTS, min_size=1)
+        m.frontiers_begin()
+        _exact(m.frontiers_end(), exp)
+        _ring_is_empty(m)
+
+
 def test_hint_cliffs_pipelined(oracle_lib):
     """One handle, overlap on, every pass a begin / end pair, through maps
     whose cluster and tile counts jump both ways: the grids, kernels and sorts

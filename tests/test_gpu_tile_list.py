@@ -1,4 +1,4 @@
-"""GPU: the persistent frontier tile list (dm_internal.h `ftiles`): every
+"""GPU: the persistent frontier tile list (dm_internal.h `flist`): every
 tile that has held a free cell since the last rebuild, appended by the
 integrate apply when a tile's free count first rises above 0 (listed flag in
 `tile_free`), rebuilt in tile order by k_list_tiles after bulk writes

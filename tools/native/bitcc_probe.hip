@@ -122,16 +122,18 @@ extern "C" int dm_probe_bitcc(dm_grid* g, int reps, double* ms, unsigned long lo
   PROBE_HIP(hipMalloc(&tot, 32 * sizeof(unsigned long long)));
   PROBE_HIP(hipMemset(tot, 0, 32 * sizeof(unsigned long long)));
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((nft + 3) / 4, 65536));
+  const dm_grid::FrWs& fw = dm_last_fw(g);
+  const int32_t* ftiles = g->flist[g->flist_cur];
   hipEvent_t e0, e1;
   PROBE_HIP(hipEventCreate(&e0));
   PROBE_HIP(hipEventCreate(&e1));
-  hipLaunchKernelGGL(k_probe_slot_sums, dim3(256), dim3(256), 0, g->stream, g->fsh, slot_per, g->slot_label,
+  hipLaunchKernelGGL(k_probe_slot_sums, dim3(256), dim3(256), 0, g->stream, fw.fsh, slot_per, g->slot_label,
                      g->slot_own, tot + 8);
-  hipLaunchKernelGGL(k_probe_bitcc, dim3(grid), dim3(256), 0, g->stream, (int64_t)g->W, (int32_t)g->TX, (int64_t)g->row0, g->fbits, g->ftiles, nft, tot);
+  hipLaunchKernelGGL(k_probe_bitcc, dim3(grid), dim3(256), 0, g->stream, (int64_t)g->W, (int32_t)g->TX, (int64_t)g->row0, fw.fbits, ftiles, nft, tot);
   PROBE_HIP(hipStreamSynchronize(g->stream));
   PROBE_HIP(hipEventRecord(e0, g->stream));
   for (int r = 0; r < reps; ++r)
-    hipLaunchKernelGGL(k_probe_bitcc, dim3(grid), dim3(256), 0, g->stream, (int64_t)g->W, (int32_t)g->TX, (int64_t)g->row0, g->fbits, g->ftiles, nft,
+    hipLaunchKernelGGL(k_probe_bitcc, dim3(grid), dim3(256), 0, g->stream, (int64_t)g->W, (int32_t)g->TX, (int64_t)g->row0, fw.fbits, ftiles, nft,
                        tot + 16);
   PROBE_HIP(hipEventRecord(e1, g->stream));
   PROBE_HIP(hipEventSynchronize(e1));
