@@ -98,66 +98,50 @@ int grow_integrate(dm_grid* g, int32_t S, int32_t N) {
   // pieces per beam: <= 2 per 64 steps + 8, and every chunk adds <= 3
   const int64_t per_beam = 2 * (g->nmax / DM_TILE) + 8 + 4 * chunks;
   const int64_t blocks = ceil_div(nb * chunks, 256);  // k_beam_prep / k_scatter workgroups
-  if (nb > g->beams_cap || blocks > g->blk_cap) {
-    const int64_t nbc = std::max<int64_t>(nb, g->beams_cap);
-    const int64_t bc = std::max<int64_t>(blocks, g->blk_cap);
-    int rc = 0;
-    for (auto& w : g->iw) {
-      if (!rc) rc = w.beams.alloc(nbc, "beams");
-      if (!rc) rc = w.blk_hist.alloc(bc * 1024, "per-block tile histograms");
-      if (!rc) rc = w.blk_n.alloc(bc, "per-block histogram sizes");
-    }
-    if (rc) { g->beams_cap = g->blk_cap = 0; return rc; }
-    g->beams_cap = nbc;
-    g->blk_cap = bc;
-  }
+  using Ws = dm_grid::IntWs;
+  // grows `cap` to n, when n exceeds it, by alloc(set) on both workspace sets
+  auto grow = [g](GroupCap& cap, int64_t n, auto alloc) -> int {
+    if (n <= cap) return DM_OK;
+    return cap.grow(n, [&] {
+      int rc = DM_OK;
+      for (auto& w : g->iw)
+        if (!rc) rc = alloc(w);
+      return rc;
+    });
+  };
+  int rc = grow(g->beams_cap, nb, [&](Ws& w) { return w.beams.alloc(nb, "beams"); });
+  if (!rc)
+    rc = grow(g->blk_cap, blocks, [&](Ws& w) {
+      const int rc = w.blk_hist.alloc(blocks * 1024, "per-block tile histograms");
+      return rc ? rc : w.blk_n.alloc(blocks, "per-block histogram sizes");
+    });
   const int64_t segs = nb * per_beam;
-  if (segs > g->segs_cap) {
-    for (auto& w : g->iw) {
-      int rc = w.pieces.alloc(segs, "ray pieces");
-      if (rc) { g->segs_cap = 0; return rc; }
-    }
-    g->segs_cap = segs;
-  }
+  if (!rc) rc = grow(g->segs_cap, segs, [&](Ws& w) { return w.pieces.alloc(segs, "ray pieces"); });
   const int64_t side = ceil_div(2 * (int64_t)g->nmax + 1, DM_TILE) + 1;
-  int64_t act = std::min<int64_t>(g->NT, std::min<int64_t>(segs, (int64_t)S * side * side));
-  if (act < 1) act = 1;
-  if (act > g->act_cap) {
-    int rc = 0;
-    for (auto& w : g->iw) {
-      if (!rc) rc = w.act_raw.alloc(act * kShards, "first-touch lists");
-      if (!rc) rc = w.litems.alloc(act, "light work items");
-    }
-    if (rc) { g->act_cap = 0; return rc; }
-    g->act_cap = act;
-  }
+  const int64_t act = std::max<int64_t>(1, std::min<int64_t>({g->NT, segs, (int64_t)S * side * side}));
+  if (!rc)
+    rc = grow(g->act_cap, act, [&](Ws& w) {
+      const int rc = w.act_raw.alloc(act * kShards, "first-touch lists");
+      return rc ? rc : w.litems.alloc(act, "light work items");
+    });
+  if (rc) return rc;
   // work items of medium and heavy tiles (exact bounds: such a tile has
   // more than kIntegrateChunk pieces, its items ceil(pieces / chunk) <=
   // pieces / chunk + 1), heavy tiles (more than kIntegrateMedium pieces)
   const int64_t chunk = kIntegrateChunk;
   const int64_t heavy = std::max<int64_t>(1, std::min<int64_t>(g->act_cap, segs / (kIntegrateMedium + 1) + 1));
   const int64_t hitems = segs / chunk + segs / (chunk + 1) + 2;
-  if (hitems > g->hitem_cap) {
-    for (auto& w : g->iw) {
-      int rc = w.hitems.alloc(hitems, "heavy work items");
-      if (rc) { g->hitem_cap = 0; return rc; }
-    }
-    g->hitem_cap = hitems;
-  }
-  if (heavy > g->heavy_cap) {
-    for (auto& w : g->iw) {
+  rc = grow(g->hitem_cap, hitems, [&](Ws& w) { return w.hitems.alloc(hitems, "heavy work items"); });
+  if (!rc)
+    rc = grow(g->heavy_cap, heavy, [&](Ws& w) {
       int rc = w.heavy_list.alloc(heavy, "heavy tiles");
-      if (!rc) rc = w.slabs.alloc(heavy * 2 * DM_TILE * DM_TILE, "heavy-tile slabs");
-      if (!rc) rc = w.heavy_done.alloc(heavy, "heavy-tile item tickets");
-      if (rc) { g->heavy_cap = 0; return rc; }
-      DM_HIP(hipMemset(w.slabs, 0, sizeof(uint32_t) * (size_t)(heavy * 2 * DM_TILE * DM_TILE)));
-      DM_HIP(hipMemset(w.heavy_done, 0, sizeof(int32_t) * (size_t)heavy));
-    }
-    g->heavy_cap = heavy;
-  }
+      if (!rc) rc = w.slabs.alloc_zeroed(heavy * 2 * DM_TILE * DM_TILE, "heavy-tile slabs");
+      if (!rc) rc = w.heavy_done.alloc_zeroed(heavy, "heavy-tile item tickets");
+      return rc;
+    });
+  if (rc) return rc;
   if (2 * (int64_t)N > g->trig.size()) {
-    int rc = g->trig.alloc(2 * (int64_t)N, "trig table");
-    if (rc) return rc;
+    if ((rc = g->trig.alloc(2 * (int64_t)N, "trig table"))) return rc;
     g->trig_n = -1;
   }
   return DM_OK;
@@ -185,48 +169,46 @@ int ensure_trig(dm_grid* g, int32_t N, float amin, float inc) {
 // Record workspace of the row-bucket sort (k_bs_*): >= every record count a
 // sort may be asked to order (band slot_cap, merge m_cap).
 int dm_grow_bucket_sort(dm_grid* g, int64_t n) {
-  if (n <= g->bs_cap) return DM_OK;
-  int rc = g->bs_key.alloc(n, "row-sort keys");
-  if (!rc) rc = g->bs_key2.alloc(n, "row-sort keys");
-  if (!rc) rc = g->bs_idx.alloc(n, "row-sort indices");
-  if (!rc) rc = g->bs_idx2.alloc(n, "row-sort indices");
-  if (!rc && g->rs_rows < g->H) {  // rows of the whole map (merges sort over H rows)
-    rc = g->rs_cnt.alloc(g->H, "row-sort counters");
-    if (!rc) rc = g->rs_off.alloc(g->H + 1, "row-sort offsets");
-    if (!rc) rc = g->rs_status.alloc(g->H / 8192 + 2, "row-sort workgroup totals");
-    if (!rc) {
-      DM_HIP(hipMemset(g->rs_cnt, 0, sizeof(int32_t) * (size_t)g->H));
-      g->rs_rows = g->H;
-    }
-  }
-  if (rc) { g->bs_cap = 0; return rc; }
-  g->bs_cap = n;
-  return DM_OK;
+  int rc = DM_OK;
+  if (g->rs_rows < g->H)  // rows of the whole map (merges sort over H rows)
+    rc = g->rs_rows.grow(g->H, [&] {
+      int rc = g->rs_cnt.alloc_zeroed(g->H, "row-sort counters");
+      if (!rc) rc = g->rs_off.alloc(g->H + 1, "row-sort offsets");
+      if (!rc) rc = g->rs_status.alloc(g->H / 8192 + 2, "row-sort workgroup totals");
+      return rc;
+    });
+  if (rc || n <= g->bs_cap) return rc;
+  return g->bs_cap.grow(n, [&] {
+    int rc = g->bs_key.alloc(n, "row-sort keys");
+    if (!rc) rc = g->bs_key2.alloc(n, "row-sort keys");
+    if (!rc) rc = g->bs_idx.alloc(n, "row-sort indices");
+    if (!rc) rc = g->bs_idx2.alloc(n, "row-sort indices");
+    return rc;
+  });
 }
 
-namespace {
-
-int grow_slots(dm_grid* g, int64_t need) {
+int dm_grow_slots(dm_grid* g, int64_t need) {
   int64_t cap = std::max<int64_t>(need, 2 * g->slot_cap);
   if (cap < (1 << 16)) cap = 1 << 16;
   cap = ceil_div(cap, kShards) * kShards;  // kShards equal regions (k_frontier_tile)
-  int rc = g->slot_label.alloc(cap, "slot labels");
-  for (auto& f : g->fw)
-    if (!rc) rc = f.slot_parent.alloc(cap, "slot parents");
-  if (!rc) rc = g->slot_root.alloc(cap, "slot roots");
-  if (!rc) rc = g->slot_own.alloc(3 * cap, "slot sums");
-  if (!rc) rc = g->slot_acc.alloc(3 * cap, "slot totals");
-  if (!rc) rc = g->clusters.alloc(4 * cap, "clusters");
-  for (int sl = 0; sl <= dm_grid::kRbSlots && !rc; ++sl)  // one per readback slot
-    rc = g->rb[sl].out_clu.alloc(cap, "sorted clusters");
-  ++g->rb_gen;
-  if (!rc) rc = g->slot_k.alloc(cap, "slot cluster index");
-  if (!rc) rc = g->rank_of.alloc(cap, "cluster sorted position");
-  if (!rc) rc = dm_grow_bucket_sort(g, cap);
-  if (rc) return rc;
-  g->slot_cap = cap;
-  return DM_OK;
+  ++g->rb_gen;  // the readback slots' device records move
+  return g->slot_cap.grow(cap, [&] {
+    int rc = g->slot_label.alloc(cap, "slot labels");
+    for (auto& f : g->fw)
+      if (!rc) rc = f.slot_parent.alloc(cap, "slot parents");
+    if (!rc) rc = g->slot_root.alloc(cap, "slot roots");
+    if (!rc) rc = g->slot_own.alloc(3 * cap, "slot sums");
+    if (!rc) rc = g->slot_acc.alloc(3 * cap, "slot totals");
+    if (!rc) rc = g->clusters.alloc(4 * cap, "clusters");
+    for (auto& r : g->rb)  // one per readback slot
+      if (!rc) rc = r.out_clu.alloc(cap, "sorted clusters");
+    if (!rc) rc = g->slot_k.alloc(cap, "slot cluster index");
+    if (!rc) rc = g->rank_of.alloc(cap, "cluster sorted position");
+    return rc ? rc : dm_grow_bucket_sort(g, cap);
+  });
 }
+
+namespace {
 
 // Grow readback slot `r`'s mapped buffer (no pass of that slot in flight).
 int grow_host_out(dm_grid::RbSlot& r, int64_t need) {
@@ -287,17 +269,16 @@ void note_goal_source(dm_grid* g, const dm_grid::RbSlot& r, int kind, int64_t n)
 
 int grow_merge(dm_grid* g, int64_t n) {
   if (n <= g->m_cap) return DM_OK;
-  int rc = g->m_parent.alloc(n, "merge parents");
-  if (!rc) rc = g->m_label.alloc(n, "merge labels");
-  if (!rc) rc = g->m_acc.alloc(3 * n, "merge sums");
-  if (!rc) rc = g->m_clu.alloc(4 * n, "merged clusters");
-  for (int sl = 0; sl <= dm_grid::kRbSlots && !rc; ++sl)
-    rc = g->rb[sl].m_out.alloc(n, "merged clusters (sorted)");
-  ++g->rb_gen;
-  if (!rc) rc = dm_grow_bucket_sort(g, n);
-  if (rc) { g->m_cap = 0; return rc; }
-  g->m_cap = n;
-  return DM_OK;
+  ++g->rb_gen;  // the readback slots' device records move
+  return g->m_cap.grow(n, [&] {
+    int rc = g->m_parent.alloc(n, "merge parents");
+    if (!rc) rc = g->m_label.alloc(n, "merge labels");
+    if (!rc) rc = g->m_acc.alloc(3 * n, "merge sums");
+    if (!rc) rc = g->m_clu.alloc(4 * n, "merged clusters");
+    for (auto& r : g->rb)
+      if (!rc) rc = r.m_out.alloc(n, "merged clusters (sorted)");
+    return rc ? rc : dm_grow_bucket_sort(g, n);
+  });
 }
 
 }  // namespace
@@ -400,15 +381,15 @@ void dm_timer_begin(dm_grid* g, const char* name, KernelTimer* t, hipStream_t s)
   if (!g->profile) return;
   t->name = name;
   t->stream = s ? s : g->stream;
-  (void)hipEventCreate(&t->start);
-  (void)hipEventCreate(&t->stop);
+  (void)t->start.create(hipEventDefault);
+  (void)t->stop.create(hipEventDefault);
   (void)hipEventRecord(t->start, t->stream);
 }
 
 void dm_timer_end(dm_grid* g, KernelTimer* t) {
   if (!g->profile) return;
   (void)hipEventRecord(t->stop, t->stream);
-  g->pending.push_back(*t);
+  g->pending.push_back(std::move(*t));
   if (g->pending.size() > 4096) {
     int32_t n = 0;
     (void)dm_profile_read(g, nullptr, 0, &n);
@@ -478,10 +459,8 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   for (auto& w : g->iw) {
     if ((rc = w.tile_count.alloc(g->NT, "tile counts"))) return fail(rc);
     if ((rc = w.tile_cur.alloc(g->NT, "tile bin cursors"))) return fail(rc);
-    if ((rc = w.cnt.alloc(CNT_N, "integrate counters"))) return fail(rc);
-    if ((rc = w.sh.alloc(kShards * kShardWords, "integrate shard counters"))) return fail(rc);
-    DM_HIP(hipMemset(w.cnt, 0, sizeof(unsigned long long) * CNT_N));
-    DM_HIP(hipMemset(w.sh, 0, sizeof(unsigned long long) * kShards * kShardWords));
+    if ((rc = w.cnt.alloc_zeroed(CNT_N, "integrate counters"))) return fail(rc);
+    if ((rc = w.sh.alloc_zeroed(kShards * kShardWords, "integrate shard counters"))) return fail(rc);
   }
   if ((rc = g->tile_free.alloc(g->NT, "tile free counts"))) return fail(rc);
   if ((rc = g->fmask.alloc(g->NT * DM_TILE * 16, "tile free / unknown bit rows"))) return fail(rc);
@@ -513,32 +492,24 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   if (const char* mb = getenv("DM_MATCH_GLOBAL_BATCH"))
     g->mg_batch = std::min<int64_t>(std::max<int64_t>(1, atoll(mb)), dm_grid::kMgExhaustiveBatch);
   for (auto& f : g->fw) {
-    e = hipEventCreateWithFlags(f.ev_split.put(), hipEventDisableTiming | hipEventDisableSystemFence);
-    if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
-    if ((rc = f.cnt.alloc(CNT_N, "frontier counters"))) return fail(rc);
-    DM_HIP(hipMemset(f.cnt, 0, sizeof(unsigned long long) * CNT_N));
-    if ((rc = f.fsh.alloc(kShards * kShardWords, "frontier shard counters"))) return fail(rc);
-    DM_HIP(hipMemset(f.fsh, 0, sizeof(unsigned long long) * kShards * kShardWords));
+    if ((rc = f.ev_split.create(hipEventDisableTiming | hipEventDisableSystemFence))) return fail(rc);
+    if ((rc = f.cnt.alloc_zeroed(CNT_N, "frontier counters"))) return fail(rc);
+    if ((rc = f.fsh.alloc_zeroed(kShards * kShardWords, "frontier shard counters"))) return fail(rc);
     if ((rc = f.big_tiles.alloc(g->NT, "frontier big tiles"))) return fail(rc);
     if ((rc = f.fbits.alloc(g->NT * DM_TILE, "frontier bit rows"))) return fail(rc);
     if ((rc = f.edge_slot.alloc(2 * g->W, "edge slots"))) return fail(rc);
   }
-  if ((rc = g->fl_n.alloc(48, "frontier list lengths"))) return fail(rc);
+  if ((rc = g->fl_n.alloc_zeroed(48, "frontier list lengths"))) return fail(rc);
   for (int i = 0; i < 2; ++i) {
     if ((rc = g->flist[i].alloc(g->NT, "frontier tile list"))) return fail(rc);
-    if ((rc = g->flist_n[i].alloc(16, "frontier tile list length"))) return fail(rc);
-    DM_HIP(hipMemset(g->flist_n[i], 0, sizeof(unsigned long long) * 16));
+    if ((rc = g->flist_n[i].alloc_zeroed(16, "frontier tile list length"))) return fail(rc);
   }
-  DM_HIP(hipMemset(g->fl_n, 0, sizeof(unsigned long long) * 48));
-  if ((rc = g->bits_flag.alloc(16, "bit-row hand-off word"))) return fail(rc);
-  DM_HIP(hipMemset(g->bits_flag, 0, sizeof(unsigned long long) * 16));
-  if ((rc = g->fe_flag.alloc(16, "front-end completion words"))) return fail(rc);
-  DM_HIP(hipMemset(g->fe_flag, 0, sizeof(unsigned long long) * 16));
+  if ((rc = g->bits_flag.alloc_zeroed(16, "bit-row hand-off word"))) return fail(rc);
+  if ((rc = g->fe_flag.alloc_zeroed(16, "front-end completion words"))) return fail(rc);
   if ((rc = g->border.alloc(g->NT * 256, "frontier borders"))) return fail(rc);
   // [0, 4 NT): the dense passes' pair hand-off words; [4 NT, 8 NT): the
   // sparse passes' per-edge stamps (dm_frontier.hip, EDGE tile kernels)
-  if ((rc = g->rel.alloc(8 * g->NT, "tile-edge hand-off words"))) return fail(rc);
-  DM_HIP(hipMemset(g->rel, 0, sizeof(unsigned long long) * 8 * (size_t)g->NT));
+  if ((rc = g->rel.alloc_zeroed(8 * g->NT, "tile-edge hand-off words"))) return fail(rc);
   if ((rc = g->edge_label.alloc(2 * g->W, "edge labels"))) return fail(rc);
   if ((rc = g->halo.alloc(2 * g->W, "halo rows"))) return fail(rc);
   // slot arrays sized for the map up front (a pass that overflows them has
@@ -546,15 +517,14 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   // tile, ~276 B each (C3: 72 MB; a 65536^2 map: 1.2 GB of its 288 GB).  A
   // C5 row band under 64 x 4096-beam fans holds 0.81 clusters per tile and
   // more than two slots per tile (test_gpu_c5_full.py).
-  if ((rc = grow_slots(g, std::max<int64_t>(1 << 16, kSlotsPerTile * g->NT)))) return fail(rc);
+  if ((rc = dm_grow_slots(g, kSlotsPerTile * g->NT))) return fail(rc);
   for (auto& r : g->rb)
     if ((rc = grow_host_out(r, 1 << 14))) return fail(rc);
   if ((rc = g->h_cnt.alloc(2 * CNT_N + 1, hipHostMallocDefault, "counters"))) return fail(rc);
   if ((rc = g->h_sh.alloc(2 * kShards * kShardWords, hipHostMallocDefault, "shard counters"))) return fail(rc);
   if ((rc = g->m_cnt.alloc(4, "merge counters"))) return fail(rc);
   if ((rc = g->h_mcnt.alloc(4, hipHostMallocDefault, "merge counters"))) return fail(rc);
-  if ((rc = g->h_hint.alloc(16, hipHostMallocMapped | hipHostMallocCoherent, "work hint"))) return fail(rc);
-  memset(g->h_hint, 0, sizeof(unsigned long long) * 16);
+  if ((rc = g->h_hint.alloc_zeroed(16, hipHostMallocMapped | hipHostMallocCoherent, "work hint"))) return fail(rc);
   e = hipDeviceGetAttribute(&g->n_cu, hipDeviceAttributeMultiprocessorCount, device);
   if (e != hipSuccess) return fail(dm_hip_check(e, "hipDeviceGetAttribute(multiprocessor count)"));
   // Stream priorities: the map chain (accumulation, frontier bit rows) and
@@ -564,32 +534,22 @@ int dm_create(dm_grid** out, const dm_params* p, int device) {
   // combination and of CU-masked streams: DESIGN.md §3.3).
   int prio_lo = 0, prio_hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-  e = hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, prio_hi);
-  if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate"));
-  g->own_stream = true;
-  e = hipStreamCreateWithPriority(g->fe_stream.put(), hipStreamNonBlocking, prio_lo);
-  if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate(front-end)"));
-  e = hipStreamCreateWithPriority(g->pass_stream.put(), hipStreamNonBlocking, prio_hi);
-  if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate(pass)"));
-  e = hipStreamCreateWithPriority(g->big_stream.put(), hipStreamNonBlocking, prio_hi);
-  if (e != hipSuccess) return fail(dm_hip_check(e, "hipStreamCreate(big)"));
+  if ((rc = g->owned_stream.create(hipStreamNonBlocking, prio_hi))) return fail(rc);
+  g->stream = g->owned_stream;
+  if ((rc = g->fe_stream.create(hipStreamNonBlocking, prio_lo))) return fail(rc);
+  if ((rc = g->pass_stream.create(hipStreamNonBlocking, prio_hi))) return fail(rc);
+  if ((rc = g->big_stream.create(hipStreamNonBlocking, prio_hi))) return fail(rc);
   // ev_fe / ev_free only order the two streams on the device: no system-
   // scope fence (no host-visible cache writeback at every step).  The host
   // waits on a readback slot's event and then reads mapped host memory:
   // default fences.
   for (DevEvent* ev : {&g->ev_fe, &g->ev_bits[0], &g->ev_bits[1], &g->iw[0].ev_free, &g->iw[1].ev_free,
-                         &g->ev_bigfork, &g->ev_big, &g->flist_ev[0], &g->flist_ev[1]}) {
-    e = hipEventCreateWithFlags(ev->put(), hipEventDisableTiming | hipEventDisableSystemFence);
-    if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
-  }
-  for (auto& r : g->rb) {
-    e = hipEventCreateWithFlags(r.ev.put(), hipEventDisableTiming);
-    if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
-  }
-  for (DevEvent& ev : g->ev_pose) {  // host waits on these before reusing a staging buffer
-    e = hipEventCreateWithFlags(ev.put(), hipEventDisableTiming);
-    if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
-  }
+                         &g->ev_bigfork, &g->ev_big, &g->flist_ev[0], &g->flist_ev[1]})
+    if ((rc = ev->create(hipEventDisableTiming | hipEventDisableSystemFence))) return fail(rc);
+  for (auto& r : g->rb)
+    if ((rc = r.ev.create(hipEventDisableTiming))) return fail(rc);
+  for (DevEvent& ev : g->ev_pose)  // host waits on these before reusing a staging buffer
+    if ((rc = ev.create(hipEventDisableTiming))) return fail(rc);
 
   if ((rc = dm_reset(g))) return fail(rc);
   *out = g;
@@ -601,8 +561,6 @@ int dm_destroy(dm_grid* g) {
   if (!g) return DM_OK;
   (void)hipSetDevice(g->device);
   (void)dm_sync_all(g);
-  for (auto& t : g->pending) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
-  if (g->stream && g->own_stream) (void)hipStreamDestroy(g->stream);
   delete g;
   return DM_OK;
 }
@@ -865,7 +823,7 @@ int dm_frontiers(dm_grid* g, uint8_t* mask, int64_t* labels, dm_cluster* out, in
   for (int attempt = 0; attempt < 8; ++attempt) {
     rc = dm_launch_frontiers(g, r, mask != nullptr, labels != nullptr, &n, &copied);
     if (rc != DM_ERR_CAPACITY) break;
-    if ((rc = grow_slots(g, n + n / 2 + 1024))) return rc;
+    if ((rc = dm_grow_slots(g, n + n / 2 + 1024))) return rc;
     rc = DM_ERR_CAPACITY;
   }
   if (rc) return rc == DM_ERR_CAPACITY ? dm_set_error(rc, "frontier slot arrays kept overflowing") : rc;
@@ -1110,7 +1068,7 @@ int dm_frontiers_end(dm_grid* g, dm_cluster* out, int64_t cap, int64_t* n_out) {
   rc = dm_frontiers_readback(g, r, &n, &copied);
   if (rc == DM_ERR_CAPACITY) {
     retire_oldest(g);
-    if ((rc = grow_slots(g, n + n / 2 + 1024))) return rc;
+    if ((rc = dm_grow_slots(g, n + n / 2 + 1024))) return rc;
     if (n_out) *n_out = 0;
     return dm_set_error(DM_ERR_INCOMPLETE, "frontier slot arrays overflowed (grown now): this pass "
                                            "has no result, run dm_frontiers");
@@ -1337,12 +1295,11 @@ int dm_set_stream(dm_grid* g, void* stream) {
   if (rc || (rc = use_device(g))) return rc;
   DM_HIP(dm_sync_all(g));
   if (stream) {
-    if (g->own_stream && g->stream) (void)hipStreamDestroy(g->stream);
+    g->owned_stream.reset();
     g->stream = (hipStream_t)stream;
-    g->own_stream = false;
-  } else if (!g->own_stream) {
-    DM_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    g->own_stream = true;
+  } else if (!g->owned_stream) {
+    if ((rc = g->owned_stream.create(hipStreamNonBlocking, 0))) return rc;  // the default priority
+    g->stream = g->owned_stream;
   }
   return DM_OK;
 }
@@ -1367,12 +1324,10 @@ int dm_profile_read(dm_grid* g, dm_kernel_stat* out, int32_t cap, int32_t* n_out
   if (g && g->sh) return dm_sh_profile_read(g, out, cap, n_out);
   int rc = check_grid(g);
   if (rc || (rc = use_device(g))) return rc;
-  DM_HIP(hipStreamSynchronize(g->stream));
+  DM_HIP(dm_sync_all(g));  // timers are recorded on all four streams
   for (auto& t : g->pending) {
     float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, t.start, t.stop);
-    (void)hipEventDestroy(t.start);
-    (void)hipEventDestroy(t.stop);
+    if (hipEventElapsedTime(&ms, t.start, t.stop) != hipSuccess) continue;  // not a launch of 0 ms
     dm_kernel_stat* s = nullptr;
     for (auto& e : g->stats)
       if (t.name == e.name) s = &e;

@@ -1,13 +1,17 @@
 // dm_buf.h — the owners of what a handle allocates: device arrays, pinned
-// host arrays, events, streams.  Each frees in its destructor, cannot be
-// copied, can be moved, and converts to the raw pointer / handle it owns, so
-// the code that uses one reads as it would with the raw thing.  The only
-// hipMalloc / hipFree / hipHostMalloc / hipHostFree calls of libdm are here.
+// host arrays, events, streams, timers, and the capacity of a group of arrays.
+// Each frees in its destructor, cannot be copied, can be moved, and converts
+// to the raw pointer / handle it owns, so the code that uses one reads as it
+// would with the raw thing.  libdm allocates and frees memory, and creates and
+// destroys events and streams, only here.
 // Plain C++ over the HIP runtime API: no device code (tests/native/buf_main.cpp
 // builds it with g++ against counting fakes of those calls).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
+#include <string.h>
+
+#include <string>
 
 #include "../../include/dm.h"
 
@@ -47,6 +51,14 @@ class DevBuf {
     }
     n_ = n;
     return DM_OK;
+  }
+  // alloc, then hipMemset to 0 (done on return); a failed fill is DM_ERR_HIP and an empty buffer too
+  int alloc_zeroed(int64_t n, const char* what, int device = -1) {
+    if (int rc = alloc(n, what, device)) return rc;
+    const hipError_t e = hipMemset(p_, 0, sizeof(T) * (size_t)n_);
+    if (e == hipSuccess) return DM_OK;
+    reset();
+    return dm_set_error(DM_ERR_HIP, "hipMemset(%s): %s (%d)", what, hipGetErrorString(e), (int)e);
   }
   // At least n elements: nothing when it already holds them, else alloc.
   int ensure(int64_t n, const char* what, int device = -1) { return n <= n_ ? DM_OK : alloc(n, what, device); }
@@ -99,6 +111,11 @@ class HostBuf {
     n_ = n;
     return DM_OK;
   }
+  int alloc_zeroed(int64_t n, unsigned flags, const char* what) {
+    if (int rc = alloc(n, flags, what)) return rc;
+    memset(p_, 0, sizeof(T) * (size_t)n_);
+    return DM_OK;
+  }
   int ensure(int64_t n, unsigned flags, const char* what) { return n <= n_ ? DM_OK : alloc(n, flags, what); }
   void reset() {
     if (p_) (void)hipHostFree(p_);
@@ -134,8 +151,28 @@ struct Headed {
   auto records_dev() const { return buf.dev() ? buf.dev() + K : nullptr; }  // mapped HostBuf only
 };
 
-// Owning event / stream: created by the caller's choice of call through
-// put(), destroyed with the owner.
+// The capacity kept beside a group of arrays that grow together.  Only a
+// growth sets it, so it never names a size one of the arrays does not have.
+class GroupCap {
+ public:
+  GroupCap& operator=(const GroupCap&) = delete;
+  operator int64_t() const { return n_; }
+  // alloc_all() allocates every array of the group for n.  The capacity is 0
+  // while it runs and afterwards n only if it returned DM_OK.
+  template <class F>
+  int grow(int64_t n, F&& alloc_all) {
+    n_ = 0;
+    const int rc = alloc_all();
+    if (rc == DM_OK) n_ = n;
+    return rc;
+  }
+
+ private:
+  int64_t n_ = 0;
+};
+
+// Owning event / stream, destroyed with the owner; DevEvent and DevStream
+// below add the call that creates one.
 template <class H, hipError_t (*Destroy)(H)>
 class HipHandle {
  public:
@@ -156,16 +193,35 @@ class HipHandle {
     if (h_) (void)Destroy(h_);
     h_ = nullptr;
   }
-  // where a hipEventCreate* / hipStreamCreate* call stores the new handle
-  // (destroys the one held)
-  H* put() {
-    reset();
-    return &h_;
-  }
   operator H() const { return h_; }
 
- private:
+ protected:
+  // after a creation call stored into h_: DM_OK, or a null handle and the error in dm_hip_check's words
+  int created(hipError_t e, const char* call) {
+    if (e == hipSuccess) return DM_OK;
+    h_ = nullptr;
+    return dm_set_error(e == hipErrorOutOfMemory ? DM_ERR_OOM : DM_ERR_HIP, "%s: %s (%d)", call,
+                        hipGetErrorString(e), (int)e);
+  }
   H h_ = nullptr;
 };
-using DevEvent = HipHandle<hipEvent_t, hipEventDestroy>;
-using DevStream = HipHandle<hipStream_t, hipStreamDestroy>;
+// create() destroys the handle held, if any, first.
+struct DevEvent : HipHandle<hipEvent_t, hipEventDestroy> {
+  int create(unsigned flags) {
+    reset();
+    return created(hipEventCreateWithFlags(&h_, flags), "hipEventCreateWithFlags");
+  }
+};
+struct DevStream : HipHandle<hipStream_t, hipStreamDestroy> {
+  int create(unsigned flags, int priority) {
+    reset();
+    return created(hipStreamCreateWithPriority(&h_, flags, priority), "hipStreamCreateWithPriority");
+  }
+};
+
+// One timed launch (dm_timer_begin / _end): the events around it on `stream`, dropped by dm_profile_read.
+struct KernelTimer {
+  std::string name;
+  DevEvent start, stop;
+  hipStream_t stream = nullptr;
+};

@@ -1915,6 +1915,9 @@ int dm_launch_bucket_sort(dm_grid* g, hipStream_t stream, const SortArgs& a, int
 // the cross-band export (dm_merge.hip).
 int dm_enqueue_frontiers(dm_grid* g, dm_grid::RbSlot& r, bool want_mask, bool want_labels, bool split,
                          hipStream_t* end_stream) {
+  // a failed growth left no slot arrays: the create-time size again
+  if (g->slot_cap == 0)
+    if (int rc = dm_grow_slots(g, kSlotsPerTile * g->NT)) return rc;
   const FGeom fg = make_fgeom(g, want_mask, want_labels);
   const int64_t cells = g->R * g->W;
   // the bit rows run on g->stream after everything shared with
@@ -1987,14 +1990,9 @@ int dm_enqueue_frontiers(dm_grid* g, dm_grid::RbSlot& r, bool want_mask, bool wa
   auto* const wave_kernel = edge ? k_frontier_tile<true> : k_frontier_tile<false>;
   // the label cache, with the first pass that launches the workgroup kernel
   // (every pass does); without the memory the passes run uncached
-  if (g->fcache_mode == 1 && !g->fcache) {
-    const int64_t words = kFcWords * g->NT;
-    if (g->fcache.alloc(words, "label cache") != DM_OK ||
-        hipMemsetAsync(g->fcache, 0, sizeof(uint64_t) * (size_t)words, g->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      g->fcache.reset();
-      g->fcache_mode = 0;
-    }
+  if (g->fcache_mode == 1 && !g->fcache && g->fcache.alloc_zeroed(kFcWords * g->NT, "label cache") != DM_OK) {
+    (void)hipGetLastError();
+    g->fcache_mode = 0;
   }
   dm_timer_begin(g, "frontier_bits", &t);
   DM_LAUNCH(k_frontier_bits, dim3(bits_grid), dim3(kFW * 64), 0, g->stream, fg, g->state, g->halo, g->fmask,

@@ -449,10 +449,8 @@ extern "C" {
 static int ensure_plan(dm_grid* g) {
   if (g->plan_cost) return DM_OK;  // allocated last: everything else is there too
   int rc = DM_OK;
-  if (!g->h_plan) {
-    if ((rc = g->h_plan.alloc(16, hipHostMallocMapped | hipHostMallocCoherent, "plan rounds"))) return rc;
-    memset(g->h_plan, 0, sizeof(unsigned long long) * 16);
-  }
+  if (!g->h_plan && (rc = g->h_plan.alloc_zeroed(16, hipHostMallocMapped | hipHostMallocCoherent, "plan rounds")))
+    return rc;
   const int64_t rows = g->NT * DM_TILE;
   if ((rc = g->plan_trav.alloc(rows, "traversable bit rows"))) return rc;
   if ((rc = g->plan_travs.alloc(rows, "traversable bit rows with sources"))) return rc;
@@ -460,20 +458,19 @@ static int ensure_plan(dm_grid* g) {
   if ((rc = g->plan_list[1].alloc(g->NT, "plan tile list"))) return rc;
   if ((rc = g->plan_stamp.alloc(g->NT, "plan tile stamps"))) return rc;
   if ((rc = g->plan_len.alloc(4, "plan list lengths"))) return rc;
-  if ((rc = g->plan_stat.alloc(8, "plan statistics"))) return rc;
-  DM_HIP(hipMemset(g->plan_stat, 0, sizeof(unsigned long long) * 8));
+  if ((rc = g->plan_stat.alloc_zeroed(8, "plan statistics"))) return rc;
   if ((rc = g->plan_src.alloc(256, "plan sources"))) return rc;
   return g->plan_cost.alloc(g->W * g->H, "distance field");
 }
 
 static int grow_plan_query(dm_grid* g, int64_t n) {
   if (n <= g->plan_qcap) return DM_OK;
-  g->plan_qcap = 0;
-  int rc = g->plan_qxy.alloc(2 * n, "plan query targets");
-  if (!rc) rc = g->plan_qcost.alloc(n, "plan query costs");
-  if (!rc) rc = g->plan_qcell.alloc(n, "plan query cells");
-  if (!rc) g->plan_qcap = n;
-  return rc;
+  return g->plan_qcap.grow(n, [&] {
+    int rc = g->plan_qxy.alloc(2 * n, "plan query targets");
+    if (!rc) rc = g->plan_qcost.alloc(n, "plan query costs");
+    if (!rc) rc = g->plan_qcell.alloc(n, "plan query cells");
+    return rc;
+  });
 }
 
 // SPEC a4's cell of a point: floor((x - origin) / resolution) per axis
@@ -624,15 +621,15 @@ int dm_plan_path(dm_grid* g, double tx, double ty, int32_t snap_cells, int64_t* 
 
 static int grow_gain(dm_grid* g, int64_t n) {
   if (n <= g->gain_cap) return DM_OK;
-  g->gain_cap = 0;
-  int rc = g->gain_xy.alloc(2 * n, "view points");
-  if (!rc) rc = g->gain_cell.alloc(n, "view cells");
-  if (!rc) rc = g->gain_out.alloc(n, "view gains");
-  if (!rc) rc = g->gain_skip.alloc(n, "view skip flags");
-  if (!rc) rc = g->gain_memo_cell.alloc(n, "gain memo cells");
-  if (!rc) rc = g->gain_memo_gain.alloc(n, "gain memo gains");
-  if (!rc) g->gain_cap = n;
-  return rc;
+  return g->gain_cap.grow(n, [&] {
+    int rc = g->gain_xy.alloc(2 * n, "view points");
+    if (!rc) rc = g->gain_cell.alloc(n, "view cells");
+    if (!rc) rc = g->gain_out.alloc(n, "view gains");
+    if (!rc) rc = g->gain_skip.alloc(n, "view skip flags");
+    if (!rc) rc = g->gain_memo_cell.alloc(n, "gain memo cells");
+    if (!rc) rc = g->gain_memo_gain.alloc(n, "gain memo gains");
+    return rc;
+  });
 }
 
 static int gain_check_radius(int32_t radius_cells) {

@@ -160,16 +160,10 @@ inline unsigned long long dm_shard_sum(const unsigned long long* sh, int field) 
   return s;
 }
 
-struct KernelTimer {
-  std::string name;
-  hipEvent_t start, stop;
-  hipStream_t stream = nullptr;
-};
-
 struct dm_shard_set;  // dm_sharded.cpp
 
-// Every allocation, event and stream of a handle is a member that owns it
-// (dm_buf.h) and goes with the handle: dm_destroy has no list of them.  The
+// Every allocation, event, stream and pending timer of a handle is a member
+// that owns it (dm_buf.h) and goes with the handle: dm_destroy has no list of them.  The
 // only raw handles left in it are hipEvent_t's that name an event one of those
 // owners holds (PassEnd::ev, IntWs::free_wait), each said so where it is
 // declared.  Nothing in it means "the slot / workspace set / tile list in
@@ -182,8 +176,9 @@ struct dm_grid {
   dm_shard_set* sh = nullptr;
   int device = 0;
   int n_cu = 256;  // compute units of the device: sizes the resident (one-pass) grids
+  // what every launch uses: owned_stream, or the caller's (dm_set_stream) while owned_stream is null
   hipStream_t stream = nullptr;
-  bool own_stream = false;
+  DevStream owned_stream;
   // dm_set_overlap: the integrate front-end (reset, beam_prep, plan, scatter)
   // runs on fe_stream, so it overlaps a frontier pass still running on
   // `stream`; the accumulation waits for it (ev_fe).  The workspace the
@@ -309,15 +304,15 @@ struct dm_grid {
   // The capacities kept beside the buffers (these, slot_cap, bs_cap, rs_rows,
   // m_cap, plan_qcap, gain_cap) are not one buffer's size, which the buffer
   // knows (size()): each is a bound the kernels are told, or covers a group of
-  // arrays that grow together.  It is set only once every array of its group
-  // is allocated and is 0 after a failed growth.
+  // arrays that grow together.  Only GroupCap::grow sets one: it is 0 until
+  // every array of its group is allocated and after a failed growth.
   // integrate workspace capacities (the arrays are per set, IntWs)
-  int64_t beams_cap = 0;
-  int64_t blk_cap = 0;            // workgroups blk_hist / blk_n hold
-  int64_t segs_cap = 0;           // pieces per workspace
-  int64_t act_cap = 0;
-  int64_t hitem_cap = 0;
-  int64_t heavy_cap = 0;
+  GroupCap beams_cap;
+  GroupCap blk_cap;            // workgroups blk_hist / blk_n hold
+  GroupCap segs_cap;           // pieces per workspace
+  GroupCap act_cap;
+  GroupCap hitem_cap;
+  GroupCap heavy_cap;
   // what the front-end hands to the accumulation, one set per call parity
   struct IntWs {
     // the front-end's own scratch (k_beam_prep -> k_plan / k_scatter): per
@@ -435,8 +430,8 @@ struct dm_grid {
   // each (pass stamp << 2 | arrived sides); never reset (stamped)
   DevBuf<unsigned long long> rel;
   int32_t fparity = 0;         // workspace set (fw) of the last frontier pass
-  int64_t border_cap = 0;      // in tiles
-  int64_t slot_cap = 0;
+  // 0 after a failed growth, which the next pass repeats at the create-time size (dm_enqueue_frontiers)
+  GroupCap slot_cap;
   DevBuf<long long> slot_label;
   DevBuf<int32_t> slot_root;
   DevBuf<long long> slot_own;  // [slot][3] size, sum_x, sum_y
@@ -458,12 +453,12 @@ struct dm_grid {
   DevBuf<unsigned long long> bs_key2;
   DevBuf<int32_t> bs_idx;      // [bs_cap] their record indices, two buffers
   DevBuf<int32_t> bs_idx2;
-  int64_t bs_cap = 0;
+  GroupCap bs_cap;
   // per-row counters (zero between sorts) and offsets
   DevBuf<int32_t> rs_cnt;      // [rs_rows]
   DevBuf<int32_t> rs_off;      // [rs_rows + 1]
   DevBuf<unsigned long long> rs_status;  // [rs_rows / 8192 + 2] k_rs_scan's workgroup totals + failure word
-  int64_t rs_rows = 0;
+  GroupCap rs_rows;
   int64_t sort_hint = 0, msort_hint = 0;  // clusters of the last band / merge readback
   int64_t ftile_hint = 0;                 // listed tiles of the last collected frontier pass
   int64_t runs_hint = 0, ftf_hint = 0;    // its runs and tiles with frontier cells
@@ -486,7 +481,7 @@ struct dm_grid {
   int sparse_pieces = 15;
 
   // cross-band merge workspace (dm_merge.hip), sized nranks * rec_cap
-  int64_t m_cap = 0;
+  GroupCap m_cap;
   DevBuf<int32_t> m_parent;
   DevBuf<long long> m_label;
   DevBuf<long long> m_acc;     // [m_cap][3] size, sum_x, sum_y
@@ -532,7 +527,7 @@ struct dm_grid {
   DevBuf<double> plan_qxy;         // [plan_qcap][2] query targets
   DevBuf<uint32_t> plan_qcost;     // [plan_qcap]
   DevBuf<int64_t> plan_qcell;      // [plan_qcap]
-  int64_t plan_qcap = 0;
+  GroupCap plan_qcap;
   DevBuf<int64_t> plan_path;       // a path, target first
   bool plan_valid = false;
   uint64_t plan_version = 0;
@@ -593,7 +588,7 @@ struct dm_grid {
   DevBuf<uint8_t> gain_skip;       // [gain_cap] views not to cast
   DevBuf<int64_t> gain_memo_cell;  // [gain_cap] per cluster: the cell of its last cast (one call)
   DevBuf<uint32_t> gain_memo_gain; // [gain_cap] and its gain
-  int64_t gain_cap = 0;
+  GroupCap gain_cap;
   // the claimed set of dm_gain_views_joint / dm_assign_goals_coord: H rows of
   // ceil(W / 32) words, allocated by the first of the two calls
   DevBuf<uint32_t> gain_claimed;
@@ -752,6 +747,8 @@ constexpr int32_t kTileListed = 1 << 30;
 constexpr int32_t kTileFreeMask = kTileListed - 1;
 // Frontier slots (tile-local components) per map tile allocated at dm_create.
 constexpr int64_t kSlotsPerTile = 4;
+// The slot group (slot_cap) for at least `need` slots and twice what it held.
+int dm_grow_slots(dm_grid* g, int64_t need);
 int dm_grow_bucket_sort(dm_grid* g, int64_t n);
 // Row-bucket sort of the raw records (labels of rows [row_base, row_base +
 // rows)): same outputs, readback header and flags as dm_launch_rank_sort.

@@ -72,11 +72,11 @@ extern "C" int dm_atomic_peak(int device, double* out, int32_t cap, int32_t* n_o
   DevEvent e0, e1;
   double v[2] = {0.0, 0.0};
   if (int rc = lds_out.alloc(blocks * kProbeThreads, "probe LDS results")) return rc;
-  if (int rc = buf.alloc(rows * 64, "probe rows")) return rc;
-  hipError_t e = hipMemset(buf, 0, sizeof(uint32_t) * (size_t)(rows * 64));
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreate(e0.put());
-  if (e == hipSuccess) e = hipEventCreate(e1.put());
+  if (int rc = buf.alloc_zeroed(rows * 64, "probe rows")) return rc;
+  if (int rc = st.create(hipStreamNonBlocking, 0)) return rc;  // the default priority
+  if (int rc = e0.create(hipEventDefault)) return rc;
+  if (int rc = e1.create(hipEventDefault)) return rc;
+  hipError_t e = hipSuccess;
   for (int pass = 0; pass < 2 && e == hipSuccess; ++pass) {  // pass 0 warms up
     float ms = 0.0f;
     hipLaunchKernelGGL(k_peak_lds, dim3((unsigned)blocks), dim3(kProbeThreads), 0, st, lds_out, 7u + pass);

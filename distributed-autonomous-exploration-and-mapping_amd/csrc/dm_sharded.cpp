@@ -315,16 +315,11 @@ extern "C" int dm_create_sharded(dm_grid** out, const dm_params* p, int32_t nran
     s->row0[(size_t)r] = r0;
     s->rows[(size_t)r] = rows;
     (void)hipSetDevice(devices[r]);
-    for (DevEvent* ev : {&s->ev_rows[(size_t)r], &s->ev_exp[(size_t)r]}) {
-      const hipError_t e = hipEventCreateWithFlags(ev->put(), hipEventDisableTiming);
-      if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
-    }
+    for (DevEvent* ev : {&s->ev_rows[(size_t)r], &s->ev_exp[(size_t)r]})
+      if ((rc = ev->create(hipEventDisableTiming))) return fail(rc);
   }
   (void)hipSetDevice(devices[0]);
-  {
-    const hipError_t e = hipEventCreateWithFlags(s->ev_in.put(), hipEventDisableTiming);
-    if (e != hipSuccess) return fail(dm_hip_check(e, "hipEventCreate"));
-  }
+  if (int rc = s->ev_in.create(hipEventDisableTiming)) return fail(rc);
   // peer access between the bands' devices where the platform offers it
   // (the copies work either way; with access they go device to device)
   for (int a = 0; a < nranks; ++a)

@@ -6,10 +6,12 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <stdint.h>
 #include <string.h>
 
 #include <set>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -21,6 +23,10 @@ int g_allocs = 0;                          // hipMalloc + hipHostMalloc calls so
 int g_fail_at = -1;                        // the call with this number fails ...
 hipError_t g_fail_code = hipErrorOutOfMemory;  // ... with this
 bool g_fail_devptr = false;                // hipHostGetDevicePointer fails
+bool g_fail_memset = false;                // hipMemset fails
+bool g_fail_create = false;                // hipEventCreateWithFlags / hipStreamCreateWithPriority fail
+unsigned g_last_flags = 0;                 // of the last event / stream creation
+int g_last_priority = 0;
 int g_last_device = -1;
 size_t g_last_bytes = 0;
 std::string g_err;
@@ -40,6 +46,7 @@ hipError_t fake_alloc(std::set<void*>& where, void** p, size_t bytes) {
   if (g_allocs++ == g_fail_at) return g_fail_code;
   g_last_bytes = bytes;
   *p = malloc(bytes);
+  memset(*p, 0xA5, bytes);  // nothing here is zero unless somebody zeroed it
   where.insert(*p);
   return hipSuccess;
 }
@@ -51,9 +58,15 @@ hipError_t fake_free(std::set<void*>& where, void* p) {
 }
 
 template <class H>
-void fake_create(H* out) {  // what hipEventCreate* / hipStreamCreate* do to *out
+hipError_t fake_create(H* out, unsigned flags) {  // what hipEventCreate* / hipStreamCreate* do to *out
+  if (g_fail_create) {
+    *out = (H)(uintptr_t)0x10;  // never a live handle: destroying it fails the run
+    return hipErrorInvalidValue;
+  }
+  g_last_flags = flags;
   *out = (H)malloc(1);
   g_handles.insert((void*)*out);
+  return hipSuccess;
 }
 }  // namespace
 
@@ -70,6 +83,17 @@ hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned int) {
   if (g_fail_devptr) return hipErrorInvalidValue;
   *d = (char*)h + (1 << 20);  // never dereferenced
   return hipSuccess;
+}
+hipError_t hipMemset(void* p, int value, size_t bytes) {
+  if (g_fail_memset) return hipErrorInvalidValue;
+  check(g_dev.count(p) == 1 && bytes <= g_last_bytes, "hipMemset inside a live device allocation", __LINE__);
+  memset(p, value, bytes);
+  return hipSuccess;
+}
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned flags) { return fake_create(e, flags); }
+hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned int flags, int priority) {
+  g_last_priority = priority;
+  return fake_create(s, flags);
 }
 hipError_t hipEventDestroy(hipEvent_t e) { return fake_free(g_handles, (void*)e); }
 hipError_t hipStreamDestroy(hipStream_t s) { return fake_free(g_handles, (void*)s); }
@@ -151,6 +175,67 @@ static void test_dev() {
   CHECK(live() == 0);
 }
 
+static void test_zeroed() {
+  {
+    DevBuf<uint32_t> b;
+    CHECK(b.alloc(6, "plain") == DM_OK && b[0] == 0xA5A5A5A5u);  // the fake's fill
+    CHECK(b.alloc_zeroed(6, "zeroed") == DM_OK && b.size() == 6 && live() == 1);
+    for (int i = 0; i < 6; ++i) CHECK(b[i] == 0u);
+    CHECK(b.alloc_zeroed(0, "one", 3) == DM_OK && b.size() == 1 && b[0] == 0u && g_last_device == 3);
+    g_fail_memset = true;  // a failed fill: empty, nothing live, the buffer's name in the message
+    CHECK(b.alloc_zeroed(4, "heavy-tile slabs") == DM_ERR_HIP && !b && b.size() == 0 && live() == 0);
+    CHECK(g_err.rfind("hipMemset(heavy-tile slabs): ", 0) == 0);
+    g_fail_memset = false;
+    g_fail_at = g_allocs;  // a failed allocation: alloc's own error
+    g_fail_code = hipErrorOutOfMemory;
+    CHECK(b.alloc_zeroed(4, "counters") == DM_ERR_OOM && !b && live() == 0);
+    CHECK(g_err == "hipMalloc(counters, 16 bytes): out of memory");
+    g_fail_at = -1;
+    HostBuf<unsigned long long> h;
+    CHECK(h.alloc_zeroed(16, hipHostMallocMapped, "work hint") == DM_OK && h.size() == 16 && h.dev());
+    for (int i = 0; i < 16; ++i) CHECK(h[i] == 0ull);
+    g_fail_at = g_allocs;
+    CHECK(h.alloc_zeroed(16, hipHostMallocDefault, "work hint") == DM_ERR_OOM && !h);
+    g_fail_at = -1;
+  }
+  CHECK(live() == 0);
+}
+
+// A group of four arrays behind one capacity, as the grow_* functions of libdm.
+static void test_group_cap() {
+  {
+    GroupCap cap;
+    DevBuf<int32_t> a, b, c, d;
+    int64_t seen = -1;  // the capacity as the callback reads it
+    auto grow = [&](int64_t n) {
+      return cap.grow(n, [&] {
+        seen = cap;
+        int rc = a.alloc(n, "a");
+        if (!rc) rc = b.alloc(2 * n, "b");
+        if (!rc) rc = c.alloc(n, "c");
+        if (!rc) rc = d.alloc(n, "d");
+        return rc;
+      });
+    };
+    g_fail_code = hipErrorOutOfMemory;
+    CHECK(cap == 0);
+    CHECK(grow(8) == DM_OK && cap == 8 && seen == 0 && live() == 4);
+    for (int k = 0; k < 4; ++k) {
+      g_fail_at = g_allocs + k;  // the k-th allocation of this growth
+      seen = -1;
+      CHECK(grow(16) == DM_ERR_OOM && cap == 0 && seen == 0);
+      CHECK(live() == 3);  // the array that failed is empty, the others hold the old or the new size
+      g_fail_at = -1;
+      CHECK(grow(16 + k) == DM_OK && cap == 16 + k && seen == 0 && live() == 4);
+      CHECK(a.size() == 16 + k && b.size() == 2 * (16 + k) && c.size() == 16 + k && d.size() == 16 + k);
+    }
+    static_assert(!std::is_assignable<GroupCap&, int64_t>::value && !std::is_assignable<GroupCap&, int>::value &&
+                      !std::is_copy_assignable<GroupCap>::value && !std::is_constructible<GroupCap, int64_t>::value,
+                  "only grow sets a capacity");
+  }
+  CHECK(live() == 0);
+}
+
 static void test_host() {
   {
     HostBuf<double> h;
@@ -203,30 +288,73 @@ static void test_handles() {
     DevEvent e, arr[2];
     DevStream s;
     CHECK((hipEvent_t)e == nullptr && (hipStream_t)s == nullptr);
-    fake_create(e.put());
-    fake_create(s.put());
-    for (auto& a : arr) fake_create(a.put());
-    CHECK((hipEvent_t)e != nullptr && live() == 4);
-    fake_create(e.put());  // put() destroys the one held
-    CHECK(live() == 4);
+    CHECK(e.create(hipEventDisableTiming) == DM_OK && g_last_flags == hipEventDisableTiming);
+    CHECK(s.create(hipStreamNonBlocking, -1) == DM_OK && g_last_flags == hipStreamNonBlocking && g_last_priority == -1);
+    for (auto& a : arr) CHECK(a.create(hipEventDefault) == DM_OK);
+    CHECK((hipEvent_t)e != nullptr && (hipStream_t)s != nullptr && live() == 4);
+    hipEvent_t first = e;
+    CHECK(e.create(hipEventDefault) == DM_OK && live() == 4);  // destroys the one held
+    CHECK(g_handles.count((void*)first) == 0 && g_handles.count((void*)(hipEvent_t)e) == 1);
+    hipStream_t first_s = s;
+    CHECK(s.create(hipStreamNonBlocking, 0) == DM_OK && live() == 4 && g_handles.count((void*)first_s) == 0);
     hipEvent_t raw = e;
     DevEvent m(std::move(e));
     CHECK((hipEvent_t)m == raw && (hipEvent_t)e == nullptr);
     arr[0] = std::move(m);
     CHECK((hipEvent_t)arr[0] == raw && live() == 3);
     std::vector<DevEvent> v(4);
-    for (auto& a : v) fake_create(a.put());
+    for (auto& a : v) CHECK(a.create(hipEventDefault) == DM_OK);
     v.resize(9);
     CHECK(live() == 7);
+    // a failed creation: a null handle (the one held is gone), the code, the call in the message
+    g_fail_create = true;
+    CHECK(v[0].create(hipEventDefault) == DM_ERR_HIP && (hipEvent_t)v[0] == nullptr && live() == 6);
+    CHECK(g_err.rfind("hipEventCreateWithFlags: ", 0) == 0);
+    CHECK(s.create(hipStreamNonBlocking, 0) == DM_ERR_HIP && (hipStream_t)s == nullptr && live() == 5);
+    CHECK(g_err.rfind("hipStreamCreateWithPriority: ", 0) == 0);
+    DevEvent never;
+    CHECK(never.create(hipEventDefault) == DM_ERR_HIP && (hipEvent_t)never == nullptr);
+    g_fail_create = false;
+  }
+  CHECK(live() == 0);
+}
+
+// Pending timers as dm_timer_end keeps them: moved into a vector that owns their events.
+static void test_timers() {
+  {
+    std::vector<KernelTimer> pending;
+    for (int i = 0; i < 10; ++i) {
+      KernelTimer t;
+      t.name = "kernel " + std::to_string(i);
+      CHECK(t.start.create(hipEventDefault) == DM_OK && t.stop.create(hipEventDefault) == DM_OK);
+      hipEvent_t start = t.start;
+      pending.push_back(std::move(t));
+      CHECK((hipEvent_t)t.start == nullptr && (hipEvent_t)t.stop == nullptr && (hipEvent_t)pending.back().start == start);
+    }
+    CHECK(live() == 20 && pending[7].name == "kernel 7");
+    pending.resize(3);
+    CHECK(live() == 6);
+    pending.clear();
+    CHECK(live() == 0);
+    pending.resize(4);  // empty timers hold nothing
+    CHECK(live() == 0 && (hipEvent_t)pending[3].start == nullptr);
+    CHECK(pending[1].start.create(hipEventDefault) == DM_OK && live() == 1);
+    pending.clear();
+    CHECK(live() == 0);
+    KernelTimer begun;  // begun, never ended: goes with its scope
+    CHECK(begun.start.create(hipEventDefault) == DM_OK && begun.stop.create(hipEventDefault) == DM_OK);
   }
   CHECK(live() == 0);
 }
 
 int main() {
   test_dev();
+  test_zeroed();
+  test_group_cap();
   test_host();
   test_headed();
   test_handles();
+  test_timers();
   CHECK(live() == 0);
   printf("buf_main: ok, %d checks, %d allocations\n", g_checks, g_allocs);
   return 0;
