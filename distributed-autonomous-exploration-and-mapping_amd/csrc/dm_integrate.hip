@@ -545,6 +545,56 @@ __device__ inline int32_t zero_bytes(uint32_t x) {
   return __popc(t);
 }
 
+// What one thread's applied cells add to its tile's totals: touched cells
+// and the net change in free cells, packed as touched + (change << 16) in one
+// register (two accumulators held through the apply cost k_tile_accum its
+// eighth workgroup per CU), and (edge tiles, heavy tiles) their updates.
+struct ApplyTotals {
+  int32_t tf = 0;
+  uint32_t dU = 0;
+  __device__ void cells(int32_t touched, int32_t dfree) { tf += touched + (int32_t)((uint32_t)dfree << 16); }
+};
+
+// The same for a wave, in scalar registers.
+struct WaveTotals {
+  int32_t T, dfree;
+  uint32_t U;
+};
+
+// A wave applies the cells of at most one tile between two reductions, a
+// thread at most kFreeBias of them (the sparse four-pass apply: 4 passes x 4
+// rows x 4 cells; a dense thread 16), so its free-cell change lies in
+// [-kFreeBias, kFreeBias] and its touched cells in [0, kFreeBias].
+constexpr int32_t kFreeBias = DM_TS * DM_TS / 64;
+static_assert(kFreeBias * 64 < (1 << 16), "a wave's touched cells fit the low half");
+static_assert(2 * kFreeBias * 64 < (1 << 15), "a wave's biased free-cell changes fit the high half");
+
+// The threads' totals summed over the wave: touched cells and the free-cell
+// change, biased per thread, in one wave_sum (both fields non-negative, so no
+// borrow crosses them), dU in one of its own only where it is counted
+// (with_u is wave-uniform).  Every lane active, in wave-uniform control flow
+// (DPP reads every lane).  A same-address LDS atomicAdd per thread instead is
+// expanded by the compiler into one scalar loop iteration per active lane
+// (about 60 x 7 dependent instructions for the touched cells after a light
+// tile's apply).
+__device__ inline WaveTotals wave_totals(const ApplyTotals& t, bool with_u) {
+  const int32_t s = wave_sum(t.tf + (kFreeBias << 16));
+  WaveTotals w;
+  w.T = s & 0xFFFF;
+  w.dfree = (s >> 16) - 64 * kFreeBias;
+  w.U = with_u ? (uint32_t)wave_sum((int32_t)t.dU) : 0u;
+  return w;
+}
+
+// One lane adds the wave's totals to the workgroup's LDS counters.
+__device__ inline void add_wave_totals(const WaveTotals& w, int lane, int32_t* s_T, int32_t* s_free,
+                                       uint32_t* s_U) {
+  if (lane != 0) return;
+  if (w.T) atomicAdd(s_T, w.T);
+  if (w.dfree) atomicAdd(s_free, w.dfree);
+  if (w.U) atomicAdd(s_U, w.U);
+}
+
 // Cells of one tile owned by one thread: 4 consecutive cells (float4 / char4)
 // of ROWS rows ly0, ly0 + dly, ...  Their L / state are loaded BEFORE the
 // pieces are accumulated (they do not depend on the counts), so the apply
@@ -595,17 +645,18 @@ struct CellRows {
   }
 
   // counts(ly, h4, m4) supplies the counts of this thread's 4 cells of row ly.
-  // Adds the touched cells to *sh_T and the change in free cells to
-  // *sh_free; the updates U of the applied cells to *sh_U only if sh_U is
-  // given (a tile inside the map counts them in the walk instead: every cell
-  // step is one update; an edge tile's pieces also step over cells past the
-  // map's edge, which are not updates).
+  // Adds the touched cells and the change in free cells to this thread's
+  // totals `tot`; the updates U of the applied cells only if count_u (a tile
+  // inside the map counts them in the walk instead: every cell step is one
+  // update; an edge tile's pieces also step over cells past the map's edge,
+  // which are not updates).  May run under a divergent branch: the caller
+  // reduces `tot` over the wave afterwards (wave_totals).
   template <class Counts>
   __device__ void apply(const Geom& g, const ApplyArgs& p, int32_t tx0, int32_t ty0, int ly0, int dly,
                         int cx, float* __restrict__ L, int8_t* __restrict__ state, Counts&& counts,
-                        int32_t* sh_T, int32_t* sh_free, uint32_t* sh_U) {
-    int32_t dT = 0, dFree = 0;
-    uint32_t dU = 0;
+                        bool count_u, ApplyTotals& tot) {
+    static_assert(ROWS * 4 <= kFreeBias, "a thread's cells per apply fit the packed reduction's bias");
+    ApplyTotals t;
 #pragma unroll
     for (int rr = 0; rr < ROWS; ++rr) {
       const int ly = ly0 + rr * dly;
@@ -615,9 +666,9 @@ struct CellRows {
       counts(ly, h4, m4);
       if (((h4[0] | m4[0]) | (h4[1] | m4[1]) | (h4[2] | m4[2]) | (h4[3] | m4[3])) == 0u) continue;
       const int64_t base = (int64_t)y * g.r.W + tx0 + cx;
-      if (sh_U) {
+      if (count_u) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) dU += tx0 + cx + e < g.r.W ? h4[e] + m4[e] : 0u;
+        for (int e = 0; e < 4; ++e) t.dU += tx0 + cx + e < g.r.W ? h4[e] + m4[e] : 0u;
       }
       if (vec) {
         // branch- and compare-free per cell: untouched cells keep their values
@@ -631,10 +682,10 @@ struct CellRows {
           nlb[e] = bfi(mh, __float_as_uint(nl), __float_as_uint(lv[e]));
           nsw |= (state_bits(p, nl) & 0xFFu) << (8 * e);
           msk |= (mh & 0xFFu) << (8 * e);
-          dT += (int32_t)(mh & 1u);
+          t.tf += (int32_t)(mh & 1u);
         }
         const uint32_t ns = bfi(msk, nsw, sw);
-        dFree += zero_bytes(ns) - zero_bytes(sw);
+        t.cells(0, zero_bytes(ns) - zero_bytes(sw));
         *reinterpret_cast<float4*>(L + base) =
             make_float4(__uint_as_float(nlb[0]), __uint_as_float(nlb[1]), __uint_as_float(nlb[2]),
                         __uint_as_float(nlb[3]));
@@ -648,14 +699,12 @@ struct CellRows {
           const int8_t ns = state_of(p, nl);
           L[i] = nl;
           state[i] = ns;
-          dT += 1;
-          dFree += (ns == 0) - (old == 0);
+          t.cells(1, (ns == 0) - (old == 0));
         }
       }
     }
-    if (dT) atomicAdd(sh_T, dT);
-    if (dFree) atomicAdd(sh_free, dFree);
-    if (dU) atomicAdd(sh_U, dU);
+    tot.tf += t.tf;
+    tot.dU += t.dU;
   }
 };
 
@@ -761,6 +810,24 @@ __device__ inline int32_t walk_piece_bytes(uint32_t* tq, const PackedPiece& mine
   return sp.n;
 }
 
+// The count tile in LDS with its spare words, zeroed by the workgroup's 256
+// threads in 16-byte stores: a fixed trip count (4 stores per thread and a
+// 32-thread tail), where the word loop was 17 trips of 7 instructions.
+constexpr int kTileLds = kTileWords + 64;
+__device__ inline void clear_tile(uint32_t* tl, int tid) {
+  static_assert(kTileLds % 4 == 0, "whole 16-byte stores");
+  constexpr int kVec = kTileLds / 4;
+  uint4* v = reinterpret_cast<uint4*>(tl);
+  // (the zero made opaque: hoisted out of k_tile_accum's item loop as a
+  // constant, its four registers stay live across the whole loop)
+  uint32_t z = 0u;
+  asm volatile("" : "+v"(z));
+  const uint4 z4 = make_uint4(z, z, z, z);
+#pragma unroll
+  for (int k = 0; k < kVec / kQuarter; ++k) v[k * kQuarter + tid] = z4;
+  if (tid < kVec % kQuarter) v[kVec / kQuarter * kQuarter + tid] = z4;
+}
+
 __device__ inline PackedPiece no_piece() {
   PackedPiece q;
   q.x = 0u; q.y = 0u; q.z = 0u; q.w = 1u;
@@ -804,11 +871,11 @@ __device__ inline void finish_tile(const Geom& g, int32_t tile, int32_t T, int32
 // shape for the memory-side atomics.  The read-and-clear is an exchange:
 // the slab was only ever written by the items' device-scope atomics, which
 // execute at the memory side, so the exchange reads the merged counts there
-// and leaves no stale L2 line.  Totals go to the workgroup's LDS counters.
+// and leaves no stale L2 line.  Totals go to the thread's `tot` (4 cells per
+// quarter, 16 per tile: the finisher reduces them once, after the fourth).
 __device__ inline void heavy_quarter(const Geom& g, const ApplyArgs& p, int64_t h, int q, int32_t tile,
                                      bool wide, uint32_t* __restrict__ slabs, float* __restrict__ L,
-                                     int8_t* __restrict__ state, int32_t* s_T, int32_t* s_free,
-                                     uint32_t* s_U) {
+                                     int8_t* __restrict__ state, ApplyTotals& tot) {
   constexpr int kQ = DM_TS * DM_TS / 4;  // cells per quarter
   const int tid = threadIdx.x;
   const int32_t x = (tile % g.r.TX) * DM_TS + (tid & 63);
@@ -833,8 +900,6 @@ __device__ inline void heavy_quarter(const Geom& g, const ApplyArgs& p, int64_t 
     hc[k] = atomicExch(sh + k * kQuarter, 0u);
     mc[k] = wide ? atomicExch(sh + DM_TS * DM_TS + k * kQuarter, 0u) : 0u;
   }
-  int32_t dT = 0, dFree = 0;
-  uint32_t dU = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     uint32_t hk = hc[k], mk;
@@ -851,13 +916,9 @@ __device__ inline void heavy_quarter(const Geom& g, const ApplyArgs& p, int64_t 
     const int8_t ns = state_of(p, nl);
     L[i] = nl;
     state[i] = ns;
-    dU += hk + mk;
-    dT += 1;
-    dFree += (ns == 0) - (sv[k] == 0);
+    tot.dU += hk + mk;
+    tot.cells(1, (ns == 0) - (sv[k] == 0));
   }
-  if (dT) atomicAdd(s_T, dT);
-  if (dFree) atomicAdd(s_free, dFree);
-  if (dU) atomicAdd(s_U, dU);
 }
 
 // Per-cell hit/miss counts never touch HBM: a 256-thread workgroup takes one
@@ -878,16 +939,18 @@ __device__ inline void heavy_quarter(const Geom& g, const ApplyArgs& p, int64_t 
 // next item's loads in the wave's in-order vmcnt queue.
 //
 // Registers (the compiler's resource summary with the Makefile's flags,
-// pinned by tests/test_kernel_resources.py): 64 VGPRs, no scratch, no
-// spilled VGPR, 21 SGPRs spilled into lanes of one VGPR, 19 024 B of LDS.
+// pinned by tests/test_kernel_resources.py): 63 VGPRs, no scratch, no
+// spilled VGPR, 24 SGPRs spilled into lanes of one VGPR, 18 976 B of LDS.
 // The launch bounds ask for 7 workgroups per CU (a budget of 72 VGPRs); at
-// 64 VGPRs and 19 KB of LDS a CU holds 8, and that eighth workgroup is what
+// <= 64 VGPRs and 19 KB of LDS a CU holds 8, and that eighth workgroup is what
 // the step gains (bounds of 8 measure the same, 7 resident
-// workgroups forced by LDS measure slower).  What keeps it at 64: wave_max /
-// wave_sum instead of shuffle butterflies, and the thread index made opaque
-// once per item, so that nothing derived from it lives across the item loop.
-// Until both were in, this kernel ran with 72 VGPRs, 13 more spilled and 44 B
-// of scratch per lane, 7 per CU.
+// workgroups forced by LDS measure slower).  What keeps it there: wave_max /
+// wave_sum instead of shuffle butterflies, the thread index made opaque
+// once per item, so that nothing derived from it lives across the item loop,
+// the apply's touched / free totals in one register (ApplyTotals; two were
+// 65 VGPRs) and clear_tile's zero made opaque (hoisted, 69).
+// Until the first two were in, this kernel ran with 72 VGPRs, 13 more spilled
+// and 44 B of scratch per lane, 7 per CU.
 #ifndef DM_ACCUM_OCC
 #define DM_ACCUM_OCC 7
 #endif
@@ -899,7 +962,7 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
     const unsigned long long* __restrict__ cnt, unsigned long long* ish, int vec_ok,
     const int32_t* __restrict__ heavy_list, int32_t* heavy_done, int32_t* tlist, unsigned long long* tlist_n,
     unsigned long long* hint, const unsigned long long* __restrict__ halt, uint8_t* __restrict__ tile_seen) {
-  __shared__ uint32_t tl[kTileWords + 64];  // + one spare word per lane (walk_tp_split)
+  __shared__ __attribute__((aligned(16))) uint32_t tl[kTileLds];  // + one spare word per lane (walk_tp_split)
   __shared__ int32_t s_T, s_free, s_last;
   __shared__ uint32_t s_U;
   int tid = threadIdx.x;  // (one-dimensional workgroups of whole waves: the lane is tid % 64)
@@ -924,14 +987,19 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
   // they run beside the dense items instead of behind the first (longest)
   // ones: a small call (one 360-beam scan) is one round of items, and its
   // sparse tiles used to queue behind its heavy and medium tiles.
-  const int64_t sp_rank = ((int64_t)blockIdx.x - n_items % G + G) % G;
+  // (in 32 bits: the host keeps the grid within kAccumGrid and the two list
+  // capacities' sum within INT32_MAX, dm_launch_integrate; the 64-bit form
+  // was some 300 scalar instructions in front of every workgroup's first loads)
+  const uint32_t sp_off = (uint32_t)n_items % gridDim.x;
+  const int32_t sp_rank = (int32_t)(blockIdx.x >= sp_off ? blockIdx.x - sp_off : blockIdx.x + gridDim.x - sp_off);
+  // this workgroup takes sparse items (its wave 0 at least)
+  const bool has_sparse = (int64_t)sp_rank * (kQuarter / 64) < SI;
   if (blockIdx.x == 0 && tid == 0) {  // the work of this call, for the next call's grid (mapped host memory)
     volatile unsigned long long* h = hint;
     h[0] = (unsigned long long)(n_items + (SI + 3) / 4);
     h[1] = (unsigned long long)(n_items + SI);
   }
-  const unsigned long long idle =
-      ((int64_t)blockIdx.x >= n_items && sp_rank * (kQuarter / 64) >= SI) ? 1ull : 0ull;
+  const unsigned long long idle = ((int64_t)blockIdx.x >= n_items && !has_sparse) ? 1ull : 0ull;
   // a timed-out front-end hand-off (kHaltWord): this call's workspace was
   // never written, so nothing is applied (the host reports DM_ERR_PIPELINE).
   // One exit test on all four loads, so they go out together.
@@ -975,7 +1043,7 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
   // counter, so pieces issued after the stores would make the next walk's
   // wait for them also a wait for the previous item's stores to drain.
   PackedPiece mine_n = mine;
-  for (int e = tid; e < kTileWords; e += kQuarter) tl[e] = 0u;
+  clear_tile(tl, tid);
   if (tid == 0) { s_T = 0; s_free = 0; s_U = 0u; s_accT = 0ull; s_accU = 0ull; }
   __syncthreads();
   DM_PH_INIT();
@@ -1053,8 +1121,9 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
         const int64_t h = heavy >> 1;
         const bool wide = heavy_list[h] < 0;
         const int32_t old_free = tid == 0 ? tile_free[tile] : 0;  // in flight during the apply
-        for (int q = 0; q < 4; ++q)
-          heavy_quarter(g, p, h, q, tile, wide, slabs, L, state, &s_T, &s_free, &s_U);
+        ApplyTotals tot;
+        for (int q = 0; q < 4; ++q) heavy_quarter(g, p, h, q, tile, wide, slabs, L, state, tot);
+        add_wave_totals(wave_totals(tot, true), lane, &s_T, &s_free, &s_U);
         __syncthreads();
         if (tid == 0) {
           finish_tile(g, tile, s_T, s_free, s_U, true, tile_count, tile_free, old_free, tlist, tlist_n, ish);
@@ -1094,6 +1163,7 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
       DM_PH(dm_phase_acc_integrate, 3);
       DM_PH_COUNT(dm_phase_acc_integrate, 16, 1);
       DM_PH_COUNT(dm_phase_acc_integrate, 18, c);
+      ApplyTotals tot;
       cells.apply(g, p, tx0, ty0, tid >> 4, 16, cx, L, state,
                   [&](int ly, uint32_t* h4, uint32_t* m4) {
                     for (int e = 0; e < 4; ++e) {
@@ -1102,7 +1172,8 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
                       m4[e] = v & 0xFFFFu;
                     }
                   },
-                  &s_T, &s_free, inside ? nullptr : &s_U);
+                  !inside, tot);
+      add_wave_totals(wave_totals(tot, !inside), lane, &s_T, &s_free, &s_U);
       DM_PH(dm_phase_acc_integrate, 4);
     }
     __syncthreads();
@@ -1117,14 +1188,21 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
     info = next;
     next = item_of(it + 2 * G);
     mine = mine_n;
-    for (int e = tid; e < kTileWords; e += kQuarter) tl[e] = 0u;
-    if (tid == 0) { s_T = 0; s_free = 0; s_U = 0u; }
-    __syncthreads();
+    // The clear, the counters' reset and their barrier are for what this
+    // workgroup runs next: a further dense item, or the sparse loop (which
+    // needs the tile zero).  At C3 a workgroup runs about one item and no
+    // sparse one, and used to hold its slot for a clear nobody read.
+    if (it + G < n_items || has_sparse) {
+      clear_tile(tl, tid);
+      if (tid == 0) { s_T = 0; s_free = 0; s_U = 0u; }
+      __syncthreads();
+    }
   }
   // Sparse items (a few pieces: C5's sparse scans on a 1 cm map): walk first,
   // then load and apply only the touched 4-cell groups.  A loop of its own
   // (after the dense items), so none of its registers are live across the
-  // dense walk.  The LDS tile is zero here: every dense item clears it.
+  // dense walk.  The LDS tile is zero here: the prologue cleared it, and a
+  // workgroup that takes sparse items clears it after every dense item.
   // One sparse item per WAVE (round 3; round 2 had one per 128-thread half,
   // whose second wave idled through the walk): with at most kSparseMax
   // pieces a cell is visited at most 15 times, so its counts fit one byte
@@ -1133,8 +1211,6 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
   // applies and clears its own tile with no workgroup barrier (LDS operations
   // of one wave complete in order; the wavefront fences keep the compiler
   // from moving them), so a CU keeps 4 x 8 = 32 sparse tiles in flight.
-  __shared__ int32_t s_wT[kQuarter / 64], s_wfree[kQuarter / 64];
-  __shared__ uint32_t s_wU[kQuarter / 64];
   __shared__ uint16_t s_list[kQuarter / 64][kSparseList];  // touched 4-cell groups of each wave's tile
   // (the thread index anew, as above: nothing of this loop is computed before
   // the dense items, and each item recomputes its lane's LDS addresses.  The
@@ -1142,7 +1218,6 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
   // from it -- tile origin, split factor -- then sit in scalar registers.)
   asm volatile("" : "+v"(tid));
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if ((tid & 63) == 0) { s_wT[wv] = 0; s_wfree[wv] = 0; s_wU[wv] = 0u; }
   const int nw = kQuarter / 64;
   for (int64_t it = sp_rank * nw + wv; it < SI; it += (int64_t)G * nw) {
     asm volatile("" : "+v"(tid));
@@ -1198,6 +1273,10 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    // the lanes' totals, reduced once per item after both shapes of apply
+    // (which run under per-lane conditions)
+    ApplyTotals tot;
+    static_assert((kSparseList + 127) / 128 * 2 * 4 <= kFreeBias, "a lane's listed cells fit wave_totals' bias");
     if (nt <= kSparseList) {
       for (int e0 = 0; e0 < nt; e0 += 128) {
         const int ea = e0 + lane, eb = e0 + 64 + lane;
@@ -1207,12 +1286,10 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
         cb.load_touched(g, tx0, ty0, wb >> 4, 0, (wb & 15) * 4, L, state, vec_ok, [&](int) { return eb < nt; });
         if (ea < nt)
           ca.apply(g, p, tx0, ty0, wa >> 4, 0, (wa & 15) * 4, L, state,
-                   [&](int, uint32_t* h4, uint32_t* m4) { counts(wa, h4, m4); }, &s_wT[wv], &s_wfree[wv],
-                   inside ? nullptr : &s_wU[wv]);
+                   [&](int, uint32_t* h4, uint32_t* m4) { counts(wa, h4, m4); }, !inside, tot);
         if (eb < nt)
           cb.apply(g, p, tx0, ty0, wb >> 4, 0, (wb & 15) * 4, L, state,
-                   [&](int, uint32_t* h4, uint32_t* m4) { counts(wb, h4, m4); }, &s_wT[wv], &s_wfree[wv],
-                   inside ? nullptr : &s_wU[wv]);
+                   [&](int, uint32_t* h4, uint32_t* m4) { counts(wb, h4, m4); }, !inside, tot);
       }
     } else {
       // the wave covers the tile in four passes of 16 rows (a lane: one
@@ -1224,27 +1301,25 @@ __global__ __launch_bounds__(kQuarter, kAccumPerCu) void k_tile_accum(
                         [&](int ly) { return tq[ly * 16 + (hcx >> 2)] != 0u; });
         sc.apply(g, p, tx0, ty0, ly0, 4, hcx, L, state,
                  [&](int ly, uint32_t* h4, uint32_t* m4) { counts(ly * 16 + (hcx >> 2), h4, m4); },
-                 &s_wT[wv], &s_wfree[wv], inside ? nullptr : &s_wU[wv]);
+                 !inside, tot);
       }
     }
+    const WaveTotals wt = wave_totals(tot, !inside);
     DM_PH(dm_phase_acc_integrate, 7);
     DM_PH_COUNT(dm_phase_acc_integrate, 21, 1);
     DM_PH_COUNT(dm_phase_acc_integrate, 22, c);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {
-      const int32_t T = s_wT[wv], df = s_wfree[wv];
-      const uint32_t U = s_wU[wv] + wU;
-      atomicAdd(&s_accT, (unsigned long long)T);
-      atomicAdd(&s_accU, (unsigned long long)U);
-      if (df) tile_free[tile] = free_update(sfree, df, tile, tlist, tlist_n);
+      atomicAdd(&s_accT, (unsigned long long)wt.T);
+      atomicAdd(&s_accU, (unsigned long long)(wt.U + wU));
+      if (wt.dfree) tile_free[tile] = free_update(sfree, wt.dfree, tile, tlist, tlist_n);
       tile_count[tile] = 0;  // ready for the next call
       tile_seen[tile] = 1;
-      s_wT[wv] = 0;
-      s_wfree[wv] = 0;
-      s_wU[wv] = 0u;
     }
-    for (int e = lane; e < DM_TS * DM_TS / 4; e += 64) tq[e] = 0u;
+#pragma unroll
+    for (int k = 0; k < DM_TS * DM_TS / 16 / 64; ++k)  // the wave's 4 KiB in 16-byte stores
+      reinterpret_cast<uint4*>(tq)[k * 64 + lane] = make_uint4(0u, 0u, 0u, 0u);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }
@@ -1574,6 +1649,12 @@ DM_TL_READER(accum)
 int dm_launch_integrate(dm_grid* g, int32_t S, const double* d_pose4, int32_t N,
                         const float* d_ranges, const double* d_trig) {
   const int64_t nb = (int64_t)S * N;
+  // k_tile_accum ranks its sparse items in 32 bits: the items of a call are
+  // at most the two lists' capacities, its grid at most kAccumGrid
+  static_assert(dm_grid::kAccumGrid <= 16384, "k_tile_accum's 32-bit sparse rank");
+  if (g->hitem_cap + g->act_cap > INT32_MAX)
+    return dm_set_error(DM_ERR_CAPACITY, "integrate: room for %lld work items exceeds 2^31 - 1",
+                        (long long)(g->hitem_cap + g->act_cap));
   // calls alternate between the two workspace sets
   g->iw_cur = (g->iw_cur + 1) % dm_grid::kIntSets;
   dm_grid::IntWs& w = g->iw[g->iw_cur];
