@@ -96,8 +96,10 @@ static int dm_mg_launch_pool(dm_grid* g, int32_t n_tiles, int32_t lb, int32_t EW
 
 // One scan: candidate poses d_pose4 [A][4], ranges d_ranges [N], g->match_trig.
 // Synchronous.  res = k, i, j, score, used beams; stats [4] as dm_match_global's.
-static int dm_mg_run_scan(dm_grid* g, const MgShape& sh, const double* d_pose4, const float* d_ranges, int32_t* res,
-                   uint64_t* stats) {
+// off_map: the window reaches no cell of the map, so only the used beams are
+// counted and nothing is bounded or scored.
+static int dm_mg_run_scan(dm_grid* g, const MgShape& sh, bool off_map, const double* d_pose4, const float* d_ranges,
+                          int32_t* res, uint64_t* stats) {
   using namespace dm_mg;
   hipStream_t s = g->stream;
   Cand* best = (Cand*)g->mg_best.get();
@@ -123,7 +125,13 @@ static int dm_mg_run_scan(dm_grid* g, const MgShape& sh, const double* d_pose4, 
     dm_timer_end(g, &t);
   }
   uint64_t refined = 0, rounds = 0;
-  if (sh.exhaustive) {
+  if (off_map) {
+    // every candidate reads cells out of the grid only: the initial best stands
+    hipLaunchKernelGGL(k_mg_fold, dim3(1), dim3(kThreads), 0, s, cand, (const uint32_t*)nullptr, 0, sh.k0, best,
+                       g->mg_nused, g->h_mg.dev());
+    DM_HIP(hipGetLastError());
+    DM_HIP(hipStreamSynchronize(s));
+  } else if (sh.exhaustive) {
     for (int64_t base = 0; base < blocks; base += dm_grid::kMgExhaustiveBatch) {
       const int32_t n = (int32_t)std::min<int64_t>(dm_grid::kMgExhaustiveBatch, blocks - base);
       dm_timer_begin(g, "mg_refine", &t);
@@ -190,7 +198,7 @@ static int dm_mg_run_scan(dm_grid* g, const MgShape& sh, const double* d_pose4, 
   res[3] = (int32_t)g->h_mg[0];
   res[4] = (int32_t)g->h_mg[5];
   stats[0] = (uint64_t)blocks;
-  stats[1] = sh.exhaustive ? 0 : (uint64_t)blocks;
+  stats[1] = sh.exhaustive || off_map ? 0 : (uint64_t)blocks;
   stats[2] = refined;
   stats[3] = rounds;
   return DM_OK;
@@ -246,6 +254,30 @@ static int match_build_tiles(dm_grid* g, const std::vector<uint8_t>& want) {
   int rc = dm_match_launch_field(g, (int32_t)list.size(), g->match_r, mono);
   if (rc) return rc;
   for (int32_t t : list) g->match_built[(size_t)t] = 1;
+  return DM_OK;
+}
+
+// Diagnostic: the tiles match_V holds for the current table and map version,
+// and how many 64 x 64 tiles of the pooled field stand on them.
+int dm_match_built(dm_grid* g, uint8_t* field_tiles, int64_t cap, int64_t* n_field, int64_t* n_pool) {
+  int rc = dm_check_whole_map(g, "dm_match_built");
+  if (rc) return rc;
+  if (!n_field || !n_pool) return dm_set_error(DM_ERR_INVALID_ARG, "n_field / n_pool is NULL");
+  if (field_tiles && cap < g->NT)
+    return dm_set_error(DM_ERR_CAPACITY, "field_tiles holds %lld flags, the map has %lld tiles", (long long)cap,
+                        (long long)g->NT);
+  const bool valid = g->match_V && g->match_r >= 0 && g->match_version == dm_map_version(g) &&
+                     g->match_built.size() == (size_t)g->NT;
+  int64_t nf = 0, np = 0;
+  for (int64_t t = 0; t < g->NT; ++t) {
+    const uint8_t b = valid && g->match_built[(size_t)t] ? 1 : 0;
+    if (field_tiles) field_tiles[t] = b;
+    nf += b;
+  }
+  if (valid && g->mg_pool && g->mg_pool_epoch == g->match_epoch)
+    for (uint8_t b : g->mg_pool_built) np += b ? 1 : 0;
+  *n_field = nf;
+  *n_pool = np;
   return DM_OK;
 }
 
@@ -517,7 +549,9 @@ int dm_match_global(dm_grid* g, int32_t S, const double* poses, int32_t N, const
         if ((rc = dm_mg_launch_pool(g, (int32_t)plist.size(), sh.lb, sh.EWB, sh.EHB, (int32_t)PTX))) return rc;
         for (int32_t t : plist) g->mg_pool_built[(size_t)t] = 1;
       }
-      if ((rc = dm_mg_run_scan(g, sh, g->match_pose4 + 4 * (size_t)s * A, g->match_ranges + (size_t)s * N, r5, stats)))
+      const bool off_map = !(fx1 >= 0.0 && fy1 >= 0.0 && fx0 < (double)g->W && fy0 < (double)g->H);
+      if ((rc = dm_mg_run_scan(g, sh, off_map, g->match_pose4 + 4 * (size_t)s * A, g->match_ranges + (size_t)s * N,
+                               r5, stats)))
         return rc;
     }
     const int32_t k = r5[0], i = r5[1], j = r5[2];

@@ -210,6 +210,7 @@ SIGNATURES = {
                        _vp, _vp, _vp, _vp, _vp],
     "dm_match_global": [_vp, _i32, _vp, _i32, _vp, _f32, _f32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
                         _vp, _vp, _vp, _vp, _vp],
+    "dm_match_built": [_vp, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     "dm_fuse_logodds": [_vp, ctypes.POINTER(DmFuseSource), _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                         _i32, _vp],
     "dm_fuse_state": [_vp, ctypes.POINTER(DmFuseSource), _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,

@@ -561,6 +561,19 @@ class OccupancyMapper:
                                             _vp(best), _vp(score), _vp(n_used), _vp(pose), _vp(stats)))
         return {"best": best, "score": score, "n_used": n_used, "pose": pose, "stats": stats}
 
+    def match_built(self) -> tuple[np.ndarray, int]:
+        """What the matcher's kept fields hold for the map as it is now
+        (dm_match_built, a diagnostic): (flags bool [tile rows, tile columns]
+        of the response field's built 64 x 64 tiles, the pooled field's built
+        tiles).  All zero before the first match and after any map write."""
+        TY, TX = -(-self.rows // 64), -(-self.width // 64)
+        flags = np.zeros((TY, TX), np.uint8)
+        n_field, n_pool = ctypes.c_int64(0), ctypes.c_int64(0)
+        with self._lock:
+            check(self._lib.dm_match_built(self._handle(), _vp(flags), flags.size, ctypes.byref(n_field),
+                                           ctypes.byref(n_pool)))
+        return flags.astype(bool), int(n_pool.value)
+
     def relocalize(self, scan, prior=None, slam=None) -> dict:
         """Find the pose of one LaserScan-like message in the map without a good
         prior: the global stage (dm_match_global with dm.match.global_params'

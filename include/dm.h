@@ -709,7 +709,8 @@ int dm_match_scans(dm_grid* g, int32_t S, const double* poses, int32_t N, const 
  * out_best: int32[S][3] = (k, i, j); out_score: uint32[S]; out_n_used:
  * int32[S]; out_pose: double[S][3]; out_stats (may be NULL): uint64[S][4] =
  * blocks in the search, blocks whose bound was computed (0 when exhaustive),
- * blocks scored exactly, rounds.  Synchronous, ordered after everything
+ * blocks scored exactly, rounds (a scan whose window reaches no cell of the
+ * map bounds and scores nothing: blocks, 0, 0, 0).  Synchronous, ordered after everything
  * enqueued on the handle; reads the map and never writes it, the map version
  * is unchanged.  The scans of one call are processed one after another.  The
  * pooled field is kept in the handle per (map version, smear_cells, kern,
@@ -720,6 +721,17 @@ int dm_match_global(dm_grid* g, int32_t S, const double* poses, int32_t N, const
                     int32_t half_y, int32_t block, int32_t exhaustive, int32_t smear_cells, const uint8_t* kern,
                     int32_t* out_best /*[S][3] k,i,j*/, uint32_t* out_score, int32_t* out_n_used,
                     double* out_pose /*[S][3]*/, uint64_t* out_stats /*[S][4], may be NULL*/);
+
+/* Which parts of the matcher's kept fields are valid for the map as it is now.
+ * field_tiles (may be NULL; else cap >= TX*TY, DM_ERR_CAPACITY otherwise):
+ * out[ty*TX + tx] = 1 iff the response field holds that tile for the current
+ * table and map version.  *n_field = their count, *n_pool = the pooled field's
+ * built 64x64 tiles (0 when it is stale or absent).  No field yet, or the map
+ * written since: all zero, DM_OK.  Host state only: no GPU work, no wait.
+ * Band and sharded handles: DM_ERR_INVALID_ARG.  A diagnostic, like
+ * dm_frontier_cache_stats: dm_match_scans and dm_match_global build the tiles
+ * their windows reach and nothing else, and this is how a test sees that. */
+int dm_match_built(dm_grid* g, uint8_t* field_tiles, int64_t cap, int64_t* n_field, int64_t* n_pool);
 
 /* ---- map fusion: merge a peer's occupancy map under a rigid transform ----
  *
