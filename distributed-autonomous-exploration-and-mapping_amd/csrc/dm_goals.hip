@@ -235,10 +235,27 @@ static int dm_plan_launch_expand(dm_grid* g, uint8_t* d_out) {
   return DM_OK;
 }
 
+// clearance for clear_cells: d_pen_tab == nullptr: the uint16 d2 into d_d2; else
+// the penalty bytes d_pen_tab[d2] into g->plan_pen
+static int dm_plan_launch_clear(dm_grid* g, int32_t clear_cells, const uint8_t* d_pen_tab, uint16_t* d_d2) {
+  KernelTimer t;
+  dm_timer_begin(g, "plan_clear", &t);
+  if (d_pen_tab)
+    hipLaunchKernelGGL(dm_plan::k_plan_clear<true>, dim3((unsigned)g->NT), dim3(dm_plan::kThreads), 0, g->stream,
+                       g->state, g->tile_seen, g->W, g->H, g->TX, clear_cells, d_pen_tab, nullptr, g->plan_pen);
+  else
+    hipLaunchKernelGGL(dm_plan::k_plan_clear<false>, dim3((unsigned)g->NT), dim3(dm_plan::kThreads), 0, g->stream,
+                       g->state, g->tile_seen, g->W, g->H, g->TX, clear_cells, nullptr, d_d2, nullptr);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  return DM_OK;
+}
+
 // The field from n source cells (host arrays: cells, and their distinct
-// tiles) over g->plan_trav; synchronous.  stats: [4] or nullptr.
+// tiles) over g->plan_trav; synchronous.  stats: [4] or nullptr.  weighted:
+// by k_plan_relax_w over g->plan_pen.
 static int dm_plan_run_field(dm_grid* g, const int64_t* cells, int32_t n, const int32_t* tiles, int32_t n_tiles,
-                      uint32_t max_cost, uint64_t* stats) {
+                      uint32_t max_cost, uint64_t* stats, bool weighted) {
   using namespace dm_plan;
   const int64_t ncell = g->W * g->H;
   hipStream_t s = g->stream;
@@ -282,11 +299,16 @@ static int dm_plan_run_field(dm_grid* g, const int64_t* cells, int32_t n, const 
   KernelTimer t;
   while (!empty && done < bound) {
     const int64_t nb = std::min<int64_t>(batch, bound - done);
-    dm_timer_begin(g, "plan_relax", &t);
+    dm_timer_begin(g, weighted ? "plan_relax_w" : "plan_relax", &t);
     for (int64_t k = 0; k < nb; ++k, ++done) {
-      hipLaunchKernelGGL(k_plan_relax, dim3(grid), dim3(kThreads), 0, s, g->plan_cost, g->plan_travs, g->W, g->H,
-                         g->TX, g->TY, max_cost, g->plan_list[done & 1], g->plan_list[(done + 1) & 1], g->plan_len,
-                         g->plan_stamp, (uint32_t)done, g->plan_stat, g->h_plan.dev());
+      if (weighted)
+        hipLaunchKernelGGL(k_plan_relax_w, dim3(grid), dim3(kThreads), 0, s, g->plan_cost, g->plan_travs, g->plan_pen,
+                           g->W, g->H, g->TX, g->TY, max_cost, g->plan_list[done & 1], g->plan_list[(done + 1) & 1],
+                           g->plan_len, g->plan_stamp, (uint32_t)done, g->plan_stat, g->h_plan.dev());
+      else
+        hipLaunchKernelGGL(k_plan_relax, dim3(grid), dim3(kThreads), 0, s, g->plan_cost, g->plan_travs, g->W, g->H,
+                           g->TX, g->TY, max_cost, g->plan_list[done & 1], g->plan_list[(done + 1) & 1], g->plan_len,
+                           g->plan_stamp, (uint32_t)done, g->plan_stat, g->h_plan.dev());
       DM_HIP(hipGetLastError());
     }
     dm_timer_end(g, &t);
@@ -328,13 +350,17 @@ static int dm_plan_launch_query(dm_grid* g, const double* d_xy, int64_t stride, 
   return DM_OK;
 }
 
-// walk back from *d_start into g->plan_path (cap entries); length and error
-// word go to g->plan_stat[4], [5]
+// walk back from *d_start into g->plan_path (cap entries) by the rule of the
+// field the handle holds; length and error word go to g->plan_stat[4], [5]
 static int dm_plan_launch_path(dm_grid* g, const int64_t* d_start, int64_t cap) {
   KernelTimer t;
   dm_timer_begin(g, "plan_path", &t);
-  hipLaunchKernelGGL(dm_plan::k_plan_path, dim3(1), dim3(64), 0, g->stream, g->plan_cost, g->plan_travs, g->W,
-                     g->H, g->TX, d_start, g->plan_path, cap, g->plan_stat + 4);
+  if (g->plan_weighted)
+    hipLaunchKernelGGL(dm_plan::k_plan_path<true>, dim3(1), dim3(64), 0, g->stream, g->plan_cost, g->plan_travs,
+                       g->plan_pen, g->W, g->H, g->TX, d_start, g->plan_path, cap, g->plan_stat + 4);
+  else
+    hipLaunchKernelGGL(dm_plan::k_plan_path<false>, dim3(1), dim3(64), 0, g->stream, g->plan_cost, g->plan_travs,
+                       nullptr, g->W, g->H, g->TX, d_start, g->plan_path, cap, g->plan_stat + 4);
   DM_HIP(hipGetLastError());
   dm_timer_end(g, &t);
   return DM_OK;
@@ -491,8 +517,10 @@ static int plan_need_field(const dm_grid* g, const char* what) {
   return DM_OK;
 }
 
-// The field from n sources (metres) over g->plan_trav, which the caller computed.
-static int plan_field_from(dm_grid* g, const double* sources_xy, int32_t n, uint32_t max_cost, uint64_t* stats) {
+// The field from n sources (metres) over g->plan_trav, which the caller
+// computed; weighted: over g->plan_pen too (dm_plan_field_cost).
+static int plan_field_from(dm_grid* g, const double* sources_xy, int32_t n, uint32_t max_cost, uint64_t* stats,
+                           bool weighted = false) {
   std::vector<int64_t> cells((size_t)n);
   std::vector<int32_t> tiles;
   for (int32_t i = 0; i < n; ++i) {
@@ -503,10 +531,12 @@ static int plan_field_from(dm_grid* g, const double* sources_xy, int32_t n, uint
     const int32_t t = (int32_t)((y / DM_TILE) * g->TX + x / DM_TILE);
     if (std::find(tiles.begin(), tiles.end(), t) == tiles.end()) tiles.push_back(t);
   }
-  if (max_cost == 0u || max_cost > 0xFFFFFFEFu) max_cost = 0xFFFFFFEFu;
+  const uint32_t cap = weighted ? DM_PLAN_COST_MAX : 0xFFFFFFEFu;
+  if (max_cost == 0u || max_cost > cap) max_cost = cap;
   g->plan_valid = false;
-  int rc = dm_plan_run_field(g, cells.data(), n, tiles.data(), (int32_t)tiles.size(), max_cost, stats);
+  int rc = dm_plan_run_field(g, cells.data(), n, tiles.data(), (int32_t)tiles.size(), max_cost, stats, weighted);
   if (rc) return rc;
+  g->plan_weighted = weighted;
   g->plan_valid = true;
   g->plan_version = dm_map_version(g);
   return DM_OK;
@@ -551,6 +581,50 @@ int dm_plan_field(dm_grid* g, const double* sources_xy, int32_t n_sources, int32
   DM_HIP(dm_join_pass_stream(g));
   if ((rc = dm_plan_launch_travers(g, inflate_cells))) return rc;
   return plan_field_from(g, sources_xy, n_sources, max_cost, out_stats);
+}
+
+static int plan_check_clear(int32_t clear_cells) {
+  if (clear_cells < 1 || clear_cells > 32)
+    return dm_set_error(DM_ERR_INVALID_ARG, "clear_cells must be in [1, 32] (got %d)", clear_cells);
+  return DM_OK;
+}
+
+int dm_plan_clearance(dm_grid* g, int32_t clear_cells, uint16_t* out) {
+  int rc = dm_check_whole_map(g, "dm_plan_clearance");
+  if (rc || (rc = use_device(g))) return rc;
+  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
+  if ((rc = plan_check_clear(clear_cells))) return rc;
+  DM_HIP(dm_join_pass_stream(g));
+  const int64_t cells = g->W * g->H;
+  DevBuf<uint16_t> d;
+  if ((rc = d.alloc(cells, "clearance image"))) return rc;
+  if ((rc = dm_plan_launch_clear(g, clear_cells, nullptr, d))) return rc;
+  hipError_t e = hipMemcpyAsync(out, d, sizeof(uint16_t) * (size_t)cells, hipMemcpyDeviceToHost, g->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+  if (e != hipSuccess) return dm_hip_check(e, "dm_plan_clearance");
+  return DM_OK;
+}
+
+int dm_plan_field_cost(dm_grid* g, const double* sources_xy, int32_t n_sources, int32_t inflate_cells,
+                       int32_t clear_cells, const uint8_t* pen, uint32_t max_cost, uint64_t* out_stats) {
+  int rc = dm_check_whole_map(g, "dm_plan_field_cost");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n_sources < 1 || n_sources > 256)
+    return dm_set_error(DM_ERR_INVALID_ARG, "n_sources must be in [1, 256] (got %d)", n_sources);
+  if (!sources_xy) return dm_set_error(DM_ERR_INVALID_ARG, "sources_xy is NULL");
+  if (!pen) return dm_set_error(DM_ERR_INVALID_ARG, "pen is NULL");
+  if ((rc = plan_check_inflate(inflate_cells)) || (rc = plan_check_clear(clear_cells))) return rc;
+  g->plan_valid = false;  // an allocation that fails below leaves no field
+  if ((rc = ensure_plan(g))) return rc;
+  if (!g->plan_pen && (rc = g->plan_pen.alloc(g->W * g->H, "cell penalties"))) return rc;
+  if (!g->plan_pen_tab && (rc = g->plan_pen_tab.alloc(32 * 32 + 2, "penalty table"))) return rc;
+  DM_HIP(dm_join_pass_stream(g));
+  // pen is the caller's: on the device before this call returns (the field's wait at the latest)
+  DM_HIP(hipMemcpyAsync(g->plan_pen_tab, pen, (size_t)(clear_cells * clear_cells + 2), hipMemcpyHostToDevice,
+                        g->stream));
+  if ((rc = dm_plan_launch_clear(g, clear_cells, g->plan_pen_tab, nullptr))) return rc;
+  if ((rc = dm_plan_launch_travers(g, inflate_cells))) return rc;
+  return plan_field_from(g, sources_xy, n_sources, max_cost, out_stats, true);
 }
 
 int dm_plan_get_field(dm_grid* g, uint32_t* out) {

@@ -12,6 +12,11 @@
 //                   traversable (no corner cutting); the rule is symmetric
 //   cost[c]         least total move cost from any source over traversable
 //                   cells, kUnreach where none is <= max_cost
+//   d2[c]           clearance for R: the least dx^2 + dy^2 <= R^2 to an in-grid
+//                   occupied cell, R^2 + 1 if none (k_plan_clear)
+//   weighted move   entering c costs b * (1 + pen[d2[c]]), b = 5 / 7, pen the
+//                   caller's uint8 table; the weighted field (k_plan_relax_w,
+//                   dm_plan_field_cost) is cost[c] with that move cost
 // The host restatement (Dijkstra) is dm/plan.py.
 //
 // Round structure (k_plan_relax): the host launches rounds over a worklist of
@@ -58,6 +63,25 @@ __device__ inline int trav_bit(const uint64_t* __restrict__ trav, int64_t TX, in
   return (int)((trav[((y >> 6) * TX + (x >> 6)) * DM_TILE + (y & 63)] >> (x & 63)) & 1ull);
 }
 
+// The occupied bit rows into s_occ[row = y - y0 + 32][left, centre, right
+// word], for k_plan_travers and k_plan_clear.  Called by all kThreads
+// threads; the caller places the barrier.
+__device__ inline void load_occ_halo(const int8_t* __restrict__ state, const uint8_t* __restrict__ tile_seen,
+                                     int64_t W, int64_t H, int64_t TX, int64_t x0, int64_t y0, int32_t r,
+                                     unsigned long long (*s_occ)[3]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int j = wave; j < 2 * DM_TILE * 3; j += kThreads / 64) {
+    const int row = j / 3, wc = j % 3;
+    const int64_t gy = y0 - 32 + row, gx = x0 + (int64_t)(wc - 1) * DM_TILE + lane;
+    bool occ = false;
+    if (row >= 32 - r && row < 32 + DM_TILE + r && gy >= 0 && gy < H && gx >= 0 && gx < W && gx >= x0 - r &&
+        gx < x0 + DM_TILE + r && tile_seen[(gy >> 6) * TX + (gx >> 6)])
+      occ = state[gy * W + gx] == 100;
+    const unsigned long long word = __ballot(occ);
+    if (lane == 0) s_occ[row][wc] = word;
+  }
+}
+
 // ---- 1. traversability ------------------------------------------------------
 // Workgroup = tile.  The occupied bits of the tile's rows with a 32-row halo
 // above and below, three 64-bit words per row (the tile's columns and the 64
@@ -88,16 +112,7 @@ __global__ __launch_bounds__(kThreads) void k_plan_travers(const int8_t* __restr
     while ((h + 1) * (h + 1) + d * d <= r * r) ++h;
     s_hw[d] = h;
   }
-  for (int j = wave; j < 2 * DM_TILE * 3; j += kThreads / 64) {
-    const int row = j / 3, wc = j % 3;
-    const int64_t gy = y0 - 32 + row, gx = x0 + (int64_t)(wc - 1) * DM_TILE + lane;
-    bool occ = false;
-    if (row >= 32 - r && row < 32 + DM_TILE + r && gy >= 0 && gy < H && gx >= 0 && gx < W && gx >= x0 - r &&
-        gx < x0 + DM_TILE + r && tile_seen[(gy >> 6) * TX + (gx >> 6)])
-      occ = state[gy * W + gx] == 100;
-    const unsigned long long word = __ballot(occ);
-    if (lane == 0) s_occ[row][wc] = word;
-  }
+  load_occ_halo(state, tile_seen, W, H, TX, x0, y0, r, s_occ);
   for (int row = wave; row < DM_TILE; row += kThreads / 64) {
     const int64_t gy = y0 + row, gx = x0 + lane;
     const bool fr = gy < H && gx < W && state[gy * W + gx] == 0;
@@ -138,6 +153,64 @@ __global__ void k_plan_expand(const uint64_t* __restrict__ trav, int64_t W, int6
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= W * H) return;
   out[i] = (uint8_t)trav_bit(trav, TX, i % W, i / W);
+}
+
+// ---- 1b. clearance ------------------------------------------------------------
+// d2[c] = the least dx^2 + dy^2 <= R^2 to an occupied cell, R^2 + 1 ("far")
+// if there is none; for every cell, whatever its state and its tile's
+// tile_seen (an untouched tile holds no obstacle but lies near others').
+// Workgroup = tile, over the same halo words as k_plan_travers.  A wave
+// takes 16 rows, a lane a column: for each dy the three words of row y + dy
+// are one LDS address for the whole wave (a broadcast read, and an empty row
+// is skipped by a wave-uniform branch), the lane aligns the 128 columns
+// around its own to bit 63 (leftwards) and bit 0 (rightwards) and takes the
+// nearest set bit by clz / ffs: |dx|, exact, and d2 = min(|dx|^2 + dy^2).
+// The other exact form, a vertical distance per column of the 64 + 2R and
+// then a minimum over dx, reads one distinct LDS value per lane and dx,
+// (2R + 1) non-broadcast reads per cell against (2R + 1) broadcasts here, and
+// cannot skip empty rows.
+// kPen: write pen[d2] as one byte per cell (the table in LDS), for
+// k_plan_relax_w; else the uint16 d2 itself (dm_plan_clearance).
+template <bool kPen>
+__global__ __launch_bounds__(kThreads) void k_plan_clear(const int8_t* __restrict__ state,
+                                                         const uint8_t* __restrict__ tile_seen, int64_t W,
+                                                         int64_t H, int64_t TX, int32_t R,
+                                                         const uint8_t* __restrict__ pen,
+                                                         uint16_t* __restrict__ out_d2,
+                                                         uint8_t* __restrict__ out_pen) {
+  __shared__ unsigned long long s_occ[2 * DM_TILE][3];
+  __shared__ uint8_t s_pen[kPen ? 32 * 32 + 2 : 1];
+  const int64_t tile = blockIdx.x, tx = tile % TX, ty = tile / TX;
+  const int64_t x0 = tx * DM_TILE, y0 = ty * DM_TILE;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  load_occ_halo(state, tile_seen, W, H, TX, x0, y0, R, s_occ);
+  if (kPen)
+    for (int i = threadIdx.x; i < R * R + 2; i += kThreads) s_pen[i] = pen[i];
+  __syncthreads();
+  const int far = R * R + 1;
+  const int64_t gx = x0 + lane;
+  for (int i = 0; i < 16; ++i) {
+    const int y = wave * 16 + i;
+    int best = far;
+    for (int dy = -R; dy <= R; ++dy) {
+      const int row = y + 32 + dy;
+      const unsigned long long L = s_occ[row][0], C = s_occ[row][1], Rr = s_occ[row][2];
+      if ((L | C | Rr) == 0ull) continue;
+      // columns x, x - 1, ... from bit 63 down; columns x, x + 1, ... from bit 0 up
+      const unsigned long long lw = (C << (63 - lane)) | ((L >> 1) >> lane);
+      const unsigned long long rw = (C >> lane) | ((Rr << 1) << (63 - lane));
+      const int dl = lw ? __clzll((long long)lw) : 64, dr = rw ? __ffsll((long long)rw) - 1 : 64;
+      const int d = min(dl, dr);
+      best = min(best, d * d + dy * dy);  // a candidate outside the disc is > R^2: "far" stays below it
+    }
+    const int64_t gy = y0 + y;
+    if (gy < H && gx < W) {
+      if (kPen)
+        out_pen[gy * W + gx] = s_pen[best];
+      else
+        out_d2[gy * W + gx] = (uint16_t)best;
+    }
+  }
 }
 
 // ---- 2. relaxation ----------------------------------------------------------
@@ -289,6 +362,165 @@ __global__ __launch_bounds__(kThreads) void k_plan_relax(uint32_t* __restrict__ 
   }
 }
 
+// One round of the penalty-weighted field: entering cell c by a legal move
+// costs b * (1 + pen[c]), b = 5 / 7.  The round structure, lists, stamps and
+// host words are k_plan_relax's, and so is the argument that the field needs
+// no atomics (values only fall, every stored value is the cost of a real
+// path); k_plan_relax itself is left as it is, so the unweighted planner keeps
+// its code.  What differs:
+//   * only the cells this workgroup relaxes are ever entered, so the entering
+//     costs are loaded for the tile's own 64 x 64 cells, not for the ring; they
+//     are kept as the row's prefix sums s_P[row][k] = sum of 5 * (1 + pen) over
+//     columns < k (at most 64 * 1280), built once per visit by a wave scan;
+//     a cell's own orthogonal cost is s_P[k + 1] - s_P[k], its diagonal 7/5 of it;
+//   * the row scan: within a run of traversable cells, moving right from x' to
+//     x enters x' + 1 .. x, moving left from x' to x enters x .. x' - 1, so
+//     best[x] = min over x' of best[x'] + |s_P[..x] - s_P[..x']|; each
+//     Kogge-Stone step shuffles the prefix sum along with best.  A candidate
+//     that ends <= max_cost is <= max_cost at every step on the way (weights
+//     are positive), so the guard delta <= max_cost - o drops nothing valid.
+__global__ __launch_bounds__(kThreads) void k_plan_relax_w(uint32_t* __restrict__ cost,
+                                                           const uint64_t* __restrict__ travs,
+                                                           const uint8_t* __restrict__ pen, int64_t W, int64_t H,
+                                                           int64_t TX, int64_t TY, uint32_t max_cost,
+                                                           const int32_t* __restrict__ list_in,
+                                                           int32_t* __restrict__ list_out, unsigned int* len,
+                                                           uint32_t* __restrict__ stamp, uint32_t round,
+                                                           unsigned long long* __restrict__ stat,
+                                                           volatile unsigned long long* hstat) {
+  __shared__ uint32_t s_c[kRing][kRing];
+  __shared__ uint32_t s_P[DM_TILE][DM_TILE + 1];
+  __shared__ unsigned long long s_tw[kRing][3];
+  __shared__ uint8_t s_t[kRing][kRing + 2];
+  __shared__ int s_flags;
+  const unsigned int n_in = len[round % 3u];
+  unsigned int* const len_out = &len[(round + 1u) % 3u];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    len[(round + 2u) % 3u] = 0u;
+    hstat[HS_LEN] = n_in;
+    if (n_in) {
+      const unsigned long long relax = stat[ST_RELAX] + n_in;
+      stat[ST_ROUNDS] = round + 1u;
+      stat[ST_RELAX] = relax;
+      hstat[HS_ROUNDS] = round + 1u;
+      hstat[HS_RELAX] = relax;
+      hstat[HS_TRAV] = stat[ST_TRAV];
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (unsigned int item = blockIdx.x; item < n_in; item += gridDim.x) {
+    const int64_t tile = list_in[item], tx = tile % TX, ty = tile / TX;
+    const int64_t x0 = tx * DM_TILE, y0 = ty * DM_TILE;
+    if (threadIdx.x == 0) s_flags = 0;
+    for (int j = threadIdx.x; j < kRing * 3; j += kThreads) {
+      const int row = j / 3, wc = j % 3;
+      const int64_t gy = y0 - 1 + row, ntx = tx + wc - 1;
+      unsigned long long w = 0ull;
+      if (gy >= 0 && gy < H && ntx >= 0 && ntx < TX) w = travs[((gy >> 6) * TX + ntx) * DM_TILE + (gy & 63)];
+      s_tw[row][wc] = w;
+    }
+    // prefix sums of the rows' orthogonal entering costs (cells outside the grid are never entered)
+    for (int i = 0; i < 16; ++i) {
+      const int row = wave * 16 + i;
+      const int64_t gy = y0 + row, gx = x0 + lane;
+      uint32_t p = gy < H && gx < W ? 5u * (1u + pen[gy * W + gx]) : 0u;
+#pragma unroll
+      for (int d = 1; d < DM_TILE; d <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)p, d);
+        if (lane >= d) p += o;
+      }
+      s_P[row][lane + 1] = p;
+      if (lane == 0) s_P[row][0] = 0u;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < kRing * kRing; j += kThreads) {
+      const int row = j / kRing, col = j % kRing;
+      const int wc = col == 0 ? 0 : (col == kRing - 1 ? 2 : 1);
+      const int bit = col == 0 ? 63 : (col == kRing - 1 ? 0 : col - 1);
+      const int t = (int)((s_tw[row][wc] >> bit) & 1ull);
+      s_t[row][col] = (uint8_t)t;
+      s_c[row][col] = t ? cost[(y0 - 1 + row) * W + (x0 - 1 + col)] : kUnreach;
+    }
+    __syncthreads();
+    uint32_t init[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) init[i] = s_c[wave * 16 + i + 1][lane + 1];
+    bool converged = false;
+    for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
+      int ch = 0;
+      for (int ii = 0; ii < 16; ++ii) {  // wave-uniform: the row scans below shuffle across all lanes
+        const int i = (sweep & 1) ? 15 - ii : ii;
+        const int rr = wave * 16 + i + 1, cc = lane + 1;
+        const int t = s_t[rr][cc];
+        const uint32_t cur = s_c[rr][cc];  // kUnreach > max_cost where the cell is not traversable
+        const uint32_t Pl = s_P[rr - 1][lane], Pr = s_P[rr - 1][lane + 1];  // sums before / through this column
+        uint32_t best = cur;
+        if (t) {
+          const uint32_t e5 = Pr - Pl, e7 = e5 / 5u * 7u;  // entering this cell; <= 1792 < kUnreach - max_cost
+          const uint32_t cn = s_c[rr - 1][cc], cs = s_c[rr + 1][cc], cw = s_c[rr][cc - 1], ce = s_c[rr][cc + 1];
+          if (cn <= max_cost) best = min(best, cn + e5);
+          if (cs <= max_cost) best = min(best, cs + e5);
+          if (cw <= max_cost) best = min(best, cw + e5);
+          if (ce <= max_cost) best = min(best, ce + e5);
+          const int tn = s_t[rr - 1][cc], ts = s_t[rr + 1][cc], tw = s_t[rr][cc - 1], te = s_t[rr][cc + 1];
+          if (tn && tw) { const uint32_t v = s_c[rr - 1][cc - 1]; if (v <= max_cost) best = min(best, v + e7); }
+          if (tn && te) { const uint32_t v = s_c[rr - 1][cc + 1]; if (v <= max_cost) best = min(best, v + e7); }
+          if (ts && tw) { const uint32_t v = s_c[rr + 1][cc - 1]; if (v <= max_cost) best = min(best, v + e7); }
+          if (ts && te) { const uint32_t v = s_c[rr + 1][cc + 1]; if (v <= max_cost) best = min(best, v + e7); }
+          if (best > max_cost) best = cur;
+        }
+        const unsigned long long gaps = ~s_tw[rr][1];
+        const unsigned long long gl = gaps & ((2ull << lane) - 1ull), gr = gaps >> lane;
+        const int run_l = gl ? lane - (63 - __clzll((long long)gl)) : lane + 1;
+        const int run_r = gr ? __ffsll((long long)gr) - 1 : 64 - lane;
+#pragma unroll
+        for (int d = 1; d < DM_TILE; d <<= 1) {  // from x - d: enters x - d + 1 .. x
+          const uint32_t o = (uint32_t)__shfl_up((int)best, d);
+          const uint32_t delta = Pr - (uint32_t)__shfl_up((int)Pr, d);
+          if (run_l > d && o <= max_cost && delta <= max_cost - o) best = min(best, o + delta);
+        }
+#pragma unroll
+        for (int d = 1; d < DM_TILE; d <<= 1) {  // from x + d: enters x .. x + d - 1
+          const uint32_t o = (uint32_t)__shfl_down((int)best, d);
+          const uint32_t delta = (uint32_t)__shfl_down((int)Pl, d) - Pl;
+          if (run_r > d && o <= max_cost && delta <= max_cost - o) best = min(best, o + delta);
+        }
+        if (best < cur) {
+          s_c[rr][cc] = best;
+          ch = 1;
+        }
+      }
+      if (!__syncthreads_or(ch)) {
+        converged = true;
+        break;
+      }
+    }
+    int flags = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = wave * 16 + i, col = lane;
+      const uint32_t v = s_c[row + 1][col + 1];
+      if (v != init[i]) cost[(y0 + row) * W + (x0 + col)] = v;
+      if (v != (round == 0u ? kUnreach : init[i])) {
+        const int n = row == 0, s = row == DM_TILE - 1, w = col == 0, e = col == DM_TILE - 1;
+        flags |= (n << 1) | (s << 7) | (w << 3) | (e << 5) | ((n & w) << 0) | ((n & e) << 2) | ((s & w) << 6) |
+                 ((s & e) << 8);
+      }
+    }
+    if (!converged) flags |= 1 << 4;
+    if (flags) atomicOr(&s_flags, flags);
+    __syncthreads();
+    if (threadIdx.x < 9 && ((s_flags >> threadIdx.x) & 1)) {
+      const int64_t ntx = tx + (int)(threadIdx.x % 3) - 1, nty = ty + (int)(threadIdx.x / 3) - 1;
+      if (ntx >= 0 && ntx < TX && nty >= 0 && nty < TY) {
+        const int64_t nt = nty * TX + ntx;
+        if (atomicExch(&stamp[nt], round + 2u) != round + 2u) list_out[atomicAdd(len_out, 1u)] = (int32_t)nt;
+      }
+    }
+    __syncthreads();
+  }
+}
+
 __global__ __launch_bounds__(kThreads) void k_plan_count(const uint32_t* __restrict__ cost, int64_t n,
                                                          unsigned long long* __restrict__ stat) {
   __shared__ int s_n;
@@ -345,8 +577,12 @@ __global__ void k_plan_query(const uint32_t* __restrict__ cost, int64_t W, int64
 // cost + w == the cell's cost is the predecessor.  out[] takes the cells
 // target-first up to cap; n_out[0] the full length, n_out[1] != 0 if the walk
 // found no predecessor (a field that is no fixpoint: never for a complete one).
+// kWeighted: the field is k_plan_relax_w's, a move into the cell costs
+// 5 / 7 times 1 + pen[cell]; false is the unweighted kernel, pen unused.
+template <bool kWeighted>
 __global__ __launch_bounds__(64) void k_plan_path(const uint32_t* __restrict__ cost,
-                                                  const uint64_t* __restrict__ travs, int64_t W, int64_t H,
+                                                  const uint64_t* __restrict__ travs,
+                                                  const uint8_t* __restrict__ pen, int64_t W, int64_t H,
                                                   int64_t TX, const int64_t* __restrict__ start,
                                                   int64_t* __restrict__ out, int64_t cap,
                                                   unsigned long long* __restrict__ n_out) {
@@ -368,7 +604,8 @@ __global__ __launch_bounds__(64) void k_plan_path(const uint32_t* __restrict__ c
       uint32_t nc = kUnreach;
       if (lane < 8 && nx >= 0 && nx < W && ny >= 0 && ny < H) {
         nc = cost[ny * W + nx];
-        const uint32_t w = (dx != 0 && dy != 0) ? 7u : 5u;
+        uint32_t w = (dx != 0 && dy != 0) ? 7u : 5u;
+        if (kWeighted) w *= 1u + pen[cur];
         ok = nc != kUnreach && (unsigned long long)nc + w == (unsigned long long)c;
         if (ok && dx != 0 && dy != 0) ok = trav_bit(travs, TX, x, ny) && trav_bit(travs, TX, nx, y);
       }

@@ -193,6 +193,8 @@ SIGNATURES = {
     "dm_assign_goals": [_vp, _vp, _i32, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _vp, _vp],
     "dm_plan_traversable": [_vp, _i32, _vp],
     "dm_plan_field": [_vp, _vp, _i32, _i32, ctypes.c_uint32, _vp],
+    "dm_plan_clearance": [_vp, _i32, _vp],
+    "dm_plan_field_cost": [_vp, _vp, _i32, _i32, _i32, _vp, ctypes.c_uint32, _vp],
     "dm_plan_get_field": [_vp, _vp],
     "dm_plan_query": [_vp, _vp, _i64, _i32, _vp, _vp],
     "dm_plan_path": [_vp, ctypes.c_double, ctypes.c_double, _i32, _vp, _i64, ctypes.POINTER(_i64)],

@@ -341,6 +341,34 @@ class OccupancyMapper:
             check(self._lib.dm_plan_field(self._handle(), _vp(xy), xy.shape[0], int(inflate_cells), int(max_cost), st))
         return {k: int(st[i]) for i, k in enumerate(self.PLAN_STAT_NAMES)}
 
+    def plan_clearance(self, clear_cells: int) -> np.ndarray:
+        """The capped squared obstacle distance (dm_plan_clearance): uint16
+        [rows, W], clear_cells**2 + 1 where no occupied cell lies within
+        clear_cells.  Same values as dm.plan.clearance."""
+        out = np.empty((self.rows, self.width), np.uint16)
+        with self._lock:
+            check(self._lib.dm_plan_clearance(self._handle(), int(clear_cells), _vp(out)))
+        return out
+
+    def plan_field_cost(self, sources_xy, inflate_cells: int, clear_cells: int, pen, max_cost: int = 0) -> dict:
+        """plan_field with a penalty on cells near obstacles
+        (dm_plan_field_cost): entering a cell costs 5 or 7 times
+        1 + pen[its clearance], for a uint8 table of clear_cells**2 + 2 entries
+        (dm.plan.inflation_table builds Nav2's).  The weighted field stays in
+        the handle like plan_field's, and plan_path follows it.  Returns the
+        call's statistics (PLAN_STAT_NAMES)."""
+        xy = np.ascontiguousarray(np.asarray(sources_xy, np.float64).reshape(-1, 2))
+        tab = None
+        if pen is not None:
+            tab = np.ascontiguousarray(pen, np.uint8)
+            if 1 <= int(clear_cells) <= 32 and tab.shape != (int(clear_cells) ** 2 + 2,):
+                raise DmError(_ffi.DM_ERR_INVALID_ARG, f"pen must have clear_cells**2 + 2 entries (got {tab.shape})")
+        st = (ctypes.c_uint64 * 4)()
+        with self._lock:
+            check(self._lib.dm_plan_field_cost(self._handle(), _vp(xy), xy.shape[0], int(inflate_cells),
+                                               int(clear_cells), None if tab is None else _vp(tab), int(max_cost), st))
+        return {k: int(st[i]) for i, k in enumerate(self.PLAN_STAT_NAMES)}
+
     def plan_cost_field(self) -> np.ndarray:
         """The field (dm_plan_get_field): uint32 [rows, W], costs in fifths of
         a cell (orthogonal move 5, diagonal 7), dm.plan.UNREACHABLE where no

@@ -19,6 +19,14 @@ integers only, so the results are unique:
 The device computes the field by tile-wise min-relaxation; here it is
 Dijkstra (scipy) over the legal-move graph.  The fixpoint of min-relaxation is
 unique, so both give the same bits.
+
+Clearance-aware planning (dm_plan_clearance, dm_plan_field_cost):
+
+* ``d2[c]`` is the least ``dx*dx + dy*dy <= R*R`` to an in-grid occupied cell,
+  ``R*R + 1`` ("far") if there is none;
+* entering cell c by a legal move costs ``b * (1 + pen[d2[c]])``, b = 5 / 7,
+  for a caller-supplied uint8 table ``pen[R*R + 2]``;
+* the weighted field and its paths are defined as above with that move cost.
 """
 from __future__ import annotations
 
@@ -28,6 +36,7 @@ import numpy as np
 
 UNREACHABLE = 0xFFFFFFFF
 MAX_COST = 0xFFFFFFEF  # what max_cost == 0 means: a stored cost plus a move never wraps
+COST_MAX_WEIGHTED = 0xFFFFF7FF  # the same for a weighted field (DM_PLAN_COST_MAX): a move costs up to 1792
 ORTHOGONAL, DIAGONAL = 5, 7
 # predecessor order of a path, (dy, dx)
 NEIGHBOURS = ((-1, -1), (-1, 0), (-1, 1), (0, -1), (0, 1), (1, -1), (1, 0), (1, 1))
@@ -58,6 +67,57 @@ def traversable(state, r: int) -> np.ndarray:
                 if dx * dx + dy * dy <= r * r:
                     blocked |= _shifted(occ, dy, dx)
     return (st == 0) & ~blocked
+
+
+def _check_clear(R: int) -> int:
+    R = int(R)
+    if not 1 <= R <= 32:
+        raise ValueError("clear_cells must be in [1, 32]")
+    return R
+
+
+def clearance(state, R: int) -> np.ndarray:
+    """uint16 [H, W]: the capped squared distance d2 to the nearest occupied
+    cell, R*R + 1 where none lies within R.  The Euclidean distance transform
+    returns the nearest obstacle's indices, so d2 is exact integer arithmetic."""
+    from scipy.ndimage import distance_transform_edt
+
+    st = np.asarray(state)
+    R = _check_clear(R)
+    far = R * R + 1
+    occ = st == 100
+    if not occ.any():
+        return np.full(st.shape, far, np.uint16)
+    idx = distance_transform_edt(~occ, return_distances=False, return_indices=True)
+    yy, xx = np.indices(st.shape)
+    d2 = (idx[0] - yy).astype(np.int64) ** 2 + (idx[1] - xx).astype(np.int64) ** 2
+    return np.where(d2 <= R * R, d2, far).astype(np.uint16)
+
+
+def penalty(state, R: int, pen) -> np.ndarray:
+    """uint8 [H, W]: pen[d2] per cell, for a table uint8 [R*R + 2]."""
+    R = _check_clear(R)
+    tab = np.asarray(pen)
+    if tab.shape != (R * R + 2,):
+        raise ValueError(f"pen must have R*R + 2 = {R * R + 2} entries")
+    if tab.dtype != np.uint8 and (tab.min() < 0 or tab.max() > 255):
+        raise ValueError("pen entries must be in [0, 255]")
+    return tab.astype(np.uint8)[clearance(state, R)]
+
+
+def inflation_table(resolution: float, clear_cells: int, inscribed_m: float, cost_scaling: float) -> np.ndarray:
+    """Nav2's inflation curve as a penalty table uint8 [R*R + 2]: 252 within
+    the inscribed radius (d = sqrt(d2) * resolution <= inscribed_m), else
+    floor(252 * exp(-cost_scaling * (d - inscribed_m))); far = 0."""
+    R = _check_clear(clear_cells)
+    out = np.zeros(R * R + 2, np.uint8)
+    for d2 in range(R * R + 1):
+        d = math.sqrt(d2) * float(resolution)
+        if d <= inscribed_m:
+            out[d2] = 252
+        else:
+            out[d2] = int(math.floor(252.0 * math.exp(-float(cost_scaling) * (d - inscribed_m))))
+    return out
 
 
 def cell_of(x: float, y: float, origin_x: float, origin_y: float, resolution: float, width: int, height: int):
@@ -92,9 +152,12 @@ def legal_moves(trav: np.ndarray):
     return out
 
 
-def field(state, sources_cells, r: int, max_cost: int = 0, trav: np.ndarray | None = None) -> np.ndarray:
+def field(state, sources_cells, r: int, max_cost: int = 0, trav: np.ndarray | None = None,
+          cell_pen: np.ndarray | None = None) -> np.ndarray:
     """uint32 [H, W] distance field from the source cells [(cx, cy), ...].
-    `trav`: a traversable mask to use instead of traversable(state, r)."""
+    `trav`: a traversable mask to use instead of traversable(state, r).
+    `cell_pen`: uint8 [H, W]; entering cell c costs b * (1 + cell_pen[c]) and
+    the cap of max_cost is the weighted field's (field_cost)."""
     from scipy.sparse import csr_matrix
     from scipy.sparse.csgraph import dijkstra
 
@@ -103,13 +166,16 @@ def field(state, sources_cells, r: int, max_cost: int = 0, trav: np.ndarray | No
         raise ValueError("need at least one source")
     t = with_sources(traversable(state, r) if trav is None else trav, sources)
     H, W = t.shape
-    max_cost = MAX_COST if int(max_cost) == 0 or int(max_cost) > MAX_COST else int(max_cost)
+    cap = MAX_COST if cell_pen is None else COST_MAX_WEIGHTED
+    max_cost = cap if int(max_cost) == 0 or int(max_cost) > cap else int(max_cost)
+    mult = None if cell_pen is None else 1.0 + np.asarray(cell_pen, np.float64).reshape(-1)
     src, dst, wgt = [], [], []
     for (dy, dx), ok in zip(NEIGHBOURS, legal_moves(t)):
         c = np.flatnonzero(ok)
         src.append(c)
         dst.append(c + dy * W + dx)
-        wgt.append(np.full(c.shape, DIAGONAL if dy and dx else ORTHOGONAL, np.float64))
+        b = float(DIAGONAL if dy and dx else ORTHOGONAL)
+        wgt.append(np.full(c.shape, b) if mult is None else b * mult[c + dy * W + dx])
     g = csr_matrix((np.concatenate(wgt), (np.concatenate(src), np.concatenate(dst))), shape=(H * W, H * W))
     idx = sorted({cy * W + cx for cx, cy in sources})
     d = dijkstra(g, directed=True, indices=idx, min_only=True, limit=float(max_cost))
@@ -117,6 +183,12 @@ def field(state, sources_cells, r: int, max_cost: int = 0, trav: np.ndarray | No
     ok = np.isfinite(d) & (d <= max_cost)
     out[ok] = d[ok].astype(np.uint32)  # integer costs are exact in float64
     return out.reshape(H, W)
+
+
+def field_cost(state, sources_cells, r: int, R: int, pen, max_cost: int = 0) -> np.ndarray:
+    """uint32 [H, W]: the penalty-weighted field (dm_plan_field_cost): Dijkstra
+    with the move into cell c costing b * (1 + pen[d2[c]])."""
+    return field(state, sources_cells, r, max_cost, cell_pen=penalty(state, R, pen))
 
 
 def snap(cost: np.ndarray, cell, s: int):
@@ -141,11 +213,12 @@ def snap(cost: np.ndarray, cell, s: int):
     return int(cost.reshape(-1)[best[1]]), int(best[1])
 
 
-def path(cost: np.ndarray, trav: np.ndarray, cell: int) -> list[int]:
+def path(cost: np.ndarray, trav: np.ndarray, cell: int, cell_pen: np.ndarray | None = None) -> list[int]:
     """Linear indices from a source to `cell` (a reached cell; -1: empty
     path).  `trav` includes the sources (with_sources).  The predecessor of c
     is the first neighbour in NEIGHBOURS order that is reached, moves legally
-    to c and has cost + w == cost[c]."""
+    to c and has cost + w == cost[c]; with `cell_pen` (uint8 [H, W], the
+    field being field_cost's) w is b * (1 + cell_pen[c])."""
     if cell < 0:
         return []
     H, W = cost.shape
@@ -159,6 +232,8 @@ def path(cost: np.ndarray, trav: np.ndarray, cell: int) -> list[int]:
             if not (0 <= nx < W and 0 <= ny < H) or cost[ny, nx] == UNREACHABLE:
                 continue
             w = DIAGONAL if dy and dx else ORTHOGONAL
+            if cell_pen is not None:
+                w *= 1 + int(cell_pen[y, x])
             if int(cost[ny, nx]) + w != int(cost[y, x]):
                 continue
             if dy and dx and not (trav[ny, x] and trav[y, nx]):

@@ -244,6 +244,12 @@ class SlamParams:
     dm_goal_path_distance: bool = False
     dm_goal_inflate_m: float = 0.10       # obstacle inflation radius (the robot's)
     dm_goal_snap_m: float = 0.25          # how far a goal may move to reach a traversable cell
+    # keep /plan away from walls: the path comes from a field whose moves cost
+    # more within this distance of an obstacle (dm_plan_field_cost with Nav2's
+    # inflation curve, inscribed radius dm_goal_inflate_m); the goal itself is
+    # chosen as before.  0: off, /plan is the shortest path, as before
+    dm_plan_clearance_m: float = 0.0
+    dm_plan_cost_scaling: float = 10.0    # Nav2's cost_scaling_factor (its default)
     # score goals by what the sensor would see from them, the unknown cells its
     # rays reach on the current map (dm_assign_goals_gain), in place of the
     # frontier's size; implies dm_goal_path_distance; off: as before
@@ -305,6 +311,14 @@ class SlamParams:
         inflate = int(math.ceil(float(self.dm_goal_inflate_m) / res))
         snap = int(math.ceil(float(self.dm_goal_snap_m) / res))
         return min(max(inflate, 0), 32), min(max(snap, 0), 16)
+
+    def clearance_cells(self) -> int:
+        """dm_plan_clearance_m in cells, ceil(x / resolution), clamped to the
+        C-ABI's limits [1, 32]; 0: off."""
+        m = float(self.dm_plan_clearance_m)
+        if not m > 0.0:
+            return 0
+        return min(max(int(math.ceil(m / float(self.resolution))), 1), 32)
 
     def gain_radius_cells(self) -> int:
         """dm_goal_gain_radius_m in cells, ceil(x / resolution), clamped to the
@@ -708,7 +722,10 @@ class MappingNode:
         dm_goal_information_gain the score's numerator is the unknown area
         visible from that cell (dm_assign_goals_gain), kept in ``last_gain``;
         with dm_goal_coordinate it is what of that the peers' goals do not
-        already see (dm_assign_goals_coord with ``peer_goals`` held)."""
+        already see (dm_assign_goals_coord with ``peer_goals`` held).  With
+        dm_plan_clearance_m the goal is chosen the same way and the path is
+        taken from the penalty-weighted field from the robot instead
+        (dm_plan_field_cost), so it keeps its distance from walls."""
         s = self.slam
         inflate, snap = s.goal_cells()
         if s.dm_goal_coordinate:
@@ -735,6 +752,12 @@ class MappingNode:
         gx, gy = g[1]
         header = Header(stamp=stamp, frame_id=s.map_frame)
         p = self.params
+        R = s.clearance_cells()
+        if R:
+            from .plan import inflation_table
+
+            pen = inflation_table(float(p.resolution), R, float(s.dm_goal_inflate_m), float(s.dm_plan_cost_scaling))
+            self.mapper.plan_field_cost([(x, y)], inflate, R, pen)
         cells = self.mapper.plan_path((gx, gy), snap_cells=0)
         px = float(p.origin_x) + ((cells % int(p.width)) + 0.5) * float(p.resolution)
         py = float(p.origin_y) + ((cells // int(p.width)) + 0.5) * float(p.resolution)

@@ -439,7 +439,8 @@ int dm_assign_goals(dm_grid* g, const double* robots_xy, int32_t n_robots, int64
 
 /* The traversability mask: out[height*width] = 1 / 0, row-major.  Replaces
  * the inflation layer of Nav2's global costmap (binary: lethal within the
- * inflation radius).  Does not touch the handle's field. */
+ * inflation radius; the graded cost around it: dm_plan_field_cost below).
+ * Does not touch the handle's field. */
 int dm_plan_traversable(dm_grid* g, int32_t inflate_cells, uint8_t* out);
 /* Compute the field from n_sources (1..256) points sources_xy[2i], [2i+1]
  * (metres; one outside the grid: DM_ERR_INVALID_ARG).  out_stats (may be
@@ -464,6 +465,41 @@ int dm_plan_query(dm_grid* g, const double* targets_xy, int64_t n, int32_t snap_
  * for the goal published on /goal_pose. */
 int dm_plan_path(dm_grid* g, double tx, double ty, int32_t snap_cells, int64_t* out_cells, int64_t cap,
                  int64_t* n_out);
+
+/* ---- Clearance-aware planning: the graded half of Nav2's inflation layer.
+ * dm_plan_field's paths are shortest, so they pass every inside corner at
+ * exactly the inflation radius; a cost that grows towards obstacles keeps them
+ * in the middle of a corridor.  Same conventions as the block above.
+ *   Clearance, for clear_cells = R in [1, 32]: d2[c] = the least dx*dx + dy*dy
+ *     over in-grid cells with state == 100 within dx*dx + dy*dy <= R*R, and
+ *     R*R + 1 ("far") if there is none; 0 on an occupied cell; defined for
+ *     every cell whatever its state.  Out-of-grid cells are not obstacles.
+ *   Penalty table: the caller's uint8 pen[R*R + 2], indexed by d2 (the last
+ *     entry is "far"); any table is valid.  The library computes no exp (as
+ *     with the matcher's kern); dm/plan.py's inflation_table is Nav2's curve.
+ *   Weighted move: entering cell c by a legal move costs b * (1 + pen[d2[c]]),
+ *     b = 5 orthogonal, 7 diagonal, so at most 1792.  Legality is as above, for
+ *     inflate_cells.
+ *   Weighted field: as the field above with that move cost; max_cost == 0 (or
+ *     any value above it) means DM_PLAN_COST_MAX, so a stored cost plus a move
+ *     never wraps and never equals DM_PLAN_UNREACHABLE.  With pen all zero it
+ *     is dm_plan_field's field bit for bit wherever both stay below their caps.
+ *   Path on a weighted field: the rule above with w = b * (1 + pen[d2[c]]). */
+#define DM_PLAN_COST_MAX 0xFFFFF7FFu
+
+/* The clearance: out[height*width] row-major.  A diagnostic and test entry,
+ * like dm_plan_traversable.  Does not touch the handle's field. */
+int dm_plan_clearance(dm_grid* g, int32_t clear_cells, uint16_t* out);
+/* dm_plan_field with the weighted move: arguments, out_stats and errors as
+ * there (DM_ERR_INCOMPLETE and DM_PLAN_MAX_ROUNDS included); clear_cells out
+ * of range or pen NULL: DM_ERR_INVALID_ARG; any error leaves the handle with
+ * no field.  The handle then holds a weighted field, and the penalty byte of
+ * every cell beside it on the device (allocated on the first such call):
+ * dm_plan_get_field and dm_plan_query read it like any field, dm_plan_path
+ * walks it by the weighted rule.  A later dm_plan_field, dm_assign_goals_path,
+ * _gain or _coord leaves an unweighted field as before. */
+int dm_plan_field_cost(dm_grid* g, const double* sources_xy, int32_t n_sources, int32_t inflate_cells,
+                       int32_t clear_cells, const uint8_t* pen, uint32_t max_cost, uint64_t* out_stats);
 /* dm_assign_goals scored by path length: over the same clusters, with the
  * same availability rule, errors, greedy order, ties and n_robots <= 256
  * limit.  For robot r the field is computed from r's cell alone (a robot
