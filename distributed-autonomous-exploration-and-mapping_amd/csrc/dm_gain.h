@@ -54,6 +54,15 @@ __global__ void k_gain_skip(const dm_cluster* __restrict__ recs, const uint32_t*
   skip[c] = (recs[c].size < min_size || cost[c] == DM_PLAN_UNREACHABLE) ? 1 : 0;
 }
 
+// The same for dm_assign_goals_team's R x K views: view r * K + c is cluster
+// c under robot r's field, cost[r * K + c].
+__global__ void k_gain_skip_team(const dm_cluster* __restrict__ recs, const uint32_t* __restrict__ cost, int64_t K,
+                                 int64_t n, int64_t min_size, uint8_t* __restrict__ skip) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n) return;
+  skip[v] = (recs[v % K].size < min_size || cost[v] == DM_PLAN_UNREACHABLE) ? 1 : 0;
+}
+
 // Words of a row of the claimed set (below): bit x & 31 of word
 // y * claimed_wpr(W) + (x >> 5) is cell (x, y).
 __host__ __device__ inline int32_t claimed_wpr(int32_t W) { return (W + 31) >> 5; }

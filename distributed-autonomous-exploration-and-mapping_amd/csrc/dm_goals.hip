@@ -20,6 +20,9 @@
 // kernels' launchers and entry points: dm_assign_goals_path, _gain and _coord
 // are one loop (assign_goals_field) over a robot's distance field, the snapped
 // cells of the cluster centroids, their gains and the same top-R lists.
+// dm_plan_team* and dm_assign_goals_team (dm_plan.h §4) compute all robots'
+// fields in the same rounds and pick the best (robot, cluster) pair first,
+// from the same top-R lists of one launch.
 #include <math.h>
 #include <string.h>
 
@@ -69,7 +72,7 @@ __device__ inline void goal_sort(unsigned long long* s_k, uint32_t* s_i) {
 // operations), and a cluster that is not reached is not eligible; `robots`
 // is not read.
 // kGain (dm_assign_goals_gain, with kPath): the numerator is the cluster's
-// visible-unknown count gain_row[c] in place of its size, and a cluster with
+// visible-unknown count gain_rows[r][c] in place of its size, and a cluster with
 // gain < min_gain is not eligible; a gain of 0 gives util 0, the key of "not
 // eligible".
 template <bool kPath, bool kGain>
@@ -79,7 +82,7 @@ __global__ __launch_bounds__(kGoalThreads) void k_goal_topk(const dm_cluster* __
                                                             unsigned long long* __restrict__ out_k,
                                                             uint32_t* __restrict__ out_i,
                                                             const uint32_t* __restrict__ cost_rows, double res,
-                                                            const uint32_t* __restrict__ gain_row,
+                                                            const uint32_t* __restrict__ gain_rows,
                                                             int64_t min_gain) {
   __shared__ unsigned long long s_k[kGoalN];
   __shared__ uint32_t s_i[kGoalN];
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(kGoalThreads) void k_goal_topk(const dm_cluster* __
         const double dx = q.cx_m - rx, dy = q.cy_m - ry;
         dist = __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
       }
-      const uint32_t gain = kGain ? gain_row[c] : 0u;
+      const uint32_t gain = kGain ? gain_rows[r * K + c] : 0u;
       if (reached && q.size >= min_size && dist >= min_dist && (!kGain || (int64_t)gain >= min_gain)) {
         const double num = kGain ? (double)gain : (double)q.size;
         const double util = __ddiv_rn(num, __dadd_rn(1.0, __dmul_rn(w, dist)));
@@ -167,7 +170,7 @@ static int dm_launch_goal_gather(dm_grid* g, const dm_cluster* d_recs, const int
 // Top-T lists of R robots over K label-sorted records; on return *d_k / *d_i
 // point at the final [R][T] lists (in g->goal_* workspace).  T <= 256.
 // d_cost: [R][K] path costs in place of the Euclidean distance (d_robots is
-// then not read), or nullptr.  d_gain (with d_cost, R == 1): [K] gains, the
+// then not read), or nullptr.  d_gain (with d_cost): [R][K] gains, the
 // numerator in place of the size, with min_gain; or nullptr.
 static int dm_launch_goal_topk(dm_grid* g, const dm_cluster* d_recs, int64_t K, const double* d_robots, int32_t R,
                                int32_t T, int64_t min_size, double w, double min_dist,
@@ -366,6 +369,124 @@ static int dm_plan_launch_path(dm_grid* g, const int64_t* d_start, int64_t cap) 
   return DM_OK;
 }
 
+// ---- team fields (dm_plan.h §4) -------------------------------------------------
+
+// device order of g->team_stat behind plan_stat's four words
+enum { TEAM_ST_PATH = 4, TEAM_ST_REACHED = 8, TEAM_ST_N = TEAM_ST_REACHED + DM_PLAN_TEAM_MAX };
+
+// The n fields from the source cells (host array) over g->team_trav, which
+// this computes for inflate_cells; synchronous.  stats: [3 + n] or nullptr.
+static int dm_plan_run_team(dm_grid* g, const int64_t* cells, int32_t n, int32_t inflate_cells, uint32_t max_cost,
+                            uint64_t* stats) {
+  using namespace dm_plan;
+  const int64_t ncell = g->W * g->H;
+  hipStream_t s = g->stream;
+  DM_HIP(hipMemsetAsync(g->team_stat, 0, sizeof(unsigned long long) * TEAM_ST_N, s));
+  KernelTimer t;
+  dm_timer_begin(g, "plan_team_travers", &t);
+  hipLaunchKernelGGL(k_plan_travers, dim3((unsigned)g->NT), dim3(kThreads), 0, s, g->state, g->tile_seen, g->W, g->H,
+                     g->TX, inflate_cells, g->team_trav, g->team_stat);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  DM_HIP(hipMemsetAsync(g->team_cost, 0xFF, sizeof(uint32_t) * (size_t)n * (size_t)ncell, s));
+  DM_HIP(hipMemsetAsync(g->team_stamp, 0, sizeof(uint32_t) * (size_t)n * (size_t)g->NT, s));
+  const unsigned int len3[3] = {(unsigned int)n, 0u, 0u};
+  DM_HIP(hipMemcpyAsync(g->team_len, len3, sizeof len3, hipMemcpyHostToDevice, s));
+  DM_HIP(hipMemcpyAsync(g->team_src, cells, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, s));
+  for (int i = 0; i < 4; ++i) g->h_team[i] = 0ull;
+  dm_timer_begin(g, "plan_team_seed", &t);
+  hipLaunchKernelGGL(k_plan_team_seed, dim3(1), dim3(DM_PLAN_TEAM_MAX), 0, s, g->team_src, n, g->W, g->TX, g->NT,
+                     ncell, g->team_cost, g->team_list[0]);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  // The round bound is dm_plan_run_field's with one source, per field: the
+  // fields settle side by side, so the team's rounds are the slowest field's.
+  const auto bound_of = [&](unsigned long long trav) { return (int64_t)(5 * (trav + 1ull) + 2); };
+  int64_t bound = g->plan_max_rounds > 0 ? g->plan_max_rounds : bound_of((unsigned long long)ncell);
+  // A visit holds 23.5 KB of LDS (6 workgroups in a CU's 160 KiB) and 4 waves
+  // of 112 VGPRs (4 waves per SIMD): registers bound it at 4 resident
+  // workgroups per CU, k_plan_relax's grid.  One field's list rarely fills
+  // that; with n fields the items of a round spread over all of it.
+  const unsigned grid =
+      (unsigned)std::min<int64_t>((int64_t)n * g->NT, 4 * (int64_t)(g->n_cu > 0 ? g->n_cu : 256));
+  int64_t done = 0;
+  int batch = 4;
+  bool empty = false;
+  while (!empty && done < bound) {
+    const int64_t nb = std::min<int64_t>(batch, bound - done);
+    dm_timer_begin(g, "plan_team_relax", &t);
+    for (int64_t k = 0; k < nb; ++k, ++done) {
+      hipLaunchKernelGGL(k_plan_relax_team, dim3(grid), dim3(kThreads), 0, s, g->team_cost, g->team_trav, g->team_src,
+                         g->W, g->H, g->TX, g->TY, max_cost, g->team_list[done & 1], g->team_list[(done + 1) & 1],
+                         g->team_len, g->team_stamp, (uint32_t)done, g->team_stat, g->h_team.dev());
+      DM_HIP(hipGetLastError());
+    }
+    dm_timer_end(g, &t);
+    DM_HIP(hipStreamSynchronize(s));
+    empty = g->h_team[HS_LEN] == 0ull;
+    if (g->plan_max_rounds <= 0) bound = std::min(bound, bound_of(g->h_team[HS_TRAV]));
+    batch = std::min(batch * 2, 32);
+  }
+  if (!empty) {  // the bound is reached: did the last round leave work?
+    unsigned int len[3];
+    DM_HIP(hipMemcpy(len, g->team_len, sizeof len, hipMemcpyDeviceToHost));
+    if (len[done % 3] != 0u)
+      return dm_set_error(DM_ERR_INCOMPLETE, "the team fields did not settle within %lld rounds (%u (field, tile) "
+                          "items still active)%s", (long long)bound, len[done % 3],
+                          g->plan_max_rounds > 0 ? "; DM_PLAN_MAX_ROUNDS is set" : "");
+  }
+  if (stats) {
+    dm_timer_begin(g, "plan_team_count", &t);
+    hipLaunchKernelGGL(k_plan_team_count,
+                       dim3((unsigned)std::min<int64_t>((ncell + kThreads - 1) / kThreads, 1024), (unsigned)n),
+                       dim3(kThreads), 0, s, g->team_cost, ncell, g->team_stat + TEAM_ST_REACHED);
+    DM_HIP(hipGetLastError());
+    dm_timer_end(g, &t);
+    unsigned long long st[TEAM_ST_N];
+    DM_HIP(hipMemcpyAsync(st, g->team_stat, sizeof st, hipMemcpyDeviceToHost, s));
+    DM_HIP(hipStreamSynchronize(s));
+    stats[0] = st[ST_TRAV];
+    stats[1] = st[ST_ROUNDS];
+    stats[2] = st[ST_RELAX];
+    for (int32_t k = 0; k < n; ++k) stats[3 + k] = st[TEAM_ST_REACHED + k];
+  }
+  return DM_OK;
+}
+
+// snap n targets (d_xy, `stride` doubles apart) to fields [r0, r0 + nr) of the team: [nr][n] into d_cost / d_cell
+static int dm_plan_launch_team_query(dm_grid* g, int32_t r0, int32_t nr, const double* d_xy, int64_t stride, int64_t n,
+                                     int32_t snap_cells, uint32_t* d_cost, int64_t* d_cell) {
+  if (n <= 0 || nr <= 0) return DM_OK;
+  KernelTimer t;
+  dm_timer_begin(g, "plan_team_query", &t);
+  hipLaunchKernelGGL(dm_plan::k_plan_team_query, dim3((unsigned)((n * nr + 127) / 128)), dim3(128), 0, g->stream,
+                     g->team_cost + (int64_t)r0 * g->W * g->H, nr, g->W, g->H, g->p.origin_x, g->p.origin_y,
+                     g->p.resolution, d_xy, stride, n, snap_cells, d_cost, d_cell);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  return DM_OK;
+}
+
+// walk back from *d_start on field `robot` into g->plan_path (cap entries):
+// k_plan_path<false> on the layer, over a copy of the team's bit rows that
+// holds this robot's source bit; length and error word go to g->team_stat[4], [5]
+static int dm_plan_launch_team_path(dm_grid* g, int32_t robot, const int64_t* d_start, int64_t cap) {
+  uint32_t* const layer = g->team_cost + (int64_t)robot * g->W * g->H;
+  DM_HIP(hipMemcpyAsync(g->team_travp, g->team_trav, sizeof(uint64_t) * (size_t)g->NT * DM_TILE,
+                        hipMemcpyDeviceToDevice, g->stream));
+  KernelTimer t;
+  dm_timer_begin(g, "plan_team_path", &t);
+  // the source's bit (and its cost 0 once more, which the layer holds already)
+  hipLaunchKernelGGL(dm_plan::k_plan_sources, dim3(1), dim3(64), 0, g->stream, g->team_src + robot, 1, g->W, g->TX,
+                     g->team_travp, layer);
+  DM_HIP(hipGetLastError());
+  hipLaunchKernelGGL(dm_plan::k_plan_path<false>, dim3(1), dim3(64), 0, g->stream, layer, g->team_travp, nullptr, g->W,
+                     g->H, g->TX, d_start, g->plan_path, cap, g->team_stat + TEAM_ST_PATH);
+  DM_HIP(hipGetLastError());
+  dm_timer_end(g, &t);
+  return DM_OK;
+}
+
 // ---- information gain (dm_gain.h) ---------------------------------------------
 
 // cells of n view points in g->gain_xy into g->gain_cell
@@ -382,6 +503,17 @@ static int dm_gain_launch_skip(dm_grid* g, const dm_cluster* d_recs, const uint3
   if (K <= 0) return DM_OK;
   hipLaunchKernelGGL(dm_gain::k_gain_skip, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, g->stream, d_recs, d_cost,
                      K, min_size, g->gain_skip);
+  DM_HIP(hipGetLastError());
+  return DM_OK;
+}
+
+// the same for R robots' rows of costs d_cost[R][K]: R * K flags into g->gain_skip
+static int dm_gain_launch_skip_team(dm_grid* g, const dm_cluster* d_recs, const uint32_t* d_cost, int64_t K, int32_t R,
+                                    int64_t min_size) {
+  const int64_t n = K * R;
+  if (n <= 0) return DM_OK;
+  hipLaunchKernelGGL(dm_gain::k_gain_skip_team, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g->stream, d_recs,
+                     d_cost, K, n, min_size, g->gain_skip);
   DM_HIP(hipGetLastError());
   return DM_OK;
 }
@@ -677,6 +809,149 @@ int dm_plan_path(dm_grid* g, double tx, double ty, int32_t snap_cells, int64_t* 
   DM_HIP(hipStreamSynchronize(g->stream));
   if (st[1])
     return dm_set_error(DM_ERR_INCOMPLETE, "dm_plan_path: the walk found no predecessor after %llu cells (the "
+                        "field is not a fixpoint)", st[0]);
+  const int64_t n = (int64_t)st[0];
+  *n_out = n;
+  if (n > cap)
+    return dm_set_error(DM_ERR_CAPACITY, "the path has %lld cells, cap is %lld", (long long)n, (long long)cap);
+  if (n > 0) {
+    std::vector<int64_t> rev((size_t)n);
+    DM_HIP(hipMemcpy(rev.data(), g->plan_path, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) out_cells[i] = rev[(size_t)(n - 1 - i)];  // source first
+  }
+  return DM_OK;
+}
+
+// ---- team fields: one field per robot, relaxed together (dm_plan.h §4) ----------
+
+// Everything the team needs for n robots; the arrays sized by n grow, the
+// others are allocated once (team_stat last).
+static int ensure_team(dm_grid* g, int32_t n) {
+  int rc = DM_OK;
+  if (!g->team_stat) {
+    if (!g->h_team && (rc = g->h_team.alloc_zeroed(16, hipHostMallocMapped | hipHostMallocCoherent, "team rounds")))
+      return rc;
+    const int64_t rows = g->NT * DM_TILE;
+    if ((rc = g->team_trav.alloc(rows, "team traversable bit rows"))) return rc;
+    if ((rc = g->team_travp.alloc(rows, "team traversable bit rows with a source"))) return rc;
+    if ((rc = g->team_src.alloc(DM_PLAN_TEAM_MAX, "team sources"))) return rc;
+    if ((rc = g->team_len.alloc(4, "team list lengths"))) return rc;
+    if ((rc = g->team_stat.alloc_zeroed(TEAM_ST_N, "team statistics"))) return rc;
+  }
+  const int64_t items = (int64_t)n * g->NT;
+  if ((rc = g->team_list[0].ensure(items, "team item list")) || (rc = g->team_list[1].ensure(items, "team item list")) ||
+      (rc = g->team_stamp.ensure(items, "team item stamps")))
+    return rc;
+  return g->team_cost.ensure((int64_t)n * g->W * g->H, "team distance fields");
+}
+
+static int plan_need_team(const dm_grid* g, const char* what) {
+  if (!g->team_cost || !g->team_valid)
+    return dm_set_error(DM_ERR_STATE, "%s: no team fields (call dm_plan_team first)", what);
+  if (g->team_version != dm_map_version(g))
+    return dm_set_error(DM_ERR_STATE, "%s: the map changed since the team fields were computed (call dm_plan_team "
+                        "again)", what);
+  return DM_OK;
+}
+
+static int plan_check_team_robot(const dm_grid* g, int32_t robot) {
+  if (robot < 0 || robot >= g->team_n)
+    return dm_set_error(DM_ERR_INVALID_ARG, "robot must be in [0, %d) (got %d)", g->team_n, robot);
+  return DM_OK;
+}
+
+// The team fields of n robots (metres), after the argument checks of the
+// entry point; leaves them in the handle.  stats: [3 + n] or nullptr.
+static int plan_team_from(dm_grid* g, const double* robots_xy, int32_t n, int32_t inflate_cells, uint32_t max_cost,
+                          uint64_t* stats) {
+  int64_t cells[DM_PLAN_TEAM_MAX];
+  for (int32_t k = 0; k < n; ++k)
+    if (!plan_cell_of(g, robots_xy[2 * k], robots_xy[2 * k + 1], &cells[k]))
+      return dm_set_error(DM_ERR_INVALID_ARG, "robot %d (%g, %g) is outside the grid", k, robots_xy[2 * k],
+                          robots_xy[2 * k + 1]);
+  if ((int64_t)n * g->NT >= (1ll << 31))
+    return dm_set_error(DM_ERR_CAPACITY, "n_robots * tiles = %lld does not fit the int32 work items",
+                        (long long)((int64_t)n * g->NT));
+  if (max_cost == 0u || max_cost > 0xFFFFFFEFu) max_cost = 0xFFFFFFEFu;
+  g->team_valid = false;
+  int rc = ensure_team(g, n);
+  if (rc) return rc;
+  DM_HIP(dm_join_pass_stream(g));
+  if ((rc = dm_plan_run_team(g, cells, n, inflate_cells, max_cost, stats))) return rc;
+  g->team_n = n;
+  g->team_valid = true;
+  g->team_version = dm_map_version(g);
+  return DM_OK;
+}
+
+int dm_plan_team(dm_grid* g, const double* robots_xy, int32_t n_robots, int32_t inflate_cells, uint32_t max_cost,
+                 uint64_t* out_stats) {
+  int rc = dm_check_whole_map(g, "dm_plan_team");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n_robots < 1 || n_robots > DM_PLAN_TEAM_MAX)
+    return dm_set_error(DM_ERR_INVALID_ARG, "n_robots must be in [1, %d] (got %d)", DM_PLAN_TEAM_MAX, n_robots);
+  if (!robots_xy) return dm_set_error(DM_ERR_INVALID_ARG, "robots_xy is NULL");
+  if ((rc = plan_check_inflate(inflate_cells))) return rc;
+  return plan_team_from(g, robots_xy, n_robots, inflate_cells, max_cost, out_stats);
+}
+
+int dm_plan_team_get_field(dm_grid* g, int32_t robot, uint32_t* out) {
+  int rc = dm_check_whole_map(g, "dm_plan_team_get_field");
+  if (rc || (rc = use_device(g))) return rc;
+  if (!out) return dm_set_error(DM_ERR_INVALID_ARG, "out is NULL");
+  if ((rc = plan_need_team(g, "dm_plan_team_get_field")) || (rc = plan_check_team_robot(g, robot))) return rc;
+  const int64_t ncell = g->W * g->H;
+  DM_HIP(hipMemcpyAsync(out, g->team_cost + (int64_t)robot * ncell, sizeof(uint32_t) * (size_t)ncell,
+                        hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  return DM_OK;
+}
+
+int dm_plan_team_query(dm_grid* g, const double* targets_xy, int64_t n, int32_t snap_cells, uint32_t* out_cost,
+                       int64_t* out_cell) {
+  int rc = dm_check_whole_map(g, "dm_plan_team_query");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n < 0) return dm_set_error(DM_ERR_INVALID_ARG, "n must be >= 0");
+  if (n > 0 && (!targets_xy || !out_cost || !out_cell))
+    return dm_set_error(DM_ERR_INVALID_ARG, "targets_xy / out_cost / out_cell is NULL");
+  if ((rc = plan_check_snap(snap_cells)) || (rc = plan_need_team(g, "dm_plan_team_query"))) return rc;
+  if (n == 0) return DM_OK;
+  const int64_t total = n * g->team_n;
+  if ((rc = grow_plan_query(g, n)) || (rc = g->team_qcost.ensure(total, "team query costs")) ||
+      (rc = g->team_qcell.ensure(total, "team query cells")))
+    return rc;
+  DM_HIP(hipMemcpyAsync(g->plan_qxy, targets_xy, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, g->stream));
+  if ((rc = dm_plan_launch_team_query(g, 0, g->team_n, g->plan_qxy, 2, n, snap_cells, g->team_qcost, g->team_qcell)))
+    return rc;
+  DM_HIP(hipMemcpyAsync(out_cost, g->team_qcost, sizeof(uint32_t) * (size_t)total, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipMemcpyAsync(out_cell, g->team_qcell, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  return DM_OK;
+}
+
+int dm_plan_team_path(dm_grid* g, int32_t robot, double tx, double ty, int32_t snap_cells, int64_t* out_cells,
+                      int64_t cap, int64_t* n_out) {
+  int rc = dm_check_whole_map(g, "dm_plan_team_path");
+  if (rc || (rc = use_device(g))) return rc;
+  if (!n_out) return dm_set_error(DM_ERR_INVALID_ARG, "n_out is NULL");
+  *n_out = 0;
+  if (cap < 0 || (cap > 0 && !out_cells)) return dm_set_error(DM_ERR_INVALID_ARG, "cap < 0 or out_cells is NULL");
+  if ((rc = plan_check_snap(snap_cells)) || (rc = plan_need_team(g, "dm_plan_team_path")) ||
+      (rc = plan_check_team_robot(g, robot)))
+    return rc;
+  if ((rc = grow_plan_query(g, 1))) return rc;
+  const int64_t dcap = std::max<int64_t>(1, std::min<int64_t>(cap, g->W * g->H));
+  if ((rc = g->plan_path.ensure(dcap, "path cells"))) return rc;
+  const double txy[2] = {tx, ty};
+  DM_HIP(hipMemcpyAsync(g->plan_qxy, txy, sizeof txy, hipMemcpyHostToDevice, g->stream));
+  if ((rc = dm_plan_launch_team_query(g, robot, 1, g->plan_qxy, 2, 1, snap_cells, g->plan_qcost, g->plan_qcell)))
+    return rc;
+  if ((rc = dm_plan_launch_team_path(g, robot, g->plan_qcell, std::min(cap, dcap)))) return rc;
+  unsigned long long st[2] = {0ull, 0ull};
+  DM_HIP(hipMemcpyAsync(st, g->team_stat + TEAM_ST_PATH, sizeof st, hipMemcpyDeviceToHost, g->stream));
+  DM_HIP(hipStreamSynchronize(g->stream));
+  if (st[1])
+    return dm_set_error(DM_ERR_INCOMPLETE, "dm_plan_team_path: the walk found no predecessor after %llu cells (the "
                         "field is not a fixpoint)", st[0]);
   const int64_t n = (int64_t)st[0];
   *n_out = n;
@@ -1028,6 +1303,110 @@ int dm_assign_goals_coord(dm_grid* g, const double* robots_xy, int32_t n_robots,
   const GoalScoring sc = {"dm_assign_goals_coord", GoalScoring::kMarginal, min_gain, radius_cells, held_xy, n_held};
   return assign_goals_field(g, sc, robots_xy, n_robots, min_size, distance_weight, min_distance, inflate_cells,
                             max_cost, snap_cells, out_index, out_xy, out_cell, out_gain);
+}
+
+// The global-greedy assignment over R best-first lists of T entries (key 0:
+// no eligible cluster left): among the pairs (r, c) with r unassigned and c
+// untaken take the greatest key, ties to the smaller record index (the
+// smaller label), then the smaller r; until no pair is left.  A robot's goal
+// is among its R best eligible clusters, since the others take at most R - 1.
+static void team_pick(const unsigned long long* hk, const uint32_t* hi, int32_t R, int32_t T,
+                      std::vector<int64_t>& idx) {
+  std::vector<int32_t> pos((size_t)R, 0);  // the first entry of r's list that may still be free
+  for (;;) {
+    int32_t br = -1;
+    unsigned long long bk = 0ull;
+    uint32_t bi = 0u;
+    for (int32_t r = 0; r < R; ++r) {
+      if (idx[(size_t)r] >= 0) continue;
+      int32_t& t = pos[(size_t)r];
+      while (t < T && hk[(size_t)r * T + t] != 0ull &&
+             std::find(idx.begin(), idx.end(), (int64_t)hi[(size_t)r * T + t]) != idx.end())
+        ++t;
+      if (t >= T || hk[(size_t)r * T + t] == 0ull) continue;
+      const unsigned long long k = hk[(size_t)r * T + t];
+      const uint32_t i = hi[(size_t)r * T + t];
+      if (br < 0 || k > bk || (k == bk && i < bi)) {  // equal (k, i): the smaller r stays
+        br = r;
+        bk = k;
+        bi = i;
+      }
+    }
+    if (br < 0) return;
+    idx[(size_t)br] = (int64_t)bi;
+  }
+}
+
+int dm_assign_goals_team(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size, int64_t min_gain,
+                         double distance_weight, double min_distance, int32_t inflate_cells, uint32_t max_cost,
+                         int32_t snap_cells, int32_t radius_cells, int64_t* out_index, double* out_xy,
+                         int64_t* out_cell, uint32_t* out_gain) {
+  const bool gain = radius_cells != 0;
+  int rc = dm_check_whole_map(g, "dm_assign_goals_team");
+  if (rc || (rc = use_device(g))) return rc;
+  if (n_robots > DM_PLAN_TEAM_MAX)
+    return dm_set_error(DM_ERR_INVALID_ARG, "n_robots must be in [0, %d] (got %d)", DM_PLAN_TEAM_MAX, n_robots);
+  if ((rc = check_goal_args(n_robots, !robots_xy || !out_index || !out_xy || !out_cell || (gain && !out_gain),
+                            gain ? "robots_xy / out_index / out_xy / out_cell / out_gain"
+                                 : "robots_xy / out_index / out_xy / out_cell",
+                            distance_weight, min_distance)))
+    return rc;
+  if (gain && min_gain < 0)
+    return dm_set_error(DM_ERR_INVALID_ARG, "min_gain must be >= 0 (got %lld)", (long long)min_gain);
+  if ((rc = plan_check_inflate(inflate_cells)) || (rc = plan_check_snap(snap_cells)) ||
+      (gain && (rc = gain_check_radius(radius_cells))))
+    return rc;
+  const dm_cluster* recs = nullptr;
+  int64_t K = 0;
+  if ((rc = goal_source(g, &recs, &K))) return rc;
+  if (n_robots == 0) return DM_OK;
+  const int32_t R = n_robots, T = n_robots;
+  const int64_t total = (int64_t)R * K;
+  // every robot's field, then the whole R x K matrix of snapped centroids, the
+  // gains of its cells and every robot's top R: one launch each
+  if ((rc = plan_team_from(g, robots_xy, R, inflate_cells, max_cost, nullptr))) return rc;
+  std::vector<int64_t> idx((size_t)R, -1);
+  for (int32_t r = 0; r < R; ++r) {
+    out_cell[r] = -1;
+    if (gain) out_gain[r] = 0u;
+    out_xy[2 * r] = out_xy[2 * r + 1] = NAN;
+  }
+  if (K > 0) {
+    if ((rc = g->team_qcost.ensure(total, "team query costs")) || (rc = g->team_qcell.ensure(total, "team query cells")))
+      return rc;
+    if (gain && (rc = grow_gain(g, total))) return rc;
+    if ((rc = dm_plan_launch_team_query(g, 0, R, &recs[0].cx_m, (int64_t)(sizeof(dm_cluster) / sizeof(double)), K,
+                                        snap_cells, g->team_qcost, g->team_qcell)))
+      return rc;
+    if (gain) {
+      if ((rc = dm_gain_launch_skip_team(g, recs, g->team_qcost, K, R, min_size))) return rc;
+      if ((rc = dm_gain_launch_views(g, g->team_qcell, g->gain_skip, total, radius_cells, false))) return rc;
+    }
+    const unsigned long long* dk = nullptr;
+    const uint32_t* di = nullptr;
+    if ((rc = dm_launch_goal_topk(g, recs, K, nullptr, R, T, min_size, distance_weight, min_distance, &dk, &di,
+                                  g->team_qcost, gain ? g->gain_out.get() : nullptr, gain ? min_gain : 0)))
+      return rc;
+    std::vector<unsigned long long> hk((size_t)R * T);
+    std::vector<uint32_t> hi((size_t)R * T);
+    DM_HIP(hipMemcpyAsync(hk.data(), dk, sizeof(unsigned long long) * hk.size(), hipMemcpyDeviceToHost, g->stream));
+    DM_HIP(hipMemcpyAsync(hi.data(), di, sizeof(uint32_t) * hi.size(), hipMemcpyDeviceToHost, g->stream));
+    DM_HIP(hipStreamSynchronize(g->stream));
+    team_pick(hk.data(), hi.data(), R, T, idx);
+    for (int32_t r = 0; r < R; ++r) {
+      const int64_t c = idx[(size_t)r];
+      if (c < 0) continue;
+      const int64_t at = (int64_t)r * K + c;
+      DM_HIP(hipMemcpyAsync(&out_cell[r], g->team_qcell + at, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+      if (gain)
+        DM_HIP(hipMemcpyAsync(&out_gain[r], g->gain_out + at, sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream));
+    }
+    DM_HIP(hipStreamSynchronize(g->stream));
+    for (int32_t r = 0; r < R; ++r)
+      if (idx[(size_t)r] >= 0) cell_centre(g, out_cell[r], out_xy + 2 * r);  // a reachable goal, not the centroid
+  }
+  memcpy(out_index, idx.data(), sizeof(int64_t) * (size_t)R);
+  return DM_OK;
 }
 
 }  // extern "C"

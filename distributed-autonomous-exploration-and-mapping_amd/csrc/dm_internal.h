@@ -541,6 +541,24 @@ struct dm_grid {
   // DM_PLAN_MAX_ROUNDS (read at dm_create; the test of DM_ERR_INCOMPLETE):
   // overrides the relaxation's round bound; 0: the derived bound
   int64_t plan_max_rounds = 0;
+  // team fields (dm_plan_team, dm_assign_goals_team; dm_plan.h §4), beside the
+  // single field and independent of it; allocated on first use, the arrays
+  // sized by the number of robots grown when a later call brings more
+  DevBuf<uint32_t> team_cost;      // [team_n][H][W]
+  DevBuf<uint64_t> team_trav;      // [NT][64] the team's traversable bit rows, no source in them
+  DevBuf<uint64_t> team_travp;     // [NT][64] dm_plan_team_path: the same with one robot's source bit
+  DevBuf<int64_t> team_src;        // [DM_PLAN_TEAM_MAX] source cell of field k
+  DevBuf<int32_t> team_list[2];    // [n * NT] active (field, tile) items of even / odd rounds
+  DevBuf<uint32_t> team_stamp;     // [n][NT]
+  DevBuf<unsigned int> team_len;   // [3] list lengths
+  // [0..3] as plan_stat (0 unused), [4..5] path length, error, [8 + k] reached cells of field k
+  DevBuf<unsigned long long> team_stat;
+  HostBuf<unsigned long long> h_team;  // mapped, as h_plan
+  DevBuf<uint32_t> team_qcost;     // [team_n][n] dm_plan_team_query's matrix
+  DevBuf<int64_t> team_qcell;
+  int32_t team_n = 0;              // fields held
+  bool team_valid = false;
+  uint64_t team_version = 0;
 
   // scan matcher (dm_match.h; dm_match_field and dm_match_scans), allocated
   // on first use.  match_V is the response field of (match_r, match_kern_h)

@@ -623,4 +623,221 @@ __global__ __launch_bounds__(64) void k_plan_path(const uint32_t* __restrict__ c
   }
 }
 
+// ---- 4. team fields (dm_plan_team) -----------------------------
+// K single-source fields cost[field][H][W] relaxed in the same rounds.  Field
+// k is k_plan_relax's field from src[k] alone; the fields are independent, so
+// a work item is one (field, tile), listed as field * NT + tile, and one launch
+// is one round of all of them.  The lists, the three rotating length words,
+// the stamps ([K][NT]) and the host words are k_plan_relax's; so is the
+// argument that no atomics are needed, per field: one workgroup owns a
+// (field, tile) in a round, values only fall, every stored value is the cost
+// of a real path of that field.
+//
+// All fields read one copy of the traversable bit rows, without any source in
+// it: a field's source cell is traversable in that field only, so its bit is
+// ORed into the row words as they are loaded into LDS (the centre word or a
+// ring word, wherever the source's row and tile column are among the 66 x 3
+// loaded), before the per-cell flags, the ring costs and the row scan's gaps
+// are derived from them.  The bit rows in memory are never written.
+//
+// This is the third copy of the sweep (k_plan_relax, k_plan_relax_w): the two
+// others are left as they are so that the single fields keep their code.
+
+// Thread = field: cost 0 at its source, and (field, source tile) on round 0's list.
+__global__ void k_plan_team_seed(const int64_t* __restrict__ src, int32_t n, int64_t W, int64_t TX, int64_t NT,
+                                 int64_t ncell, uint32_t* __restrict__ cost, int32_t* __restrict__ list) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int64_t c = src[k], x = c % W, y = c / W;
+  cost[(int64_t)k * ncell + c] = 0u;
+  list[k] = (int32_t)((int64_t)k * NT + (y >> 6) * TX + (x >> 6));
+}
+
+__global__ __launch_bounds__(kThreads) void k_plan_relax_team(uint32_t* __restrict__ cost_all,
+                                                              const uint64_t* __restrict__ travs,
+                                                              const int64_t* __restrict__ src, int64_t W,
+                                                              int64_t H, int64_t TX, int64_t TY, uint32_t max_cost,
+                                                              const int32_t* __restrict__ list_in,
+                                                              int32_t* __restrict__ list_out, unsigned int* len,
+                                                              uint32_t* __restrict__ stamp, uint32_t round,
+                                                              unsigned long long* __restrict__ stat,
+                                                              volatile unsigned long long* hstat) {
+  __shared__ uint32_t s_c[kRing][kRing];
+  __shared__ unsigned long long s_tw[kRing][3];
+  __shared__ uint8_t s_t[kRing][kRing + 2];
+  __shared__ int s_flags;
+  const unsigned int n_in = len[round % 3u];
+  unsigned int* const len_out = &len[(round + 1u) % 3u];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    len[(round + 2u) % 3u] = 0u;
+    hstat[HS_LEN] = n_in;
+    if (n_in) {
+      const unsigned long long relax = stat[ST_RELAX] + n_in;
+      stat[ST_ROUNDS] = round + 1u;
+      stat[ST_RELAX] = relax;
+      hstat[HS_ROUNDS] = round + 1u;
+      hstat[HS_RELAX] = relax;
+      hstat[HS_TRAV] = stat[ST_TRAV];
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t NT = TX * TY;
+  for (unsigned int item = blockIdx.x; item < n_in; item += gridDim.x) {
+    const int64_t it = list_in[item], field = it / NT, tile = it % NT, tx = tile % TX, ty = tile / TX;
+    const int64_t x0 = tx * DM_TILE, y0 = ty * DM_TILE;
+    uint32_t* const cost = cost_all + field * (W * H);
+    const int64_t sc = src[field], sy = sc / W, stx = (sc % W) >> 6;
+    const unsigned long long sbit = 1ull << ((sc % W) & 63);
+    if (threadIdx.x == 0) s_flags = 0;
+    // traversable words of the ring rows: left neighbour, tile, right neighbour,
+    // with this field's source bit where its row and tile column are loaded
+    for (int j = threadIdx.x; j < kRing * 3; j += kThreads) {
+      const int row = j / 3, wc = j % 3;
+      const int64_t gy = y0 - 1 + row, ntx = tx + wc - 1;
+      unsigned long long w = 0ull;
+      if (gy >= 0 && gy < H && ntx >= 0 && ntx < TX) w = travs[((gy >> 6) * TX + ntx) * DM_TILE + (gy & 63)];
+      if (gy == sy && ntx == stx) w |= sbit;  // the source is in the grid
+      s_tw[row][wc] = w;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < kRing * kRing; j += kThreads) {
+      const int row = j / kRing, col = j % kRing;
+      const int wc = col == 0 ? 0 : (col == kRing - 1 ? 2 : 1);
+      const int bit = col == 0 ? 63 : (col == kRing - 1 ? 0 : col - 1);
+      const int t = (int)((s_tw[row][wc] >> bit) & 1ull);
+      // traversable bits are set for in-grid cells only; the others hold no cost
+      s_t[row][col] = (uint8_t)t;
+      s_c[row][col] = t ? cost[(y0 - 1 + row) * W + (x0 - 1 + col)] : kUnreach;
+    }
+    __syncthreads();
+    uint32_t init[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) init[i] = s_c[wave * 16 + i + 1][lane + 1];
+    bool converged = false;
+    for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
+      int ch = 0;
+      for (int ii = 0; ii < 16; ++ii) {  // wave-uniform: the row scans below shuffle across all lanes
+        const int i = (sweep & 1) ? 15 - ii : ii;
+        const int rr = wave * 16 + i + 1, cc = lane + 1;
+        const int t = s_t[rr][cc];
+        const uint32_t cur = s_c[rr][cc];  // kUnreach > max_cost where the cell is not traversable
+        uint32_t best = cur;
+        if (t) {
+          const uint32_t cn = s_c[rr - 1][cc], cs = s_c[rr + 1][cc], cw = s_c[rr][cc - 1], ce = s_c[rr][cc + 1];
+          if (cn <= max_cost) best = min(best, cn + 5u);
+          if (cs <= max_cost) best = min(best, cs + 5u);
+          if (cw <= max_cost) best = min(best, cw + 5u);
+          if (ce <= max_cost) best = min(best, ce + 5u);
+          const int tn = s_t[rr - 1][cc], ts = s_t[rr + 1][cc], tw = s_t[rr][cc - 1], te = s_t[rr][cc + 1];
+          if (tn && tw) { const uint32_t v = s_c[rr - 1][cc - 1]; if (v <= max_cost) best = min(best, v + 7u); }
+          if (tn && te) { const uint32_t v = s_c[rr - 1][cc + 1]; if (v <= max_cost) best = min(best, v + 7u); }
+          if (ts && tw) { const uint32_t v = s_c[rr + 1][cc - 1]; if (v <= max_cost) best = min(best, v + 7u); }
+          if (ts && te) { const uint32_t v = s_c[rr + 1][cc + 1]; if (v <= max_cost) best = min(best, v + 7u); }
+          if (best > max_cost) best = cur;
+        }
+        // the row scan of k_plan_relax, over the words that hold the source bit
+        const unsigned long long gaps = ~s_tw[rr][1];
+        const unsigned long long gl = gaps & ((2ull << lane) - 1ull), gr = gaps >> lane;
+        const int run_l = gl ? lane - (63 - __clzll((long long)gl)) : lane + 1;
+        const int run_r = gr ? __ffsll((long long)gr) - 1 : 64 - lane;
+#pragma unroll
+        for (int d = 1; d < DM_TILE; d <<= 1) {
+          const uint32_t o = (uint32_t)__shfl_up((int)best, d);
+          if (run_l > d && o <= max_cost && 5u * d <= max_cost - o) best = min(best, o + 5u * d);
+        }
+#pragma unroll
+        for (int d = 1; d < DM_TILE; d <<= 1) {
+          const uint32_t o = (uint32_t)__shfl_down((int)best, d);
+          if (run_r > d && o <= max_cost && 5u * d <= max_cost - o) best = min(best, o + 5u * d);
+        }
+        if (best < cur) {
+          s_c[rr][cc] = best;
+          ch = 1;
+        }
+      }
+      if (!__syncthreads_or(ch)) {
+        converged = true;
+        break;
+      }
+    }
+    int flags = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = wave * 16 + i, col = lane;
+      const uint32_t v = s_c[row + 1][col + 1];
+      // v != init only where the cell is traversable, and those are in the grid
+      if (v != init[i]) cost[(y0 + row) * W + (x0 + col)] = v;
+      // round 0 publishes the source itself: nobody has seen its zero
+      if (v != (round == 0u ? kUnreach : init[i])) {
+        const int n = row == 0, s = row == DM_TILE - 1, w = col == 0, e = col == DM_TILE - 1;
+        flags |= (n << 1) | (s << 7) | (w << 3) | (e << 5) | ((n & w) << 0) | ((n & e) << 2) | ((s & w) << 6) |
+                 ((s & e) << 8);
+      }
+    }
+    if (!converged) flags |= 1 << 4;  // stopped at the sweep bound: this item again
+    if (flags) atomicOr(&s_flags, flags);
+    __syncthreads();
+    if (threadIdx.x < 9 && ((s_flags >> threadIdx.x) & 1)) {
+      const int64_t ntx = tx + (int)(threadIdx.x % 3) - 1, nty = ty + (int)(threadIdx.x / 3) - 1;
+      if (ntx >= 0 && ntx < TX && nty >= 0 && nty < TY) {
+        const int64_t nt = field * NT + nty * TX + ntx;  // < 2^31: dm_plan_team checks n_robots * NT
+        if (atomicExch(&stamp[nt], round + 2u) != round + 2u) list_out[atomicAdd(len_out, 1u)] = (int32_t)nt;
+      }
+    }
+    __syncthreads();  // s_flags / LDS reuse by the next item
+  }
+}
+
+// Reached cells per field: blockIdx.y = field, into reached[field].
+__global__ __launch_bounds__(kThreads) void k_plan_team_count(const uint32_t* __restrict__ cost, int64_t ncell,
+                                                              unsigned long long* __restrict__ reached) {
+  __shared__ int s_n;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const uint32_t* const layer = cost + (int64_t)blockIdx.y * ncell;
+  int c = 0;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < ncell; i += (int64_t)gridDim.x * kThreads)
+    c += layer[i] != kUnreach;
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_n, c);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_n) atomicAdd(&reached[blockIdx.y], (unsigned long long)s_n);
+}
+
+// k_plan_query's snap, thread = (robot, target): out[robot * n + target] under
+// field `robot` of cost[n_robots][H][W].
+__global__ void k_plan_team_query(const uint32_t* __restrict__ cost, int32_t n_robots, int64_t W, int64_t H,
+                                  double ox, double oy, double res, const double* __restrict__ xy, int64_t stride,
+                                  int64_t n, int32_t s, uint32_t* __restrict__ out_cost,
+                                  int64_t* __restrict__ out_cell) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * n_robots) return;
+  const int64_t r = i / n, tg = i % n;
+  const uint32_t* const layer = cost + r * (W * H);
+  const double fx = floor((xy[tg * stride] - ox) / res), fy = floor((xy[tg * stride + 1] - oy) / res);
+  uint32_t bc = kUnreach;
+  int64_t bcell = -1;
+  if (fx >= 0.0 && fx < (double)W && fy >= 0.0 && fy < (double)H) {  // NaN: out of grid
+    const int64_t cx = (int64_t)fx, cy = (int64_t)fy;
+    int bd = 0x7FFFFFFF;
+    for (int dy = -s; dy <= s; ++dy) {  // rows, then columns: ascending linear index
+      const int64_t y = cy + dy;
+      if (y < 0 || y >= H) continue;
+      for (int dx = -s; dx <= s; ++dx) {
+        const int64_t x = cx + dx;
+        if (x < 0 || x >= W) continue;
+        const int d = dx * dx + dy * dy;
+        if (d >= bd) continue;
+        const uint32_t c = layer[y * W + x];
+        if (c == kUnreach) continue;
+        bd = d;
+        bc = c;
+        bcell = y * W + x;
+      }
+    }
+  }
+  out_cost[i] = bc;
+  out_cell[i] = bcell;
+}
+
 }  // namespace dm_plan

@@ -27,6 +27,7 @@ DM_ERR_PIPELINE = -9
 DM_ERR_COLLECTIVE = -10
 DM_TILE = 64
 DM_PLAN_UNREACHABLE = 0xFFFFFFFF
+DM_PLAN_TEAM_MAX = 64
 
 _ERR_NAMES = {
     DM_ERR_INVALID_ARG: "DM_ERR_INVALID_ARG",
@@ -207,6 +208,12 @@ SIGNATURES = {
     "dm_assign_goals_coord": [_vp, _vp, _i32, _vp, _i32, _i64, _i64, ctypes.c_double, ctypes.c_double, _i32,
                               ctypes.c_uint32, _i32, _i32, _vp, _vp, _vp, _vp],
     "dm_gain_claimed": [_vp, _vp],
+    "dm_plan_team": [_vp, _vp, _i32, _i32, ctypes.c_uint32, _vp],
+    "dm_plan_team_get_field": [_vp, _i32, _vp],
+    "dm_plan_team_query": [_vp, _vp, _i64, _i32, _vp, _vp],
+    "dm_plan_team_path": [_vp, _i32, ctypes.c_double, ctypes.c_double, _i32, _vp, _i64, ctypes.POINTER(_i64)],
+    "dm_assign_goals_team": [_vp, _vp, _i32, _i64, _i64, ctypes.c_double, ctypes.c_double, _i32, ctypes.c_uint32,
+                             _i32, _i32, _vp, _vp, _vp, _vp],
     "dm_match_field": [_vp, _i32, _vp, _vp],
     "dm_match_scans": [_vp, _i32, _vp, _i32, _vp, _f32, _f32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp,
                        _vp, _vp, _vp, _vp, _vp],

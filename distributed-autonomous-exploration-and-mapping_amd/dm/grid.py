@@ -101,6 +101,7 @@ class OccupancyMapper:
         self.row0 = int(out.band_row0)
         self._cap = 1 << 12  # cluster records per frontiers() buffer (grown on demand)
         self.last_incomplete = None  # dm_last_error() of the last pass that returned no result
+        self._team_n = 0  # fields of the last plan_team / assign_goals_team: the rows of plan_team_query's matrix
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
@@ -489,6 +490,78 @@ class OccupancyMapper:
         with self._lock:
             check(self._lib.dm_gain_claimed(self._handle(), _vp(out)))
         return out.astype(bool)
+
+    # -- team planning (csrc/dm_plan.h §4; host restatement: dm/plan.py) ----
+    def plan_team(self, robots_xy, inflate_cells: int = 2, max_cost: int = 0) -> dict:
+        """One distance field per robot (metres), relaxed together on the
+        device (dm_plan_team): field k is plan_field([robots_xy[k]]) bit for
+        bit.  The fields stay in the handle beside plan_field's, for
+        plan_team_field / plan_team_query / plan_team_path, until the map
+        changes.  Returns {"traversable", "rounds", "tile_relaxations",
+        "reached": [per robot]}."""
+        xy = np.ascontiguousarray(np.asarray(robots_xy, np.float64).reshape(-1, 2))
+        n = xy.shape[0]
+        st = (ctypes.c_uint64 * (3 + max(n, 1)))()
+        with self._lock:
+            check(self._lib.dm_plan_team(self._handle(), _vp(xy), n, int(inflate_cells), int(max_cost), st))
+            self._team_n = n
+        return {"traversable": int(st[0]), "rounds": int(st[1]), "tile_relaxations": int(st[2]),
+                "reached": [int(st[3 + k]) for k in range(n)]}
+
+    def plan_team_field(self, k: int) -> np.ndarray:
+        """Robot k's field of the last plan_team (dm_plan_team_get_field):
+        uint32 [rows, W], as plan_cost_field."""
+        out = np.empty((self.rows, self.width), np.uint32)
+        with self._lock:
+            check(self._lib.dm_plan_team_get_field(self._handle(), int(k), _vp(out)))
+        return out
+
+    def plan_team_query(self, targets_xy, snap_cells: int = 5):
+        """The robot x target matrix (dm_plan_team_query): (cost uint32
+        [n_robots, n], cell int64 [n_robots, n]), plan_query's snap of every
+        target under every robot's field."""
+        xy = np.ascontiguousarray(np.asarray(targets_xy, np.float64).reshape(-1, 2))
+        n = xy.shape[0]
+        # the library knows how many fields it holds; its limit bounds the buffers
+        cost = np.empty((_ffi.DM_PLAN_TEAM_MAX, n), np.uint32)
+        cell = np.empty((_ffi.DM_PLAN_TEAM_MAX, n), np.int64)
+        with self._lock:
+            check(self._lib.dm_plan_team_query(self._handle(), _vp(xy), n, int(snap_cells), _vp(cost), _vp(cell)))
+            R = self._team_n
+        return cost.reshape(-1)[: R * n].reshape(R, n).copy(), cell.reshape(-1)[: R * n].reshape(R, n).copy()
+
+    def plan_team_path(self, k: int, target_xy, snap_cells: int = 5, cap: int | None = None) -> np.ndarray:
+        """plan_path on robot k's field (dm_plan_team_path)."""
+        n = ctypes.c_int64(0)
+        size = 4096 if cap is None else int(cap)
+        with self._lock:
+            while True:
+                buf = np.empty(max(size, 1), np.int64)
+                rc = self._lib.dm_plan_team_path(self._handle(), int(k), float(target_xy[0]), float(target_xy[1]),
+                                                 int(snap_cells), _vp(buf), size, ctypes.byref(n))
+                if rc == _ffi.DM_ERR_CAPACITY and cap is None and n.value > size:
+                    size = int(n.value)
+                    continue
+                check(rc)
+                return buf[: int(n.value)].copy()
+
+    def assign_goals_team(self, robots_xy, min_size: int = 8, min_gain: int = 0, distance_weight: float = 1.0,
+                          min_distance: float = 0.0, inflate_cells: int = 2, max_cost: int = 0,
+                          snap_cells: int = 5, radius_cells: int = 0):
+        """Global-greedy goals (dm_assign_goals_team): the best (robot,
+        cluster) pair is assigned first, so the result does not depend on the
+        order of the robots.  radius_cells == 0 scores by cluster size as
+        assign_goals_path and returns, per robot, (cluster index, (x, y), cell)
+        or None; radius_cells >= 1 scores by information gain as
+        assign_goals_gain and returns (cluster index, (x, y), cell, gain).
+        Leaves the robots' team fields in the handle (plan_team_path).  Same
+        policy as dm.plan.assign_goals_team."""
+        rad = int(radius_cells)
+        got = self._assign(self._lib.dm_assign_goals_team, robots_xy,
+                           (int(min_size), int(min_gain), float(distance_weight), float(min_distance),
+                            int(inflate_cells), int(max_cost), int(snap_cells), rad), (np.int64, np.uint32))
+        self._team_n = len(got)
+        return got if rad != 0 else [g and g[:3] for g in got]
 
     # -- scan matching (csrc/dm_match.h; host restatement: dm/match.py) ----
     def match_field(self, smear_cells: int, kern) -> np.ndarray:

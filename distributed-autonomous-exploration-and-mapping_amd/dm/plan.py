@@ -27,6 +27,15 @@ Clearance-aware planning (dm_plan_clearance, dm_plan_field_cost):
 * entering cell c by a legal move costs ``b * (1 + pen[d2[c]])``, b = 5 / 7,
   for a caller-supplied uint8 table ``pen[R*R + 2]``;
 * the weighted field and its paths are defined as above with that move cost.
+
+Team planning (dm_plan_team, dm_assign_goals_team):
+
+* ``team_fields`` is ``field`` per robot, a robot's own cell being a source in
+  its own field only;
+* ``assign_goals_team`` scores like ``assign_goals_path`` (or, with a view
+  radius, ``dm.gain.assign_goals_gain``) and assigns the best (robot, cluster)
+  pair first, ties to the smaller label, then the smaller robot
+  (``global_greedy``).
 """
 from __future__ import annotations
 
@@ -325,3 +334,100 @@ def assign_goals_path(state, clusters: np.ndarray, robots_xy, origin_x: float, o
     got = _greedy_goals(st, clusters, cells, origin_x, origin_y, resolution, min_size, distance_weight, min_distance,
                         inflate_cells, max_cost, snap_cells, cache, lambda i, cell: int(clusters["size"][i]))
     return [g and g[:3] for g in got]
+
+
+# ---- team planning (dm_plan_team, dm_assign_goals_team) ----------------------
+TEAM_MAX = 64
+
+
+def team_fields(state, robot_cells, r: int, max_cost: int = 0) -> list[np.ndarray]:
+    """dm_plan_team: one field per robot cell (cx, cy), each `field` from that
+    cell alone.  A robot's own cell is traversable (with_sources) in its own
+    field only; the traversable mask is shared."""
+    cells = [(int(cx), int(cy)) for cx, cy in robot_cells]
+    if not 1 <= len(cells) <= TEAM_MAX:
+        raise ValueError(f"n_robots must be in [1, {TEAM_MAX}]")
+    trav = traversable(state, r)
+    return [field(state, [c], r, max_cost, trav=trav) for c in cells]
+
+
+def global_greedy(util: np.ndarray, labels) -> list[int]:
+    """The pick of dm_assign_goals_team over util [R, K] (-inf: not eligible):
+    among the pairs (r, c) with r unassigned and c untaken take the greatest
+    util, ties to the smaller label, then the smaller r; until no pair is
+    left.  Per robot the cluster index, or -1."""
+    u = np.array(util, np.float64)
+    R, K = u.shape
+    labels = np.asarray(labels)
+    out = [-1] * R
+    while True:
+        m = u.max() if u.size else -np.inf
+        if not np.isfinite(m):
+            return out
+        rs, cs = np.nonzero(u == m)
+        j = np.lexsort((rs, labels[cs]))[0]  # by label, then by robot
+        r, c = int(rs[j]), int(cs[j])
+        out[r] = c
+        u[r, :] = -np.inf
+        u[:, c] = -np.inf
+
+
+def assign_goals_team(state, clusters: np.ndarray, robots_xy, origin_x: float, origin_y: float, resolution: float,
+                      min_size: int = 8, min_gain: int = 0, distance_weight: float = 1.0, min_distance: float = 0.0,
+                      inflate_cells: int = 2, max_cost: int = 0, snap_cells: int = 5, radius_cells: int = 0):
+    """dm_assign_goals_team: the global-greedy assignment over the robots'
+    team fields.  radius_cells == 0: dist, eligibility and util of
+    assign_goals_path (numerator: the cluster's size), per robot (cluster
+    index, (x, y) centre of the snapped cell, snapped cell) or None;
+    radius_cells >= 1: those of dm.gain.assign_goals_gain (numerator: the
+    visible-unknown count of the snapped cell under that robot's field,
+    >= min_gain and > 0), per robot (index, (x, y), cell, gain) or None."""
+    if not float(distance_weight) >= 0.0:
+        raise ValueError("distance_weight must be >= 0 (dm_assign_goals_team rejects it too)")
+    gain_mode = int(radius_cells) != 0
+    if gain_mode:
+        from . import gain as _gain
+
+        R_view = _gain.check_radius(radius_cells)
+        if int(min_gain) < 0:
+            raise ValueError("min_gain must be >= 0")
+    st = np.asarray(state)
+    H, W = st.shape
+    cells = _robot_cells(robots_xy, origin_x, origin_y, resolution, W, H)
+    if len(cells) > TEAM_MAX:
+        raise ValueError(f"n_robots must be in [0, {TEAM_MAX}]")
+    if not cells or clusters is None or len(clusters) == 0:
+        return [None] * len(cells)
+    fields = team_fields(st, cells, inflate_cells, max_cost)
+    targets = [cell_of(float(c["cx_m"]), float(c["cy_m"]), origin_x, origin_y, resolution, W, H) for c in clusters]
+    K = len(clusters)
+    util = np.full((len(cells), K), -np.inf)
+    snapped = np.full((len(cells), K), -1, np.int64)
+    num = np.zeros((len(cells), K), np.int64)
+    gains: dict = {}
+    for r, f in enumerate(fields):
+        got = [snap(f, t, snap_cells) for t in targets]
+        cost = np.array([s[0] for s in got], np.uint32)
+        snapped[r] = [s[1] for s in got]
+        dist = cost.astype(np.float64) * float(resolution) / 5.0
+        if gain_mode:
+            for i, cell in enumerate(snapped[r]):
+                if cell >= 0:
+                    if cell not in gains:
+                        gains[cell] = _gain.visible_unknown(st, (int(cell % W), int(cell // W)), R_view)
+                    num[r, i] = gains[cell]
+        else:
+            num[r] = clusters["size"]
+        ok = (clusters["size"] >= min_size) & (cost != UNREACHABLE) & (dist >= min_distance) & (num[r] > 0)
+        if gain_mode:
+            ok &= num[r] >= int(min_gain)
+        util[r] = np.where(ok, num[r].astype(np.float64) / (1.0 + float(distance_weight) * dist), -np.inf)
+    out = []
+    for r, i in enumerate(global_greedy(util, clusters["label"])):
+        if i < 0:
+            out.append(None)
+            continue
+        cell = int(snapped[r, i])
+        xy = (origin_x + ((cell % W) + 0.5) * resolution, origin_y + ((cell // W) + 0.5) * resolution)
+        out.append((i, xy, cell, int(num[r, i])) if gain_mode else (i, xy, cell))
+    return out

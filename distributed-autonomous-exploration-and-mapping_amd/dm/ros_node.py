@@ -46,6 +46,10 @@ callback signatures:
   (``geometry_msgs/PoseArray``: the goals the other robots hold) and scores its
   own goal by what it would see that those goals do not
   (``dm_assign_goals_coord``);
+* with ``dm_team_poses_topic`` set (default off), subscribes the teammates'
+  poses (``geometry_msgs/PoseArray``) and publishes on ``/team_goals`` one goal
+  per robot, own pose first, from the global-greedy assignment over all of them
+  (``dm_assign_goals_team``);
 * with ``dm_peer_map_topic`` set (default off), subscribes a peer's
   ``nav_msgs/OccupancyGrid`` in the peer's own map frame and folds it into this
   map on the device (``dm_fuse_state``; the merge step of a multi-robot stack,
@@ -262,6 +266,12 @@ class SlamParams:
     # dm_goal_information_gain; off: as before
     dm_goal_coordinate: bool = False
     dm_peer_goals_topic: str = "/peer_goals"
+    # the teammates' poses (geometry_msgs/PoseArray in the map frame); when set,
+    # the node also publishes on /team_goals one goal per robot, own pose first,
+    # from the global-greedy assignment over all of them (dm_assign_goals_team:
+    # the best robot-frontier pair first, so no robot takes the frontier next to
+    # a teammate).  Uses the goal settings above; "": off, nothing changes.
+    dm_team_poses_topic: str = ""
     # a peer's map (nav_msgs/OccupancyGrid in the peer's map frame) folded into
     # this one on the device (dm_fuse_state); "": off.  Mode "fill" writes only
     # cells this map does not know yet, so a peer republishing its map every
@@ -465,7 +475,7 @@ class MappingNode:
 
     def __init__(self, params: SlamParams | None = None, pose_provider=None, map_publisher=None,
                  frontier_publisher=None, goal_publisher=None, clock=time.monotonic, gate: bool = True,
-                 mapper=None, plan_publisher=None, **overrides):
+                 mapper=None, plan_publisher=None, team_goals_publisher=None, **overrides):
         """`overrides` set SlamParams fields (tests: dm_width=..., ...).
         `mapper`: an object with OccupancyMapper's interface to use instead of
         creating one (tests inject CPU stand-ins)."""
@@ -496,6 +506,8 @@ class MappingNode:
         self.last_plan = None  # the Path of the last goal chosen by path length
         self.last_gain = None  # the gain of the last goal chosen with dm_goal_information_gain
         self.peer_goals = []   # (x, y) of the goals the peers hold (dm_goal_coordinate)
+        self.team_poses = []   # (x, y) of the teammates (dm_team_poses_topic)
+        self.team_goals_pub = team_goals_publisher or ListPublisher("/team_goals")
         self.clock = clock
         self._last_publish = -math.inf
         self._pass_stamp = None  # stamp of the frontier pass in flight (None: none)
@@ -566,6 +578,41 @@ class MappingNode:
         """dm_peer_goals_topic: the goals the other robots hold now; the next
         choose_goal with dm_goal_coordinate discounts what they will see."""
         self.peer_goals = [(float(p.position.x), float(p.position.y)) for p in msg.poses]
+
+    def team_poses_cb(self, msg):
+        """dm_team_poses_topic: where the teammates are now; the next
+        choose_team_goals assigns goals to this robot and to them together."""
+        self.team_poses = [(float(p.position.x), float(p.position.y)) for p in msg.poses]
+
+    def choose_team_goals(self, stamp: float | None = None):
+        """dm_team_poses_topic: the goals of this robot (first) and of its
+        teammates, in the order of the last team_poses message, from the
+        global-greedy assignment over the last published frontier clusters
+        (dm_assign_goals_team), with the node's goal settings; scored by
+        information gain with dm_goal_information_gain, else by size.  A
+        PoseArray in the map frame with one pose per robot, NaN position for a
+        robot without a goal; None when the topic is not set or there is no
+        pose or frontier result yet."""
+        s = self.slam
+        if not s.dm_team_poses_topic or self.last_frontiers is None or self.latest_pose is None:
+            return None
+        x, y, _ = self.latest_pose
+        robots = [(x, y)] + list(self.team_poses)
+        inflate, snap = s.goal_cells()
+        gain = s.dm_goal_information_gain or s.dm_goal_coordinate
+        goals = self.mapper.assign_goals_team(robots, min_size=s.dm_goal_min_size, min_gain=s.dm_goal_min_gain,
+                                              distance_weight=s.dm_goal_distance_weight,
+                                              min_distance=s.dm_goal_min_distance, inflate_cells=inflate,
+                                              snap_cells=snap, radius_cells=s.gain_radius_cells() if gain else 0)
+        msg = PoseArray(header=Header(stamp=self._last_publish if stamp is None else stamp, frame_id=s.map_frame))
+        for (rx, ry), g in zip(robots, goals):
+            if g is None:
+                msg.poses.append(Pose(position=Point(math.nan, math.nan, 0.0)))
+            else:
+                gx, gy = g[1]
+                msg.poses.append(Pose(position=Point(gx, gy, 0.0),
+                                      orientation=quaternion_from_yaw(math.atan2(gy - ry, gx - rx))))
+        return msg
 
     def align_peer(self, scan_msg, peer_pose) -> bool:
         """Find the peer's frame in ours from one of its scans: `scan_msg` was
@@ -801,6 +848,10 @@ class MappingNode:
                 self.goal_pub.publish(goal)
                 if self.last_plan is not None:
                     self.plan_pub.publish(self.last_plan)
+            if self.slam.dm_team_poses_topic:
+                team = self.choose_team_goals(stamp)
+                if team is not None:
+                    self.team_goals_pub.publish(team)
         return True
 
     def map_image_png(self) -> bytes:
@@ -900,11 +951,29 @@ def main(args=None):  # pragma: no cover - needs ROS 2
                 m.poses.append(q)
             plan_pub.publish(m)
 
+    team_pub = node.create_publisher(RosPoseArray, "/team_goals", 10) if sp.dm_team_poses_topic else None
+
+    class _TeamGoalsAdapter:
+        def publish(self, goals):
+            pa = RosPoseArray()
+            pa.header.frame_id = goals.header.frame_id
+            pa.header.stamp = node.get_clock().now().to_msg()
+            for g in goals.poses:
+                ps = RosPose()
+                ps.position.x, ps.position.y = g.position.x, g.position.y
+                ps.orientation.z, ps.orientation.w = g.orientation.z, g.orientation.w
+                pa.poses.append(ps)
+            team_pub.publish(pa)
+
     mn = MappingNode(sp, pose_provider=lookup, map_publisher=map_pub, frontier_publisher=_FrontierAdapter(),
-                     goal_publisher=_GoalAdapter(), plan_publisher=_PlanAdapter(), clock=lambda: node.get_clock().now().nanoseconds * 1e-9)
+                     goal_publisher=_GoalAdapter(), plan_publisher=_PlanAdapter(),
+                     team_goals_publisher=_TeamGoalsAdapter() if team_pub is not None else None,
+                     clock=lambda: node.get_clock().now().nanoseconds * 1e-9)
     node.create_subscription(RosLaserScan, sp.scan_topic, mn.scan_cb, 10)
     if sp.dm_goal_coordinate:
         node.create_subscription(RosPoseArray, sp.dm_peer_goals_topic, mn.peer_goals_cb, 10)
+    if sp.dm_team_poses_topic:
+        node.create_subscription(RosPoseArray, sp.dm_team_poses_topic, mn.team_poses_cb, 10)
     if sp.dm_peer_map_topic:
         node.create_subscription(RosGrid, sp.dm_peer_map_topic, mn.peer_map_cb, 10)
     # slam_toolbox publishes the map on its own period, not per scan

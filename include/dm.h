@@ -641,6 +641,76 @@ int dm_assign_goals_coord(dm_grid* g, const double* robots_xy, int32_t n_robots,
  * DM_ERR_STATE if neither call has run yet (or the last one failed). */
 int dm_gain_claimed(dm_grid* g, uint8_t* out);
 
+/* ---- Team planning: one distance field per robot, relaxed together, and a
+ * goal assignment that does not depend on the order of the robots.  The
+ * reference's robots explore independently (main.py:123-188); this is what a
+ * multi-robot task allocator starts from, the robot x target path-cost matrix.
+ * Conventions as the path planning block: synchronous, ordered after
+ * everything enqueued on the handle, whole-map handles only (a band or a
+ * dm_create_sharded handle: DM_ERR_INVALID_ARG), integers only, the map is
+ * read and never written and its version does not change.
+ *   Team field k of n_robots in [1, DM_PLAN_TEAM_MAX]: bit for bit what
+ *     dm_plan_field(&robots_xy[2k], 1, inflate_cells, max_cost) leaves on the
+ *     same map: the same moves, legality, max_cost saturation and
+ *     DM_PLAN_UNREACHABLE.  Robot k's own cell is traversable in field k
+ *     whatever its state, and in no other field: a robot on an unknown or
+ *     inflated cell opens no passage for its teammates.  Two robots may share
+ *     a cell.  A robot outside the grid: DM_ERR_INVALID_ARG.
+ *   The fields live in the handle beside dm_plan_field's, n_robots * height *
+ *     width * 4 bytes, allocated on first use and grown when a later call
+ *     needs more (DM_ERR_OOM if that fails; freed by dm_destroy), with the
+ *     team's own copy of the traversable bit rows.  The two results do not
+ *     disturb each other: dm_plan_team leaves what dm_plan_get_field,
+ *     dm_plan_query and dm_plan_path return, dm_plan_field (with any inflation)
+ *     leaves what the team readers return.  The fields are stamped with the
+ *     map's version: after any call that writes the map the three readers
+ *     return DM_ERR_STATE until dm_plan_team (or dm_assign_goals_team) ran again.
+ * Out of scope: a penalty-weighted team field (dm_plan_field_cost's move), a
+ * coordinated (marginal-gain, dm_assign_goals_coord's) team assignment, and
+ * sharded handles. */
+#define DM_PLAN_TEAM_MAX 64
+
+/* Compute the n_robots fields.  out_stats (may be NULL) receives
+ * [3 + n_robots]: [0] traversable cells (sources not counted), [1] rounds,
+ * [2] (field, tile) relaxations, [3 + k] reached cells of field k.  The
+ * rounds are the maximum over the fields, not their sum; the round bound is
+ * dm_plan_field's with one source, DM_PLAN_MAX_ROUNDS applies, and
+ * DM_ERR_INCOMPLETE leaves the handle with no team fields.  n_robots * tiles
+ * >= 2^31: DM_ERR_CAPACITY. */
+int dm_plan_team(dm_grid* g, const double* robots_xy, int32_t n_robots, int32_t inflate_cells,
+                 uint32_t max_cost, uint64_t* out_stats /* [3 + n_robots], may be NULL */);
+/* Field `robot`: out[height*width] row-major.  robot outside [0, n_robots) of
+ * the last dm_plan_team: DM_ERR_INVALID_ARG (here and in dm_plan_team_path). */
+int dm_plan_team_get_field(dm_grid* g, int32_t robot, uint32_t* out /* [height*width] */);
+/* The robot x target matrix: dm_plan_query's snap of target i under field r
+ * in out_cost[r * n + i], out_cell[r * n + i]. */
+int dm_plan_team_query(dm_grid* g, const double* targets_xy, int64_t n, int32_t snap_cells,
+                       uint32_t* out_cost /* [n_robots][n] */, int64_t* out_cell /* [n_robots][n] */);
+/* dm_plan_path on field `robot`: the same snap, predecessor rule, outputs
+ * and errors. */
+int dm_plan_team_path(dm_grid* g, int32_t robot, double tx, double ty, int32_t snap_cells,
+                      int64_t* out_cells, int64_t cap, int64_t* n_out);
+/* Global-greedy goals over the clusters of the last collected result, with
+ * dm_assign_goals' errors; n_robots in [0, DM_PLAN_TEAM_MAX].  Row r is robot
+ * r's team field and every centroid is snapped to it.  With radius_cells == 0
+ * dist, the eligibility tests and util are dm_assign_goals_path's (score by
+ * size; min_gain is not read, out_gain may be NULL and is not written); with
+ * radius_cells in [1, 511] they are dm_assign_goals_gain's: gain(r, c) is the
+ * visible-unknown count of c's snapped cell under r's field, gain >= min_gain,
+ * and a gain of 0 is never a goal.  Then, repeatedly: among the eligible pairs
+ * (r, c) with r unassigned and c untaken the one with the greatest util is
+ * assigned, ties to the smaller label, then the smaller r; until no pair is
+ * left.  So robot 0 does not take the frontier next to robot 1 only because
+ * it chooses first.  Outputs as dm_assign_goals_gain.  With n_robots == 1 the
+ * result is dm_assign_goals_path's / dm_assign_goals_gain's bit for bit.  The
+ * call leaves the team fields of these robots in the handle (dm_plan_team_path
+ * can follow it) and does not touch dm_plan_field's field. */
+int dm_assign_goals_team(dm_grid* g, const double* robots_xy, int32_t n_robots, int64_t min_size,
+                         int64_t min_gain, double distance_weight, double min_distance,
+                         int32_t inflate_cells, uint32_t max_cost, int32_t snap_cells,
+                         int32_t radius_cells /* 0: score by size */, int64_t* out_index,
+                         double* out_xy, int64_t* out_cell, uint32_t* out_gain /* may be NULL when radius_cells == 0 */);
+
 /* ---- Correlative scan matching against the device-resident map.  In the
  * reference the pose of a scan comes from slam_toolbox's correlative scan
  * matcher (slam_config.yaml:35 use_scan_matching; :50-53 the correlation
