@@ -254,9 +254,84 @@ static int dm_plan_launch_clear(dm_grid* g, int32_t clear_cells, const uint8_t* 
   return DM_OK;
 }
 
+// What the rounds of a relaxation work on: the single field's members of
+// dm_grid (plan_*) or the team's (team_*), and the two nouns of its error text.
+struct PlanRounds {
+  int32_t* list[2];
+  unsigned int* len;
+  uint32_t* stamp;
+  unsigned long long* stat;
+  const unsigned long long* host;      // the mapped words (dm_plan::HS_*) as the host reads them
+  volatile unsigned long long* hstat;  // and as k_plan_relax writes them
+  const char* what;                    // "distance field" / "team fields"
+  const char* items;                   // "tiles" / "(field, tile) items"
+};
+
+// The rounds of one relaxation, until the list runs empty; synchronous.
+// n_src: the sources of one field (the bound).  max_items: the longest list
+// there can be.  launch(round, grid): one round, k_plan_relax<., .> reading
+// r.list[round & 1] and appending to r.list[(round + 1) & 1].
+template <class Launch>
+static int dm_plan_run_rounds(dm_grid* g, const PlanRounds& r, int32_t n_src, int64_t max_items, const char* timer,
+                              Launch launch) {
+  using namespace dm_plan;
+  // Round bound.  Induction over rounds: after round k every cell whose
+  // shortest path crosses at most k tile borders holds its final cost (round
+  // k's visit of a tile relaxes it to its fixpoint against ring values that
+  // were final after round k - 1, and a tile whose ring changed is on the
+  // list).  A shortest path visits no cell twice, so it has fewer moves, and
+  // crosses fewer tile borders, than there are traversable cells T (sources
+  // included: T + n_src).  Two more rounds see the last lowered border cell's
+  // neighbours find nothing to lower and the list run empty; a visit that
+  // stops at its sweep bound (kMaxSweeps) lists its tile again, at most
+  // 4096 / kMaxSweeps + 1 = 5 visits for one ring state.  The team's fields
+  // settle side by side, each under this bound with its one source, so the
+  // team's rounds are the slowest field's.
+  // The traversable count is on the host after the first wait; until then
+  // the bound is the map's cell count.
+  const auto bound_of = [&](unsigned long long trav) { return (int64_t)(5 * (trav + (unsigned long long)n_src) + 2); };
+  int64_t bound = g->plan_max_rounds > 0 ? g->plan_max_rounds : bound_of((unsigned long long)(g->W * g->H));
+  // A visit holds 23.5 KB of LDS (6 workgroups in a CU's 160 KiB) and 4 waves
+  // of 112 VGPRs (4 waves per SIMD; the weighted kernel's 160 give 3):
+  // registers bound it at 4 resident workgroups per CU, the grid.  One field's
+  // list rarely fills that; with n fields the items of a round spread over
+  // all of it.
+  const unsigned grid = (unsigned)std::min<int64_t>(max_items, 4 * (int64_t)(g->n_cu > 0 ? g->n_cu : 256));
+  // The list length comes back through mapped host memory, read after a wait
+  // for the rounds enqueued so far; several rounds go out per wait (4, 8, 16,
+  // ...: short fields end after one wait, long ones pay ~ one wait per 32
+  // rounds), the launches after the list ran empty exit at once.
+  int64_t done = 0;
+  int batch = 4;
+  bool empty = false;
+  KernelTimer t;
+  while (!empty && done < bound) {
+    const int64_t nb = std::min<int64_t>(batch, bound - done);
+    dm_timer_begin(g, timer, &t);
+    for (int64_t k = 0; k < nb; ++k, ++done) {
+      launch((uint32_t)done, grid);
+      DM_HIP(hipGetLastError());
+    }
+    dm_timer_end(g, &t);
+    DM_HIP(hipStreamSynchronize(g->stream));
+    empty = r.host[HS_LEN] == 0ull;
+    if (g->plan_max_rounds <= 0) bound = std::min(bound, bound_of(r.host[HS_TRAV]));
+    batch = std::min(batch * 2, 32);
+  }
+  if (!empty) {  // the bound is reached: did the last round leave work?
+    unsigned int len[3];
+    DM_HIP(hipMemcpy(len, r.len, sizeof len, hipMemcpyDeviceToHost));
+    if (len[done % 3] != 0u)
+      return dm_set_error(DM_ERR_INCOMPLETE, "the %s did not settle within %lld rounds (%u %s still active)%s", r.what,
+                          (long long)bound, len[done % 3], r.items,
+                          g->plan_max_rounds > 0 ? "; DM_PLAN_MAX_ROUNDS is set" : "");
+  }
+  return DM_OK;
+}
+
 // The field from n source cells (host arrays: cells, and their distinct
 // tiles) over g->plan_trav; synchronous.  stats: [4] or nullptr.  weighted:
-// by k_plan_relax_w over g->plan_pen.
+// by k_plan_relax<true, false> over g->plan_pen.
 static int dm_plan_run_field(dm_grid* g, const int64_t* cells, int32_t n, const int32_t* tiles, int32_t n_tiles,
                       uint32_t max_cost, uint64_t* stats, bool weighted) {
   using namespace dm_plan;
@@ -277,60 +352,19 @@ static int dm_plan_run_field(dm_grid* g, const int64_t* cells, int32_t n, const 
   hipLaunchKernelGGL(k_plan_sources, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, g->plan_src, n, g->W, g->TX,
                      g->plan_travs, g->plan_cost);
   DM_HIP(hipGetLastError());
-  // Round bound.  Induction over rounds: after round k every cell whose
-  // shortest path crosses at most k tile borders holds its final cost (round
-  // k's visit of a tile relaxes it to its fixpoint against ring values that
-  // were final after round k - 1, and a tile whose ring changed is on the
-  // list).  A shortest path visits no cell twice, so it has fewer moves, and
-  // crosses fewer tile borders, than there are traversable cells T (sources
-  // included: T + n).  Two more rounds see the last lowered border cell's
-  // neighbours find nothing to lower and the list run empty; a visit that
-  // stops at its sweep bound (kMaxSweeps) lists its tile again, at most
-  // 4096 / kMaxSweeps + 1 = 5 visits for one ring state.
-  // The traversable count is on the host after the first wait; until then
-  // the bound is the map's cell count.
-  const auto bound_of = [&](unsigned long long trav) { return (int64_t)(5 * (trav + (unsigned long long)n) + 2); };
-  int64_t bound = g->plan_max_rounds > 0 ? g->plan_max_rounds : bound_of((unsigned long long)ncell);
-  // The list length comes back through mapped host memory, read after a wait
-  // for the rounds enqueued so far; several rounds go out per wait (4, 8, 16,
-  // ...: short fields end after one wait, long ones pay ~ one wait per 32
-  // rounds), the launches after the list ran empty exit at once.
-  const unsigned grid = (unsigned)std::min<int64_t>(g->NT, 4 * (int64_t)(g->n_cu > 0 ? g->n_cu : 256));
-  int64_t done = 0;
-  int batch = 4;
-  bool empty = false;
-  KernelTimer t;
-  while (!empty && done < bound) {
-    const int64_t nb = std::min<int64_t>(batch, bound - done);
-    dm_timer_begin(g, weighted ? "plan_relax_w" : "plan_relax", &t);
-    for (int64_t k = 0; k < nb; ++k, ++done) {
-      if (weighted)
-        hipLaunchKernelGGL(k_plan_relax_w, dim3(grid), dim3(kThreads), 0, s, g->plan_cost, g->plan_travs, g->plan_pen,
-                           g->W, g->H, g->TX, g->TY, max_cost, g->plan_list[done & 1], g->plan_list[(done + 1) & 1],
-                           g->plan_len, g->plan_stamp, (uint32_t)done, g->plan_stat, g->h_plan.dev());
-      else
-        hipLaunchKernelGGL(k_plan_relax, dim3(grid), dim3(kThreads), 0, s, g->plan_cost, g->plan_travs, g->W, g->H,
-                           g->TX, g->TY, max_cost, g->plan_list[done & 1], g->plan_list[(done + 1) & 1], g->plan_len,
-                           g->plan_stamp, (uint32_t)done, g->plan_stat, g->h_plan.dev());
-      DM_HIP(hipGetLastError());
-    }
-    dm_timer_end(g, &t);
-    DM_HIP(hipStreamSynchronize(s));
-    empty = g->h_plan[HS_LEN] == 0ull;
-    if (g->plan_max_rounds <= 0) bound = std::min(bound, bound_of(g->h_plan[HS_TRAV]));
-    batch = std::min(batch * 2, 32);
-  }
-  if (!empty) {  // the bound is reached: did the last round leave work?
-    unsigned int len[3];
-    DM_HIP(hipMemcpy(len, g->plan_len, sizeof len, hipMemcpyDeviceToHost));
-    if (len[done % 3] != 0u)
-      return dm_set_error(DM_ERR_INCOMPLETE, "the distance field did not settle within %lld rounds (%u tiles "
-                          "still active)%s", (long long)bound, len[done % 3],
-                          g->plan_max_rounds > 0 ? "; DM_PLAN_MAX_ROUNDS is set" : "");
-  }
+  const PlanRounds r = {{g->plan_list[0], g->plan_list[1]}, g->plan_len, g->plan_stamp, g->plan_stat, g->h_plan,
+                        g->h_plan.dev(), "distance field", "tiles"};
+  const auto kernel = weighted ? k_plan_relax<true, false> : k_plan_relax<false, false>;
+  const char* const timer = weighted ? "plan_relax_w" : "plan_relax";
+  int rc = dm_plan_run_rounds(g, r, n, g->NT, timer, [&](uint32_t k, unsigned grid) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, s, g->plan_cost, g->plan_travs,
+                       weighted ? g->plan_pen : nullptr, nullptr, g->W, g->H, g->TX, g->TY, max_cost, r.list[k & 1],
+                       r.list[(k + 1) & 1], r.len, r.stamp, k, r.stat, r.hstat);
+  });
+  if (rc) return rc;
   if (stats) {
-    hipLaunchKernelGGL(k_plan_count, dim3((unsigned)std::min<int64_t>((ncell + kThreads - 1) / kThreads, 1024)),
-                       dim3(kThreads), 0, s, g->plan_cost, ncell, g->plan_stat);
+    hipLaunchKernelGGL(k_plan_team_count, dim3((unsigned)std::min<int64_t>((ncell + kThreads - 1) / kThreads, 1024)),
+                       dim3(kThreads), 0, s, g->plan_cost, ncell, g->plan_stat + ST_REACHED);
     DM_HIP(hipGetLastError());
     unsigned long long st[4];
     DM_HIP(hipMemcpyAsync(st, g->plan_stat, sizeof st, hipMemcpyDeviceToHost, s));
@@ -340,17 +374,24 @@ static int dm_plan_run_field(dm_grid* g, const int64_t* cells, int32_t n, const 
   return DM_OK;
 }
 
-static int dm_plan_launch_query(dm_grid* g, const double* d_xy, int64_t stride, int64_t n, int32_t snap_cells,
-                         uint32_t* d_cost, int64_t* d_cell) {
-  if (n <= 0) return DM_OK;
+// snap n targets (d_xy, `stride` doubles apart) to the nr fields at d_field: [nr][n] into d_cost / d_cell
+static int dm_plan_launch_snap(dm_grid* g, const char* timer, const uint32_t* d_field, int32_t nr, const double* d_xy,
+                               int64_t stride, int64_t n, int32_t snap_cells, uint32_t* d_cost, int64_t* d_cell) {
+  if (n <= 0 || nr <= 0) return DM_OK;
   KernelTimer t;
-  dm_timer_begin(g, "plan_query", &t);
-  hipLaunchKernelGGL(dm_plan::k_plan_query, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, g->stream,
-                     g->plan_cost, g->W, g->H, g->p.origin_x, g->p.origin_y, g->p.resolution, d_xy, stride, n,
+  dm_timer_begin(g, timer, &t);
+  hipLaunchKernelGGL(dm_plan::k_plan_team_query, dim3((unsigned)((n * nr + 127) / 128)), dim3(128), 0, g->stream,
+                     d_field, nr, g->W, g->H, g->p.origin_x, g->p.origin_y, g->p.resolution, d_xy, stride, n,
                      snap_cells, d_cost, d_cell);
   DM_HIP(hipGetLastError());
   dm_timer_end(g, &t);
   return DM_OK;
+}
+
+// to the handle's single field
+static int dm_plan_launch_query(dm_grid* g, const double* d_xy, int64_t stride, int64_t n, int32_t snap_cells,
+                         uint32_t* d_cost, int64_t* d_cell) {
+  return dm_plan_launch_snap(g, "plan_query", g->plan_cost, 1, d_xy, stride, n, snap_cells, d_cost, d_cell);
 }
 
 // walk back from *d_start into g->plan_path (cap entries) by the rule of the
@@ -399,42 +440,14 @@ static int dm_plan_run_team(dm_grid* g, const int64_t* cells, int32_t n, int32_t
                      ncell, g->team_cost, g->team_list[0]);
   DM_HIP(hipGetLastError());
   dm_timer_end(g, &t);
-  // The round bound is dm_plan_run_field's with one source, per field: the
-  // fields settle side by side, so the team's rounds are the slowest field's.
-  const auto bound_of = [&](unsigned long long trav) { return (int64_t)(5 * (trav + 1ull) + 2); };
-  int64_t bound = g->plan_max_rounds > 0 ? g->plan_max_rounds : bound_of((unsigned long long)ncell);
-  // A visit holds 23.5 KB of LDS (6 workgroups in a CU's 160 KiB) and 4 waves
-  // of 112 VGPRs (4 waves per SIMD): registers bound it at 4 resident
-  // workgroups per CU, k_plan_relax's grid.  One field's list rarely fills
-  // that; with n fields the items of a round spread over all of it.
-  const unsigned grid =
-      (unsigned)std::min<int64_t>((int64_t)n * g->NT, 4 * (int64_t)(g->n_cu > 0 ? g->n_cu : 256));
-  int64_t done = 0;
-  int batch = 4;
-  bool empty = false;
-  while (!empty && done < bound) {
-    const int64_t nb = std::min<int64_t>(batch, bound - done);
-    dm_timer_begin(g, "plan_team_relax", &t);
-    for (int64_t k = 0; k < nb; ++k, ++done) {
-      hipLaunchKernelGGL(k_plan_relax_team, dim3(grid), dim3(kThreads), 0, s, g->team_cost, g->team_trav, g->team_src,
-                         g->W, g->H, g->TX, g->TY, max_cost, g->team_list[done & 1], g->team_list[(done + 1) & 1],
-                         g->team_len, g->team_stamp, (uint32_t)done, g->team_stat, g->h_team.dev());
-      DM_HIP(hipGetLastError());
-    }
-    dm_timer_end(g, &t);
-    DM_HIP(hipStreamSynchronize(s));
-    empty = g->h_team[HS_LEN] == 0ull;
-    if (g->plan_max_rounds <= 0) bound = std::min(bound, bound_of(g->h_team[HS_TRAV]));
-    batch = std::min(batch * 2, 32);
-  }
-  if (!empty) {  // the bound is reached: did the last round leave work?
-    unsigned int len[3];
-    DM_HIP(hipMemcpy(len, g->team_len, sizeof len, hipMemcpyDeviceToHost));
-    if (len[done % 3] != 0u)
-      return dm_set_error(DM_ERR_INCOMPLETE, "the team fields did not settle within %lld rounds (%u (field, tile) "
-                          "items still active)%s", (long long)bound, len[done % 3],
-                          g->plan_max_rounds > 0 ? "; DM_PLAN_MAX_ROUNDS is set" : "");
-  }
+  const PlanRounds r = {{g->team_list[0], g->team_list[1]}, g->team_len, g->team_stamp, g->team_stat, g->h_team,
+                        g->h_team.dev(), "team fields", "(field, tile) items"};
+  int rc = dm_plan_run_rounds(g, r, 1, (int64_t)n * g->NT, "plan_team_relax", [&](uint32_t k, unsigned grid) {
+    hipLaunchKernelGGL((k_plan_relax<false, true>), dim3(grid), dim3(kThreads), 0, s, g->team_cost, g->team_trav,
+                       nullptr, g->team_src, g->W, g->H, g->TX, g->TY, max_cost, r.list[k & 1], r.list[(k + 1) & 1],
+                       r.len, r.stamp, k, r.stat, r.hstat);
+  });
+  if (rc) return rc;
   if (stats) {
     dm_timer_begin(g, "plan_team_count", &t);
     hipLaunchKernelGGL(k_plan_team_count,
@@ -453,18 +466,11 @@ static int dm_plan_run_team(dm_grid* g, const int64_t* cells, int32_t n, int32_t
   return DM_OK;
 }
 
-// snap n targets (d_xy, `stride` doubles apart) to fields [r0, r0 + nr) of the team: [nr][n] into d_cost / d_cell
+// to fields [r0, r0 + nr) of the team
 static int dm_plan_launch_team_query(dm_grid* g, int32_t r0, int32_t nr, const double* d_xy, int64_t stride, int64_t n,
                                      int32_t snap_cells, uint32_t* d_cost, int64_t* d_cell) {
-  if (n <= 0 || nr <= 0) return DM_OK;
-  KernelTimer t;
-  dm_timer_begin(g, "plan_team_query", &t);
-  hipLaunchKernelGGL(dm_plan::k_plan_team_query, dim3((unsigned)((n * nr + 127) / 128)), dim3(128), 0, g->stream,
-                     g->team_cost + (int64_t)r0 * g->W * g->H, nr, g->W, g->H, g->p.origin_x, g->p.origin_y,
-                     g->p.resolution, d_xy, stride, n, snap_cells, d_cost, d_cell);
-  DM_HIP(hipGetLastError());
-  dm_timer_end(g, &t);
-  return DM_OK;
+  return dm_plan_launch_snap(g, "plan_team_query", g->team_cost + (int64_t)r0 * g->W * g->H, nr, d_xy, stride, n,
+                             snap_cells, d_cost, d_cell);
 }
 
 // walk back from *d_start on field `robot` into g->plan_path (cap entries):

@@ -530,7 +530,7 @@ struct dm_grid {
   GroupCap plan_qcap;
   DevBuf<int64_t> plan_path;       // a path, target first
   // dm_plan_field_cost: the per-cell penalty bytes pen[d2] the weighted field
-  // was relaxed over (k_plan_clear<true> writes them, k_plan_relax_w and the
+  // was relaxed over (k_plan_clear<true> writes them, k_plan_relax<true, .> and the
   // weighted k_plan_path read them), allocated on the first such call
   DevBuf<uint8_t> plan_pen;        // [H][W] row-major
   DevBuf<uint8_t> plan_pen_tab;    // [32 * 32 + 2] the caller's table
